@@ -8,7 +8,12 @@ rate is reported separately and in DESIGN.md).  With --gpus N every rank owns
 its own batch (independent windows => replicas, no data-path collective,
 "scaling": "weak"); timing is barrier + synchronize on both sides, max over ranks.
 
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` and
+A plain run (no --full) does only what `value` needs: it builds the batch, warms
+up, times --steps launches, optionally writes the last step's results
+(--dump-outputs DIR: one .npy per array, float64) and prints the contract
+fields.  Every other leg below runs only with --full.
+
+Rank 0 prints ONE JSON line; with --full it holds the contract fields plus `roofline` and
 `cpu_baseline` (the CPU oracle -- a port of the reference solve -- timed on a
 bounded sample of the same windows on this box's host cores: one thread, which
 is what the reference gives Ceres (estimator.cpp:985 leaves num_threads = 1), and
@@ -138,6 +143,26 @@ def project_large_window(measured_n):
     return out
 
 
+def dump_outputs(out_dir, states, reps):
+    """What a caller of uvs_batch_download receives after the last timed launch, window by window, as float64 .npy files
+    (256 windows: about 0.6 MB).  The per-window landmark arrays are concatenated in window order; n_points / n_lines give the split."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "pose": np.stack([s.pose for s in states]), "speedbias": np.stack([s.speedbias for s in states]),
+        "ex_pose": np.stack([s.ex_pose for s in states]), "td": np.array([s.td for s in states]), "relo_pose": np.stack([s.relo_pose for s in states]),
+        "n_points": np.array([len(s.inv_depth) for s in states]), "inv_depth": np.concatenate([s.inv_depth for s in states]),
+        "n_lines": np.array([len(s.line_orth) for s in states]), "line_orth": np.concatenate([s.line_orth.reshape(-1, 4) for s in states]),
+    }
+    for f in ("status", "termination", "num_iterations", "num_successful", "initial_cost", "final_cost"):
+        arrays[f] = np.array([getattr(r, f) for r in reps])
+    k = max(int(r.num_iterations) for r in reps) + 1
+    for f in ("cost", "candidate_cost", "model_cost_change", "relative_decrease", "radius", "step_norm", "gradient_max_norm", "accepted"):
+        # per-iteration trace, entries 0..num_iterations of each window (zero past its own count)
+        arrays[f] = np.array([list(getattr(r, f)[:r.num_iterations + 1]) + [0] * (k - 1 - r.num_iterations) for r in reps])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -152,7 +177,12 @@ def main():
     ap.add_argument("--no-large", action="store_true", help="skip the configs[3] large-window timing (profiling runs)")
     ap.add_argument("--no-scale-point", action="store_true", help="skip the 200 000-point window of the large_window leg (not a BASELINE config; ~30 s of generation and packing)")
     ap.add_argument("--no-fused-single", action="store_true", help="skip the multi-workgroup form of the single window (keeps a kernel trace of the configs[3] leg clean)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (roofline, single window, end-to-end stream, configs[3], replay, batch marginalization, "
+                                                        "CPU baseline); the --no-* switches above apply to these legs only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's results (rank 0's batch) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0")); local_rank = int(os.environ.get("LOCAL_RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     dist = None
@@ -203,11 +233,13 @@ def main():
     states, reps = solver.download()
     n_total = args.batch * world * args.steps
     value = n_total / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, states, reps)
 
     # ---- end to end (never `value`): a STREAM of fresh batches through uvs_batch_stream -- host packing (threads), H2D, solve, D2H of consecutive
     # batches overlapped on two buffer sets.  The same 256 windows are packed and uploaded again for every batch (nothing is cached between batches).
     end_to_end = None
-    if rank == 0 and not args.no_stream:
+    if rank == 0 and args.full and not args.no_stream:
         nb = 32
         try:
             _, sreps, _ = solver.stream(windows * 6, args.batch, want_states=False)      # warm-up: every buffer set twice (the first batch of a set sizes its pinned staging buffer, the second packs in place)
@@ -228,7 +260,7 @@ def main():
 
     # ---- BASELINE configs[3]: ONE window with 20 000 points + 5 000 lines, landmarks sharded k mod N over the ranks (all ranks take part)
     large = None
-    if not args.no_large:
+    if args.full and not args.no_large:
         wl = synth.make_window(70, n_points=20000, n_lines=5000, n_tagged=3750)
         shard = synth.shard_landmarks(wl, rank, world)[0] if world > 1 else wl
         sl = api.Solver(device=local_rank, max_batch=1, max_points=20008, max_point_obs=240000, max_lines=5008, max_line_obs=60000)
@@ -304,8 +336,22 @@ def main():
             except Exception as e:
                 large["ten_times_the_landmarks"] = {"error": repr(e)}
 
+    out = None
     if rank == 0:
         its = np.array([r.num_iterations for r in reps])
+        out = {
+            "metric": "sliding-window solves/sec (10 KF, 150 pts, 40 lines, 3 VP)", "value": value, "unit": "solves/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"W10-P150-L40-V3 x {args.batch} independent windows per GPU (BASELINE configs[2]); "
+                                   "single window (configs[1]) in single_window, the 20k-point window (configs[3]) in large_window (both with --full)",
+                       "windows_per_gpu": args.batch, "frames": 11, "points": 150, "lines": 40, "vp_tagged_lines": 30,
+                       "prior": (not args.no_prior), "max_lm_iterations": 10, "parallelism": f"replicas x{world}"},
+            "lm_iterations_mean": float(its.mean()), "lm_successful_steps_mean": float(np.mean([r.num_successful for r in reps])), "final_cost_mean": float(np.mean([r.final_cost for r in reps])),
+            "batch_pack_upload_ms": pack_upload_ms,
+        }
+
+    if rank == 0 and args.full:
         bytes_per_launch = float(sum(synth.algorithmic_bytes(w) for w in windows))
         flops_per_launch = float(sum(algorithmic_flops(w, int(r.num_iterations)) for w, r in zip(windows, reps)))
         flops_executed = float(sum(algorithmic_flops(w, int(r.num_iterations), int(r.num_successful)) for w, r in zip(windows, reps)))
@@ -530,19 +576,12 @@ def main():
                                       "and factors its n x n Schur complement (k_marg_finish: parallel cyclic Jacobi, csrc/uvs_marg_kernel.h); the one-window call finishes on a host core")
             except Exception as e:      # (a secondary leg must never cost the bench line)
                 marg_batch = {"error": repr(e)}
-        out = {
-            "metric": "sliding-window solves/sec (10 KF, 150 pts, 40 lines, 3 VP)", "value": value, "unit": "solves/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"W10-P150-L40-V3 x {args.batch} independent windows per GPU (BASELINE configs[2]); "
-                                   "single window (configs[1]) in single_window, the 20k-point window (configs[3]) in large_window",
-                       "windows_per_gpu": args.batch, "frames": 11, "points": 150, "lines": 40, "vp_tagged_lines": 30,
-                       "prior": (not args.no_prior), "max_lm_iterations": 10, "parallelism": f"replicas x{world}"},
-            "lm_iterations_mean": float(its.mean()), "lm_successful_steps_mean": float(np.mean([r.num_successful for r in reps])), "final_cost_mean": float(np.mean([r.final_cost for r in reps])),
-            "batch_pack_upload_ms": pack_upload_ms, "value_end_to_end": (end_to_end or {}).get("solves_per_s"), "end_to_end": end_to_end,
+        out.update({
+            "value_end_to_end": (end_to_end or {}).get("solves_per_s"), "end_to_end": end_to_end,
             "single_window": single, "single_window_ms": sw_ms, "single_window_solves_per_s": 1e3 / sw_ms, "single_window_pcie_inclusive_ms": pcie * 1e3,
             "replay": replay, "marginalization_batch": marg_batch, "large_window": large, "roofline": roofline, "cpu_baseline": cpu,
-        }
+        })
+    if rank == 0:
         print(json.dumps(out))
     solver.close()
     if dist is not None:

@@ -7,8 +7,8 @@ set -u
 TAG=${1:-r01}
 R=$(pwd)
 export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-replay --no-large --no-stream"
-LCMD="python $R/bench.py --steps 2 --warmup 1 --batch 4 --no-cpu-baseline --no-replay --no-fused-single --no-stream --no-scale-point"      # the configs[3] window through the fused loop (kernel trace only)
+CMD="python $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-replay --no-large --no-stream"
+LCMD="python $R/bench.py --steps 2 --warmup 1 --batch 4 --full --no-cpu-baseline --no-replay --no-fused-single --no-stream --no-scale-point"      # the configs[3] window through the fused loop (kernel trace only)
 cd /tmp
 rm -rf $R/gpurun_out/prof_kt $R/gpurun_out/prof_fetch $R/gpurun_out/prof_write $R/gpurun_out/prof_sq $R/gpurun_out/prof_sq2
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt -o runc -- $CMD > $R/gpurun_out/prof_kt.log 2>&1
@@ -33,8 +33,8 @@ UVS_KSOLVE_NT=256 python tests/gpu_debug_prior.py > gpurun_out/${TAG}_phase_cycl
 # per-wave step log of one LM iteration (second linearization of the canonical window with its prior), both instantiations
 UVS_DEBUG_LIN_TIMELINE=$R/gpurun_out/${TAG}_tl512.bin python tests/gpu_debug_prior.py > /dev/null 2>&1; python tools/lin_timeline.py gpurun_out/${TAG}_tl512.bin 2 > gpurun_out/${TAG}_lin_timeline.txt 2>&1
 UVS_KSOLVE_NT=256 UVS_DEBUG_LIN_TIMELINE=$R/gpurun_out/${TAG}_tl256.bin python tests/gpu_debug_prior.py > /dev/null 2>&1; echo "---- UVS_KSOLVE_NT=256" >> gpurun_out/${TAG}_lin_timeline.txt; python tools/lin_timeline.py gpurun_out/${TAG}_tl256.bin 2 >> gpurun_out/${TAG}_lin_timeline.txt 2>&1
-# same-box A/B of the two instantiations (batch of 256 + one window), twice each
-for rep_ in 1 2; do for nt_ in 512 256; do UVS_KSOLVE_NT=$nt_ python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-replay --no-large --no-stream 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('UVS_KSOLVE_NT=$nt_', 'batch ms %.4f (kernel %.4f) value %.0f  single window %.4f ms' % (d['ms_per_step'], d['roofline']['kernel_ms_per_launch'], d['value'], d['single_window_ms']))"; done; done > gpurun_out/${TAG}_ab_512_vs_256_threads.txt 2>&1
+# same-box A/B of the two instantiations (batch of 256 + one window), twice each; the summary is written straight to profiles/
+for rep_ in 1 2; do for nt_ in 512 256; do UVS_KSOLVE_NT=$nt_ python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-replay --no-large --no-stream 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('UVS_KSOLVE_NT=$nt_', 'batch ms %.4f (kernel %.4f) value %.0f  single window %.4f ms' % (d['ms_per_step'], d['roofline']['kernel_ms_per_launch'], d['value'], d['single_window_ms']))"; done; done > profiles/${TAG}_ab_512_vs_256_threads.txt 2>&1
 python tools/batch_tail.py > gpurun_out/${TAG}_batch_tail.txt 2>&1
 python tools/large_timeline.py config3 > gpurun_out/${TAG}_large_timeline.txt 2>&1; python tools/large_timeline.py canonical >> gpurun_out/${TAG}_large_timeline.txt 2>&1
 bash tools/pmc_icache.sh > gpurun_out/${TAG}_icache_l2_counters.txt 2>&1

@@ -1,7 +1,7 @@
 """Turns the rocprofv3 CSVs under gpurun_out/ into the small summaries committed under profiles/.
 
 Collected on MI355X with (each PMC group in its own pass, per MI355X_MICROARCH.md):
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_kt -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline
+  rocprofv3 --kernel-trace --stats --output-format csv -d <trace dir>/prof_kt -- python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline
   rocprofv3 --pmc FETCH_SIZE --kernel-trace ...   rocprofv3 --pmc WRITE_SIZE --kernel-trace ...   rocprofv3 --pmc SQ_... --kernel-trace ...
 """
 import collections, csv, glob, json, os, sys
