@@ -390,6 +390,63 @@ int uvs_large_solve_fused(uvs_solver *s, const uvs_window *w, uvs_state *out, uv
 /* ---- size helpers for callers that serialise windows ---- */
 int uvs_reduced_dim(const uvs_options *opts);  /* 165 (+6 if estimate_extrinsic) */
 
+/* ---- 4-DoF pose graph of loop closure (reference pose_graph/src/pose_graph.cpp:403-579, PoseGraph::optimize4DoF) ----
+ * The caller passes the keyframes of the solve in list order -- first_looped_index .. cur_index of the reference -- as local indices 0 .. n-1.
+ * Each keyframe is (yaw in DEGREES, t); yaw, pitch and roll are Utility::R2ypr of q.  Pitch and roll are never variables.  Keyframe i is
+ * constant when constant[i] != 0 (the reference: index == first_looped_index or sequence == 0).  The library builds the sequential edges
+ * itself, exactly as the reference does: FourDOFError (i-j, i) for j = 1..4 when both have the same sequence, measured from the initial poses
+ * (rel_t = R(q_{i-j})^T (t_i - t_{i-j}), rel_yaw = yaw_i - yaw_{i-j}, pitch / roll of i-j), no loss.  Loop edge l is
+ * FourDOFWeightError (old, cur) with HuberLoss(0.1), yaw residual / 10, pitch / roll of the initial pose of `old`.  Solver: Ceres LM with
+ * max_num_iterations = 5 and otherwise the defaults of uvs_default_options(), an exact solve of the damped normal
+ * equations.  Edges whose two keyframes are both constant are not part of the problem (Ceres drops them from its reduced program): the costs
+ * reported here are those of the other edges.  No CPU path: uvs_pg_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_PG_MAX_KEYFRAMES 65536            /* largest max_keyframes uvs_pg_create takes */
+#define UVS_PG_MAX_LOOPS 256                  /* largest max_loops uvs_pg_create takes      */
+typedef struct uvs_pose_graph uvs_pose_graph;  /* opaque: device buffers, stream */
+
+typedef struct uvs_pg_loop {
+    int32_t cur;                       /* local index of the keyframe that has the loop  (pose_graph.cpp:516-530) */
+    int32_t old;                       /* local index of its loop_index keyframe, 0 <= old < cur */
+    double rel_t[3];                   /* loop_info(0..2): t of cur in the frame of old    */
+    double rel_yaw;                    /* loop_info(7), degrees                            */
+} uvs_pg_loop;
+
+typedef struct uvs_pg_problem {
+    int32_t n;                         /* keyframes, >= 1 */
+    int32_t n_loops;                   /* loop edges, >= 0 */
+    const double *t;                   /* [n][3] initial (VIO) translation */
+    const double *q;                   /* [n][4] initial (VIO) rotation, (x, y, z, w) */
+    const int32_t *sequence;           /* [n] */
+    const int32_t *constant;           /* [n] != 0: yaw and t held fixed */
+    const uvs_pg_loop *loops;          /* [n_loops] */
+} uvs_pg_problem;
+
+/* Entry 0 of the arrays is the initial evaluation, entry k >= 1 LM iteration k (as in uvs_report). */
+typedef struct uvs_pg_report {
+    int32_t status;                    /* UVS_OK / UVS_ERR_NUMERIC */
+    int32_t termination;               /* UVS_TERM_* */
+    int32_t num_iterations;
+    int32_t num_successful;
+    int32_t n_free;                    /* keyframes that are variables */
+    int32_t n_edges;                   /* sequential + loop edges in the problem */
+    int32_t n_loop_columns;            /* 4 x loop edges with two free ends (the low-rank part of the normal equations) */
+    int32_t reserved;
+    double initial_cost;
+    double final_cost;
+    double cost[UVS_MAX_ITER + 1];
+    double candidate_cost[UVS_MAX_ITER + 1];
+    double model_cost_change[UVS_MAX_ITER + 1];
+    double radius[UVS_MAX_ITER + 1];
+    int32_t accepted[UVS_MAX_ITER + 1];        /* 1 accepted, 0 rejected, -1 invalid step */
+} uvs_pg_report;
+
+int uvs_pg_create(int device, int max_keyframes, int max_loops, uvs_pose_graph **out);
+void uvs_pg_destroy(uvs_pose_graph *pg);
+const char *uvs_pg_last_error(const uvs_pose_graph *pg);
+/* out_yaw_t[n][4] = (yaw in degrees, tx, ty, tz) after the solve, every keyframe (constant ones unchanged).  UVS_ERR_INVALID_ARG: null pointer,
+ * n < 1, or a loop outside 0 <= old < cur < n; UVS_ERR_CAPACITY: n or n_loops above the handle's capacity. */
+int uvs_pg_optimize(uvs_pose_graph *pg, const uvs_pg_problem *problem, double *out_yaw_t, uvs_pg_report *report);
+
 #ifdef __cplusplus
 }
 #endif

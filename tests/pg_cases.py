@@ -1,0 +1,124 @@
+"""Pose-graph problems for the tests of the 4-DoF optimizer (uvs_pg_*): MH_05 keyframes from tests/golden/mh05_groundtruth.npz with a seeded
+yaw + translation random-walk drift (the VIO estimate), loop edges from ground-truth revisits, and small synthetic edge cases."""
+import importlib
+import os
+
+import numpy as np
+
+import pg_ref
+
+uvs = importlib.import_module("uv-slam_amd")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def Rz(deg):
+    return pg_ref.ypr2R(deg, 0.0, 0.0)
+
+
+def mh05_keyframes(rate_hz):
+    """Ground-truth keyframes every 1 / rate_hz seconds: stamps, p [n, 3], R [n, 3, 3]."""
+    gt = uvs.trajectory.load_groundtruth_fixture(os.path.join(GOLDEN, "mh05_groundtruth.npz"))
+    t0, t1 = gt["t"][0], gt["t"][-1]
+    stamps = t0 + np.arange(int(np.floor((t1 - t0) * rate_hz)) + 1) / rate_hz
+    idx = np.clip(np.searchsorted(gt["t"], stamps, side="right") - 1, 0, len(gt["t"]) - 1)
+    qw = gt["q_wxyz"][idx]
+    q = np.concatenate([qw[:, 1:], qw[:, :1]], 1)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    return stamps, gt["p"][idx].copy(), pg_ref.quat_to_R(q)
+
+
+def drift(p, R, seed, yaw_sigma=0.05, t_sigma=0.003):
+    """VIO-like estimate: every relative motion rotated by an accumulated yaw random walk (deg) plus a translation random walk (m)."""
+    rng = np.random.default_rng(seed)
+    n = len(p)
+    psi = np.cumsum(rng.normal(0.0, yaw_sigma, n)); psi -= psi[0]
+    dt = np.cumsum(rng.normal(0.0, t_sigma, (n, 3)), 0); dt -= dt[0]
+    pv = np.empty_like(p); Rv = np.empty_like(R)
+    pv[0] = p[0]; Rv[0] = R[0]
+    for k in range(1, n):
+        Rk = Rz(psi[k])
+        pv[k] = pv[k - 1] + Rk @ (p[k] - p[k - 1]) + (dt[k] - dt[k - 1])
+        Rv[k] = Rk @ R[k]
+    return pv, Rv
+
+
+def revisit_loops(stamps, p, R, seed, radius=0.7, min_gap=20.0, t_noise=0.01, yaw_noise=0.2):
+    """At most one loop edge per keyframe: to the nearest earlier keyframe within `radius` m and more than `min_gap` s before.
+    Measurement = the true relative pose (t in the old keyframe's frame, yaw difference) with small noise."""
+    rng = np.random.default_rng(seed)
+    ypr = pg_ref.R2ypr(R)
+    loops = []
+    for k in range(len(p)):
+        cand = np.flatnonzero(stamps < stamps[k] - min_gap)
+        if len(cand) == 0:
+            continue
+        d = np.linalg.norm(p[cand] - p[k], axis=1)
+        if d.min() >= radius:
+            continue
+        j = int(cand[np.argmin(d)])
+        rel_t = R[j].T @ (p[k] - p[j]) + rng.normal(0.0, t_noise, 3)
+        rel_yaw = float(pg_ref.normalize_angle(ypr[k, 0] - ypr[j, 0] + rng.normal(0.0, yaw_noise)))
+        loops.append((k, j, rel_t, rel_yaw))
+    return loops
+
+
+def window(p, R, loops, sequence=None, constant_seq0=True):
+    """The keyframes of one optimize4DoF call: from the earliest loop's old keyframe to the last keyframe with a loop, in local indices.
+    Constant: the first one and every sequence-0 keyframe.  -> dict(t, q, sequence, constant, loops, first, last)."""
+    first = min(j for _, j, _, _ in loops); last = max(k for k, _, _, _ in loops)
+    seq = np.ones(len(p), np.int32) if sequence is None else np.asarray(sequence, np.int32)
+    sl = slice(first, last + 1)
+    const = (seq[sl] == 0).astype(np.int32) if constant_seq0 else np.zeros(last + 1 - first, np.int32)
+    const[0] = 1
+    return dict(t=p[sl].copy(), q=pg_ref.R_to_quat(R[sl]), sequence=seq[sl].copy(), constant=const,
+                loops=[(k - first, j - first, rt, ry) for k, j, rt, ry in loops], first=first, last=last)
+
+
+def mh05_case(rate_hz, seed=3, outliers=0):
+    stamps, p, R = mh05_keyframes(rate_hz)
+    pv, Rv = drift(p, R, seed)
+    loops = revisit_loops(stamps, p, R, seed + 100)
+    if outliers:
+        rng = np.random.default_rng(seed + 200)
+        for l in rng.choice(len(loops), outliers, replace=False):
+            k, j, rt, ry = loops[l]
+            loops[l] = (k, j, rt + rng.normal(0.0, 1.5, 3), float(pg_ref.normalize_angle(ry + rng.choice([-1, 1]) * rng.uniform(10, 25))))
+    w = window(pv, Rv, loops)
+    w.update(stamps=stamps[w["first"]:w["last"] + 1], p_true=p[w["first"]:w["last"] + 1])
+    return w
+
+
+def two_sequence_case(seed=5):
+    """Sequence 0 = the first half of MH_05 at 2 keyframes/s with its true poses (a constant base map); sequence 1 = the second half,
+    drifted, in a frame turned by 25 deg and moved by (1, -2, 0.3) m, attached to sequence 0 by loop edges only."""
+    stamps, p, R = mh05_keyframes(2.0)
+    h = len(p) // 2
+    pv, Rv = drift(p[h:], R[h:], seed)
+    S = Rz(25.0); off = np.array([1.0, -2.0, 0.3])
+    pv = (S @ pv.T).T + off; Rv = S @ Rv
+    P = np.concatenate([p[:h], pv]); RR = np.concatenate([R[:h], Rv])
+    seq = np.r_[np.zeros(h, np.int32), np.ones(len(p) - h, np.int32)]
+    loops = [lp for lp in revisit_loops(stamps, p, R, seed + 100, min_gap=5.0) if lp[0] >= h]
+    return window(P, RR, loops, sequence=seq)
+
+
+def chain_case(n, seed, yaw0=0.0, n_loops=2):
+    """A small synthetic chain (one sequence) with drift; yaw0 turns the whole path (170 deg puts the yaws across +-180)."""
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(0.0, 2 * np.pi, n, endpoint=False)
+    p = np.stack([2 * np.cos(ang), 2 * np.sin(ang), 0.1 * np.sin(3 * ang)], 1)
+    R = np.stack([pg_ref.ypr2R(yaw0 + np.degrees(a) + 90.0, rng.normal(0, 2), rng.normal(0, 2)) for a in ang])
+    p = (Rz(yaw0) @ p.T).T
+    stamps = np.arange(n, dtype=float)
+    pv, Rv = drift(p, R, seed, yaw_sigma=0.5, t_sigma=0.01)
+    ypr = pg_ref.R2ypr(R)
+    loops = []
+    for k in range(n - n_loops, n):
+        j = k - (n - n_loops)
+        loops.append((k, j, R[j].T @ (p[k] - p[j]), float(pg_ref.normalize_angle(ypr[k, 0] - ypr[j, 0]))))
+    const = np.zeros(n, np.int32); const[0] = 1
+    return dict(t=pv, q=pg_ref.R_to_quat(Rv), sequence=np.ones(n, np.int32), constant=const, loops=loops)
+
+
+def positions_ate(P_est, P_true):
+    return uvs.sequence.ate(P_est, P_true)

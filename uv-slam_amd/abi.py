@@ -371,3 +371,52 @@ class Eval:
         for name in ("pt_r", "pt_J", "ln_r", "ln_J", "vp_r", "vp_J", "imu_r", "imu_J", "prior_r", "pt_Jtd"):
             setattr(e, name, _dp(getattr(self, name)))
         return e
+
+
+# ---- 4-DoF pose graph of loop closure (uvs_pg_*, include/uvs_solver.h) ------------------------------------------------
+PG_MAX_KEYFRAMES = 65536
+PG_MAX_LOOPS = 256
+
+
+class PgLoop(C.Structure):
+    _fields_ = [("cur", C.c_int32), ("old", C.c_int32), ("rel_t", C.c_double * 3), ("rel_yaw", C.c_double)]
+
+
+class PgProblem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_loops", C.c_int32), ("t", c_double_p), ("q", c_double_p), ("sequence", c_int_p), ("constant", c_int_p),
+                ("loops", C.POINTER(PgLoop))]
+
+
+class PgReport(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("termination", C.c_int32), ("num_iterations", C.c_int32), ("num_successful", C.c_int32),
+        ("n_free", C.c_int32), ("n_edges", C.c_int32), ("n_loop_columns", C.c_int32), ("reserved", C.c_int32),
+        ("initial_cost", C.c_double), ("final_cost", C.c_double),
+        ("cost", C.c_double * (MAX_ITER + 1)), ("candidate_cost", C.c_double * (MAX_ITER + 1)),
+        ("model_cost_change", C.c_double * (MAX_ITER + 1)), ("radius", C.c_double * (MAX_ITER + 1)),
+        ("accepted", C.c_int32 * (MAX_ITER + 1)),
+    ]
+
+    def trace(self):
+        k = self.num_iterations + 1
+        f = lambda a: np.array(a[:k])
+        return dict(cost=f(self.cost), candidate_cost=f(self.candidate_cost), model_cost_change=f(self.model_cost_change), radius=f(self.radius),
+                    accepted=np.array(self.accepted[:k]))
+
+
+def pg_problem(t, q, sequence, constant, loops):
+    """(PgProblem, keepalive).  t [n,3], q [n,4] (x,y,z,w), sequence / constant [n], loops = iterable of (cur, old, rel_t[3], rel_yaw)."""
+    k = dict(t=np.ascontiguousarray(t, dtype=np.float64).reshape(-1, 3), q=np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 4),
+             sequence=np.ascontiguousarray(sequence, dtype=np.int32), constant=np.ascontiguousarray(constant, dtype=np.int32))
+    loops = list(loops)
+    arr = (PgLoop * max(len(loops), 1))()
+    for l, (cur, old, rel_t, rel_yaw) in enumerate(loops):
+        arr[l].cur, arr[l].old, arr[l].rel_yaw = int(cur), int(old), float(rel_yaw)
+        for c in range(3):
+            arr[l].rel_t[c] = float(rel_t[c])
+    k["loops"] = arr
+    p = PgProblem()
+    p.n, p.n_loops = len(k["t"]), len(loops)
+    p.t, p.q, p.sequence, p.constant = _dp(k["t"]), _dp(k["q"]), _ip(k["sequence"]), _ip(k["constant"])
+    p.loops = C.cast(arr, C.POINTER(PgLoop))
+    return p, k

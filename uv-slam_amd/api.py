@@ -19,7 +19,7 @@ _lib = None
 EXPORTS = [
     "uvs_abi_version", "uvs_default_options", "uvs_create", "uvs_destroy", "uvs_last_error", "uvs_status_string",
     "uvs_solve_window", "uvs_batch_upload", "uvs_batch_solve", "uvs_batch_download", "uvs_batch_stream", "uvs_evaluate", "uvs_marginalize", "uvs_marginalize_resident", "uvs_marginalize_batch",
-    "uvs_reduced_dim",
+    "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize",
 ]
 
 
@@ -72,6 +72,10 @@ def lib():
         L.uvs_large_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p]; L.uvs_large_comm_init.restype = C.c_int
         L.uvs_large_comm_destroy.argtypes = [C.c_void_p]; L.uvs_large_comm_destroy.restype = None
         L.uvs_large_solve_fused.argtypes = [C.c_void_p, C.POINTER(abi.WindowC), C.POINTER(abi.StateC), C.POINTER(abi.Report), C.POINTER(C.c_float)]; L.uvs_large_solve_fused.restype = C.c_int
+        L.uvs_pg_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_pg_create.restype = C.c_int
+        L.uvs_pg_destroy.argtypes = [C.c_void_p]; L.uvs_pg_destroy.restype = None
+        L.uvs_pg_last_error.argtypes = [C.c_void_p]; L.uvs_pg_last_error.restype = C.c_char_p
+        L.uvs_pg_optimize.argtypes = [C.c_void_p, C.POINTER(abi.PgProblem), abi.c_double_p, C.POINTER(abi.PgReport)]; L.uvs_pg_optimize.restype = C.c_int
         _lib = L
     return _lib
 
@@ -309,3 +313,44 @@ class Solver:
         self._check(lib().uvs_debug_first_iteration(self._h, C.byref(wc), *[abi._dp(a) for a in (S, g, hd, dd, step, scal)]))
         return dict(S=S, g=g, hd=hd, dd=dd, step=step, cost=scal[0], gmax=scal[1], chol_ok=scal[2], mcc=scal[3], step2=scal[4],
                     cycles=dict(zip(['setup', 'obs', 'lmprep', 'gather', 'assemble', 'chol', 'trsv', 'backsub', 'cost', 'misc', 'chol_diag', 'chol_panel', 'chol_trail', 'asm_imu', 'asm_zero', 'asm_add'], scal[8:24])), sub_timers=dict(cost_phase=dict(zip(['stage_dx', 'prior_residual', 'observations', 'imu'], scal[24:28])), chol_busy_per_wave=scal[28:32].copy()))
+
+
+class PoseGraphSolver:
+    """Owns one `uvs_pose_graph` handle: the 4-DoF pose-graph optimizer of loop closure (PoseGraph::optimize4DoF) on one GPU.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    def __init__(self, device=0, max_keyframes=16384, max_loops=256):
+        self._h = C.c_void_p()
+        rc = lib().uvs_pg_create(device, max_keyframes, max_loops, C.byref(self._h))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_pg_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
+
+    def close(self):
+        if self._h:
+            lib().uvs_pg_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def optimize_raw(self, t, q, sequence, constant, loops):
+        """-> (return code, yaw_t [n, 4], report) without raising: for the tests of the argument checks."""
+        p, keep = abi.pg_problem(t, q, sequence, constant, loops)
+        out = np.zeros((max(p.n, 1), 4))
+        rep = abi.PgReport()
+        t0 = time.perf_counter()
+        rc = lib().uvs_pg_optimize(self._h, C.byref(p), abi._dp(out), C.byref(rep))
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: upload, every LM iteration, download
+        return rc, out[:p.n], rep
+
+    def optimize(self, t, q, sequence, constant, loops):
+        """t [n,3], q [n,4] (x,y,z,w) initial poses, sequence [n], constant [n], loops = [(cur, old, rel_t[3], rel_yaw deg)] in local indices.
+        -> (yaw_t [n, 4] = (yaw deg, tx, ty, tz), abi.PgReport)."""
+        rc, out, rep = self.optimize_raw(t, q, sequence, constant, loops)
+        if rc not in (abi.UVS_OK, abi.UVS_ERR_NUMERIC):
+            raise RuntimeError(f"uvs_pg_optimize: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
+        return out, rep

@@ -1,0 +1,150 @@
+// pose_graph.cpp -- see pose_graph.h.  Reference line numbers are those of pose_graph/src/pose_graph.cpp.
+#include "pose_graph.h"
+#include <cmath>
+#include <cstdio>
+#include <stdexcept>
+#include "utility.h"
+
+void KeyFrame::updateLoop(const LoopInfo& info) {          // keyframe.cpp:571-578
+    if (std::fabs(info[7]) < 30.0 && std::sqrt(info[0] * info[0] + info[1] * info[1] + info[2] * info[2]) < 20.0) loop_info = info;
+}
+
+PoseGraph::PoseGraph(int device, int max_keyframes, int max_loops) {
+    sequence_loop.push_back(0);                             // :14
+    const int rc = uvs_pg_create(device, max_keyframes, max_loops, &pg_);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_pg_create: ") + uvs_status_string(rc));
+}
+
+PoseGraph::~PoseGraph() {
+    uvs_pg_destroy(pg_);
+    for (KeyFrame* kf : keyframelist) delete kf;
+}
+
+KeyFrame* PoseGraph::getKeyFrame(int index) {
+    for (KeyFrame* kf : keyframelist) if (kf->index == index) return kf;
+    return nullptr;
+}
+
+void PoseGraph::addKeyFrame(KeyFrame* cur_kf, int loop_index, const LoopInfo* loop_info) {
+    Eigen::Vector3d vio_P_cur;
+    Eigen::Matrix3d vio_R_cur;
+    if (sequence_cnt != cur_kf->sequence) {                 // :45-56 a new sequence starts in its own VIO frame
+        sequence_cnt++;
+        sequence_loop.push_back(0);
+        w_t_vio = Eigen::Vector3d(0, 0, 0); w_r_vio = Eigen::Matrix3d::Identity();
+        t_drift = Eigen::Vector3d(0, 0, 0); r_drift = Eigen::Matrix3d::Identity();
+    }
+    cur_kf->getVioPose(vio_P_cur, vio_R_cur);               // :58-62 shift to the base frame
+    vio_P_cur = w_r_vio * vio_P_cur + w_t_vio;
+    vio_R_cur = w_r_vio * vio_R_cur;
+    cur_kf->updateVioPose(vio_P_cur, vio_R_cur);
+    cur_kf->index = global_index++;
+    KeyFrame* old_kf = loop_index >= 0 ? getKeyFrame(loop_index) : nullptr;
+    if (old_kf && loop_info) {                               // :75-121, with findConnection's outcome given
+        cur_kf->has_loop = true; cur_kf->loop_index = loop_index; cur_kf->loop_info = *loop_info;
+        if (earliest_loop_index > loop_index || earliest_loop_index == -1) earliest_loop_index = loop_index;
+        Eigen::Vector3d w_P_old, w_P_cur;
+        Eigen::Matrix3d w_R_old, w_R_cur;
+        old_kf->getVioPose(w_P_old, w_R_old);
+        cur_kf->getVioPose(vio_P_cur, vio_R_cur);
+        const Eigen::Vector3d relative_t = cur_kf->getLoopRelativeT();
+        const Eigen::Matrix3d relative_q = cur_kf->getLoopRelativeQ().toRotationMatrix();
+        w_P_cur = w_R_old * relative_t + w_P_old;
+        w_R_cur = w_R_old * relative_q;
+        const double shift_yaw = Utility::R2ypr(w_R_cur).x() - Utility::R2ypr(vio_R_cur).x();
+        const Eigen::Matrix3d shift_r = Utility::ypr2R(Eigen::Vector3d(shift_yaw, 0, 0));
+        const Eigen::Vector3d shift_t = w_P_cur - w_R_cur * vio_R_cur.transpose() * vio_P_cur;
+        if (old_kf->sequence != cur_kf->sequence && sequence_loop[cur_kf->sequence] == 0) {     // shift the whole new sequence
+            w_r_vio = shift_r; w_t_vio = shift_t;
+            vio_P_cur = w_r_vio * vio_P_cur + w_t_vio;
+            vio_R_cur = w_r_vio * vio_R_cur;
+            cur_kf->updateVioPose(vio_P_cur, vio_R_cur);
+            for (KeyFrame* kf : keyframelist)
+                if (kf->sequence == cur_kf->sequence) {
+                    Eigen::Vector3d P; Eigen::Matrix3d R;
+                    kf->getVioPose(P, R);
+                    kf->updateVioPose(w_r_vio * P + w_t_vio, w_r_vio * R);
+                }
+            sequence_loop[cur_kf->sequence] = 1;
+        }
+    }
+    Eigen::Vector3d P; Eigen::Matrix3d R;                    // :124-129 the current drift correction
+    cur_kf->getVioPose(P, R);
+    cur_kf->updatePose(r_drift * P + t_drift, r_drift * R);
+    keyframelist.push_back(cur_kf);
+}
+
+void PoseGraph::updateKeyFrameLoop(int index, const LoopInfo& loop_info) {      // :888-892 (the FAST_RELOCALIZATION branch is not mirrored)
+    if (KeyFrame* kf = getKeyFrame(index)) kf->updateLoop(loop_info);
+}
+
+int PoseGraph::optimize4DoF(int cur_index) {
+    const int first_looped_index = earliest_loop_index;
+    KeyFrame* cur_kf = getKeyFrame(cur_index);
+    if (!cur_kf || first_looped_index < 0) { last_error = "optimize4DoF: no such keyframe or no loop yet"; return UVS_ERR_INVALID_ARG; }
+    std::vector<double> t, q, euler;
+    std::vector<int32_t> seq, constant;
+    std::vector<uvs_pg_loop> loops;
+    std::vector<KeyFrame*> kfs;
+    int i = 0;
+    for (KeyFrame* kf : keyframelist) {                      // :453-531
+        if (kf->index < first_looped_index) continue;
+        kf->local_index = i;
+        Eigen::Vector3d tmp_t; Eigen::Matrix3d tmp_r;
+        kf->getVioPose(tmp_t, tmp_r);
+        const Eigen::Quaterniond tmp_q(tmp_r);
+        t.insert(t.end(), {tmp_t.x(), tmp_t.y(), tmp_t.z()});
+        q.insert(q.end(), {tmp_q.x(), tmp_q.y(), tmp_q.z(), tmp_q.w()});
+        const Eigen::Vector3d e = Utility::R2ypr(tmp_q.toRotationMatrix());
+        euler.insert(euler.end(), {e.x(), e.y(), e.z()});
+        seq.push_back(kf->sequence);
+        constant.push_back(kf->index == first_looped_index || kf->sequence == 0);
+        if (kf->has_loop) {
+            KeyFrame* old_kf = getKeyFrame(kf->loop_index);
+            if (!old_kf || old_kf->index < first_looped_index) { last_error = "optimize4DoF: loop before first_looped_index"; return UVS_ERR_INVALID_ARG; }
+            uvs_pg_loop l;
+            l.cur = i; l.old = old_kf->local_index;
+            const Eigen::Vector3d rt = kf->getLoopRelativeT();
+            l.rel_t[0] = rt.x(); l.rel_t[1] = rt.y(); l.rel_t[2] = rt.z(); l.rel_yaw = kf->getLoopRelativeYaw();
+            loops.push_back(l);
+        }
+        kfs.push_back(kf);
+        if (kf->index == cur_index) break;
+        i++;
+    }
+    uvs_pg_problem p;
+    p.n = (int)kfs.size(); p.n_loops = (int)loops.size();
+    p.t = t.data(); p.q = q.data(); p.sequence = seq.data(); p.constant = constant.data(); p.loops = loops.data();
+    std::vector<double> yaw_t(4 * kfs.size());
+    const int rc = uvs_pg_optimize(pg_, &p, yaw_t.data(), &last_report);
+    if (rc != UVS_OK) { last_error = uvs_pg_last_error(pg_); return rc; }
+    for (size_t k = 0; k < kfs.size(); ++k)                   // :555-568 write back ypr2R(yaw, pitch, roll), t
+        kfs[k]->updatePose(Eigen::Vector3d(yaw_t[4 * k + 1], yaw_t[4 * k + 2], yaw_t[4 * k + 3]),
+                           Eigen::Quaterniond(Utility::ypr2R(Eigen::Vector3d(yaw_t[4 * k], euler[3 * k + 1], euler[3 * k + 2]))).toRotationMatrix());
+    Eigen::Vector3d cur_t, vio_t; Eigen::Matrix3d cur_r, vio_r;                // :570-577 drift
+    cur_kf->getPose(cur_t, cur_r);
+    cur_kf->getVioPose(vio_t, vio_r);
+    yaw_drift = Utility::R2ypr(cur_r).x() - Utility::R2ypr(vio_r).x();
+    r_drift = Utility::ypr2R(Eigen::Vector3d(yaw_drift, 0, 0));
+    t_drift = cur_t - r_drift * vio_t;
+    bool after = false;                                       // :582-591 every keyframe after cur
+    for (KeyFrame* kf : keyframelist) {
+        if (after) {
+            Eigen::Vector3d P; Eigen::Matrix3d R;
+            kf->getVioPose(P, R);
+            kf->updatePose(r_drift * P + t_drift, r_drift * R);
+        }
+        if (kf == cur_kf) after = true;
+    }
+    return UVS_OK;
+}
+
+bool PoseGraph::writeTum(const std::string& path) const {
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    for (const KeyFrame* kf : keyframelist) {
+        const Eigen::Quaterniond Q(kf->R_w_i);
+        std::fprintf(f, "%.9f %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n", kf->time_stamp, kf->T_w_i.x(), kf->T_w_i.y(), kf->T_w_i.z(), Q.x(), Q.y(), Q.z(), Q.w());
+    }
+    return std::fclose(f) == 0;
+}
