@@ -397,8 +397,8 @@ int uvs_reduced_dim(const uvs_options *opts);  /* 165 (+6 if estimate_extrinsic)
  * itself, exactly as the reference does: FourDOFError (i-j, i) for j = 1..4 when both have the same sequence, measured from the initial poses
  * (rel_t = R(q_{i-j})^T (t_i - t_{i-j}), rel_yaw = yaw_i - yaw_{i-j}, pitch / roll of i-j), no loss.  Loop edge l is
  * FourDOFWeightError (old, cur) with HuberLoss(0.1), yaw residual / 10, pitch / roll of the initial pose of `old`.  Solver: Ceres LM with
- * max_num_iterations = 5 and otherwise the defaults of uvs_default_options(), an exact solve of the damped normal
- * equations.  Edges whose two keyframes are both constant are not part of the problem (Ceres drops them from its reduced program): the costs
+ * max_num_iterations = 5 and otherwise the defaults of uvs_default_options(), a direct solve of the damped normal
+ * equations (banded Cholesky + Woodbury, one step of iterative refinement when loop edges have two free ends).  Edges whose two keyframes are both constant are not part of the problem (Ceres drops them from its reduced program): the costs
  * reported here are those of the other edges.  No CPU path: uvs_pg_create fails with UVS_ERR_NO_DEVICE without a GPU. */
 #define UVS_PG_MAX_KEYFRAMES 65536            /* largest max_keyframes uvs_pg_create takes */
 #define UVS_PG_MAX_LOOPS 256                  /* largest max_loops uvs_pg_create takes      */
@@ -446,6 +446,13 @@ const char *uvs_pg_last_error(const uvs_pose_graph *pg);
 /* out_yaw_t[n][4] = (yaw in degrees, tx, ty, tz) after the solve, every keyframe (constant ones unchanged).  UVS_ERR_INVALID_ARG: null pointer,
  * n < 1, or a loop outside 0 <= old < cur < n; UVS_ERR_CAPACITY: n or n_loops above the handle's capacity. */
 int uvs_pg_optimize(uvs_pose_graph *pg, const uvs_pg_problem *problem, double *out_yaw_t, uvs_pg_report *report);
+
+/* Diagnostic (tests only): ONE damped solve of the first LM iteration of uvs_pg_optimize, through the same kernels.  Linearizes at the
+ * initial poses, computes the Jacobi scaling as the first linearization does and solves the damped system at `radius`:
+ * delta[4 * n_free] = the unscaled step in free-keyframe order (yaw deg, t), scal[UVS_PG_DEBUG_SCAL_LEN] = {banded Cholesky fail flag,
+ * capacitance Cholesky fail flag, n_loop_columns, n_free}.  UVS_ERR_INVALID_ARG also for a radius that is not finite or <= 0. */
+#define UVS_PG_DEBUG_SCAL_LEN 4
+int uvs_pg_debug_step(uvs_pose_graph *pg, const uvs_pg_problem *problem, double radius, double *delta, double *scal);
 
 #ifdef __cplusplus
 }

@@ -122,3 +122,107 @@ def chain_case(n, seed, yaw0=0.0, n_loops=2):
 
 def positions_ate(P_est, P_true):
     return uvs.sequence.ate(P_est, P_true)
+
+
+# ---------------------------------------------------------------- structures the solve kernels branch on
+def _loop(p, R, k, j, rng, t_noise=0.01, yaw_noise=0.2):
+    """Loop edge (cur = k, old = j) measuring the true relative pose with small noise."""
+    ypr = pg_ref.R2ypr(R[[k, j]])
+    rel_t = R[j].T @ (p[k] - p[j]) + rng.normal(0.0, t_noise, 3)
+    return (int(k), int(j), rel_t, float(pg_ref.normalize_angle(ypr[0, 0] - ypr[1, 0] + rng.normal(0.0, yaw_noise))))
+
+
+def _circuit(n, seed, per_lap=40):
+    """True poses on laps of a circle (one keyframe per 360 / per_lap deg, pitch / roll of a few degrees) and their drifted estimate."""
+    rng = np.random.default_rng(seed)
+    ang = 2 * np.pi * np.arange(n) / per_lap
+    rad = 3.0 + 0.2 * (np.arange(n) // per_lap)
+    p = np.stack([rad * np.cos(ang), rad * np.sin(ang), 0.1 * np.sin(3 * ang)], 1)
+    R = pg_ref.ypr2R(np.degrees(ang) + 90.0, rng.normal(0, 2, n), rng.normal(0, 2, n))
+    pv, Rv = drift(p, R, seed, yaw_sigma=0.3, t_sigma=0.01)
+    return p, R, pv, Rv
+
+
+def interleaved_constants_case():
+    """MH_05 at 2 keyframes/s (mh05_case(2.0)) with constant keyframes INSIDE the free run: two single ones and runs of 2, 3, 4 and 5.  Across
+    a run of c < 4 constants the sequential edges reach over it, so free neighbours a - d and a are j = d + c keyframes apart (j != d)."""
+    w = mh05_case(2.0)
+    for lo, cnt in ((20, 1), (50, 1), (80, 2), (110, 3), (140, 4), (170, 5)):
+        w["constant"][lo:lo + cnt] = 1
+    return w
+
+
+def three_sequence_case(seed=5):
+    """The first 120 MH_05 keyframes at 2 keyframes/s.  No sequence 0: keyframe 0 is the only constant one; sequence 1 = keyframes 0..59,
+    sequence 2 = 60..119 (a VIO restart: its own drift, in a frame turned by 25 deg and moved by (1, -2, 0.3) m).  Ten loop edges from
+    sequence 2 back to sequence 1, all with two free ends: sequence 2 is anchored only through the low-rank part U, so the band part A has a
+    4-DoF gauge null space that only the damping closes."""
+    _, p, R = mh05_keyframes(2.0)
+    p, R = p[:120], R[:120]
+    h = 60
+    p1, R1 = drift(p[:h], R[:h], seed)
+    p2, R2 = drift(p[h:], R[h:], seed + 1)
+    S = Rz(25.0); off = np.array([1.0, -2.0, 0.3])
+    P = np.concatenate([p1, (S @ p2.T).T + off]); RR = np.concatenate([R1, S @ R2])
+    rng = np.random.default_rng(seed + 100)
+    loops = []
+    for k in range(h + 2, 120, 6):                     # k -> k - 57: old ends spread over keyframes 5..59 of sequence 1
+        loops.append(_loop(p, R, k, k - 57, rng))
+    const = np.zeros(120, np.int32); const[0] = 1
+    return dict(t=P, q=pg_ref.R_to_quat(RR), sequence=np.r_[np.ones(h, np.int32), 2 * np.ones(120 - h, np.int32)], constant=const,
+                loops=loops)
+
+
+def band_overlap_case(seed=12):
+    """60 keyframes of one sequence, keyframe 0 constant.  Loop edges whose ends are 1..4 keyframes apart (inside the sequential band),
+    several loops sharing one old keyframe, a loop listed twice, and two loops to the constant keyframe."""
+    n = 60
+    p, R, pv, Rv = _circuit(n, seed)
+    rng = np.random.default_rng(seed + 100)
+    pairs = [(10, 9), (15, 13), (22, 19), (31, 27), (40, 36)]                # cur - old = 1, 2, 3, 4, 4
+    pairs += [(20, 5), (33, 5), (47, 5), (58, 5), (45, 42)]                 # old keyframe 5 shared four times
+    pairs += [(50, 12), (41, 0), (59, 0)]
+    loops = [_loop(p, R, k, j, rng) for k, j in pairs]
+    loops.append(loops[-4])                                                    # (50, 12) again, the same measurement
+    const = np.zeros(n, np.int32); const[0] = 1
+    return dict(t=pv, q=pg_ref.R_to_quat(Rv), sequence=np.ones(n, np.int32), constant=const, loops=loops)
+
+
+def sized_case(nf, nu, seed=0):
+    """Exactly nf free keyframes (n = nf + 1, keyframe 0 constant, one sequence) and nu loop edges with two free ends between random
+    keyframes 1..nf (nu > 0 needs nf >= 2; pairs may repeat).  Without U columns, one loop edge to keyframe 0 instead."""
+    assert nf >= 1 and nu >= 0 and (nu == 0 or nf >= 2)
+    n = nf + 1
+    p, R, pv, Rv = _circuit(n, seed + 1000 * nf + nu, per_lap=max(8, min(40, n)))
+    rng = np.random.default_rng(seed + 7 * nf + 13 * nu)
+    loops = []
+    for _ in range(nu):
+        k = int(rng.integers(2, n)); j = int(rng.integers(1, k))
+        loops.append(_loop(p, R, k, j, rng))
+    if nu == 0:
+        loops.append(_loop(p, R, n - 1, 0, rng))
+    const = np.zeros(n, np.int32); const[0] = 1
+    return dict(t=pv, q=pg_ref.R_to_quat(Rv), sequence=np.ones(n, np.int32), constant=const, loops=loops)
+
+
+def all_constant_case():
+    """Every keyframe constant: no variable, no edge in the problem (Ceres converges without an iteration)."""
+    w = chain_case(12, 13)
+    w["constant"][:] = 1
+    return w
+
+
+def structure(w):
+    """What the solve kernels see of a case: free numbering, U columns, and the band pairs (free a - d, free a, d = 1..4) that carry a
+    sequential edge, with the keyframe distance j of each."""
+    const = np.asarray(w["constant"]).astype(bool); seq = np.asarray(w["sequence"])
+    free = np.flatnonzero(~const)
+    two_free = [(k, j) for k, j, _, _ in w["loops"] if not const[k] and not const[j]]
+    pairs = []
+    for a in range(len(free)):
+        for d in range(1, 5):
+            if a - d >= 0:
+                j = free[a] - free[a - d]
+                if 1 <= j <= 4 and seq[free[a]] == seq[free[a - d]]:
+                    pairs.append((a, d, int(j)))
+    return dict(nf=len(free), nu=len(two_free), n_loop_columns=4 * len(two_free), two_free=two_free, band_pairs=pairs)

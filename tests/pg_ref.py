@@ -243,3 +243,52 @@ def optimize(t, q, sequence, constant, loops, max_num_iterations=MAX_ITER):
         tr.radius.append(radius); tr.cost.append(cost)
     tr.num_iterations = it; tr.final_cost = cost
     return x, tr
+
+
+# ---------------------------------------------------------------- one damped solve in extended precision
+def damped_system(pb, radius):
+    """The scaled damped system of the FIRST LM iteration at radius, formed exactly as `optimize` forms it:
+    -> (M = S H S + diag(clip(diag(S H S), 1e-6, 1e32)) / radius, b = -S g, s = diag(S)), FP64."""
+    r, J, _ = residuals(pb, pb.x0)
+    H, g, _ = normal_equations(pb, r, J)
+    s = 1.0 / (1.0 + np.sqrt(np.diag(H)))
+    Hs = H * np.outer(s, s)
+    diag = np.clip(np.diag(Hs), 1e-6, 1e32)
+    return Hs + np.diag(diag / radius), -(g * s), s
+
+
+def cholesky_ld(M, nb=32):
+    """Lower Cholesky factor of the symmetric positive definite M in np.longdouble (blocked right-looking, numpy only)."""
+    A = np.array(M, dtype=np.longdouble)
+    m = len(A)
+    for k0 in range(0, m, nb):
+        k1 = min(m, k0 + nb)
+        for k in range(k0, k1):
+            if not A[k, k] > 0:
+                raise np.linalg.LinAlgError(f"cholesky_ld: pivot {k} is {A[k, k]}")
+            A[k:, k] /= np.sqrt(A[k, k])
+            c = A[k + 1:, k]
+            A[k + 1:, k + 1:k1] -= c[:, None] * c[None, :k1 - k - 1]
+        P = A[k1:, k0:k1]
+        A[k1:, k1:] -= P @ P.T
+    return np.tril(A)
+
+
+def solve_ld(M, b):
+    """M y = b through cholesky_ld and two triangular sweeps, all in np.longdouble.  -> y (np.longdouble)."""
+    assert np.finfo(np.longdouble).eps < 1e-18, "np.longdouble is not an extended type here: the reference would be plain FP64"
+    L = cholesky_ld(M)
+    m = len(L)
+    y = np.array(b, dtype=np.longdouble)
+    for k in range(m):
+        y[k] = (y[k] - L[k, :k] @ y[:k]) / L[k, k]
+    for k in range(m - 1, -1, -1):
+        y[k] = (y[k] - L[k + 1:, k] @ y[k + 1:]) / L[k, k]
+    return y
+
+
+def damped_step(pb, radius):
+    """The unscaled step delta = S y of the first LM iteration at `radius` (free-keyframe order, [4 nf]), y solved in np.longdouble:
+    the reference of uvs_pg_debug_step.  -> delta (np.longdouble)."""
+    M, b, s = damped_system(pb, radius)
+    return s.astype(np.longdouble) * solve_ld(M, b)

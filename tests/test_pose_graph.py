@@ -108,8 +108,64 @@ def test_pg_ref_constant_blocks_stay_fixed():
     assert tr.num_iterations >= 1 and tr.final_cost < tr.initial_cost
 
 
+def test_pg_ref_damped_step_extended_precision():
+    """damped_step solves in np.longdouble: it agrees with an FP64 dense solve on a well-conditioned system, and its residual is at the
+    extended type's level, far below what FP64 can reach."""
+    assert np.finfo(np.longdouble).eps < 1e-18
+    w = pc.sized_case(33, 1)
+    pb = pg_ref.Problem(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+    M, b, s = pg_ref.damped_system(pb, 1e4)
+    assert np.linalg.cond(M) < 1e6
+    d = pg_ref.damped_step(pb, 1e4)
+    assert d.dtype == np.longdouble and d.shape == (4 * 33,)
+    d64 = s * np.linalg.solve(M, b)
+    assert np.linalg.norm(d64 - d.astype(np.float64)) <= 1e-13 * np.linalg.norm(d.astype(np.float64))
+    y = pg_ref.solve_ld(M, b)
+    res = np.asarray(b, np.longdouble) - np.asarray(M, np.longdouble) @ y
+    assert float(np.linalg.norm(res) / np.linalg.norm(b)) <= 1e-17
+
+
+def test_pg_case_structures():
+    """Each generator builds the structure its name promises, so the GPU tests below keep testing what they claim to."""
+    # constants inside the free run: band pairs whose keyframe distance j differs from the free-index distance d
+    w = pc.interleaved_constants_case(); st = pc.structure(w)
+    const = w["constant"].astype(bool)
+    assert const[0] and const[1:].sum() == 2 + 2 + 3 + 4 + 5
+    assert sum(1 for _, d, j in st["band_pairs"] if j != d) >= 10
+    assert {j - d for _, d, j in st["band_pairs"]} >= {0, 1, 2, 3}
+    assert st["nu"] > 0
+    # three sequences: sequence 2 free, no constant keyframe and no loop with one free end; anchored through U columns only
+    w = pc.three_sequence_case(); st = pc.structure(w)
+    seq, const = w["sequence"], w["constant"].astype(bool)
+    assert set(seq.tolist()) == {1, 2} and np.flatnonzero(const).tolist() == [0]
+    s2 = seq == 2
+    assert not const[s2].any()
+    touching = [(k, j) for k, j, _, _ in w["loops"] if s2[k] or s2[j]]
+    assert len(touching) == 10 and all(s2[k] and seq[j] == 1 for k, j in touching)
+    assert st["nu"] == 10 and st["n_loop_columns"] == 40
+    assert all(seq[free_a] == seq[free_b] for free_a, free_b in [(np.flatnonzero(~const)[a], np.flatnonzero(~const)[a - d]) for a, d, _ in st["band_pairs"]])
+    # band overlap: loop ends 1..4 keyframes apart, a shared old keyframe, a duplicated loop
+    w = pc.band_overlap_case(); st = pc.structure(w)
+    gaps = {k - j for k, j in st["two_free"]}
+    assert {1, 2, 3, 4} <= gaps
+    olds = [j for _, j in st["two_free"]]
+    assert max(olds.count(j) for j in set(olds)) >= 4
+    assert len(set(st["two_free"])) < len(st["two_free"])
+    assert any(w["constant"][j] for _, j, _, _ in w["loops"])
+    # sized cases: exactly nf free keyframes and nu loops with two free ends
+    for nf, nu in SIZED_STEP + [(222, 256)]:
+        st = pc.structure(pc.sized_case(nf, nu))
+        assert st["nf"] == nf and st["nu"] == nu and st["n_loop_columns"] == 4 * nu
+    ncols = lambda nu: ((4 * nu + 1 + 63) // 64) * 64
+    assert ncols(16) == 128 and (4 * 16) % 64 == 0           # the -g column alone in its tile
+    assert ncols(256) == 1088                                 # k_pg_capsolve's LDS capacity
+    # all constant
+    st = pc.structure(pc.all_constant_case())
+    assert st["nf"] == 0 and st["nu"] == 0
+
+
 # ---------------------------------------------------------------- C ABI surface (CPU)
-PG_SYMBOLS = ["uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize"]
+PG_SYMBOLS = ["uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step"]
 
 
 def test_pose_graph_symbols_exported():
@@ -159,6 +215,12 @@ def _check_parity(w, pg=None):
     assert rep.termination == tr.termination
     assert abs(rep.initial_cost - tr.initial_cost) <= 1e-9 * max(tr.initial_cost, 1e-300) + 1e-18
     assert abs(rep.final_cost - tr.final_cost) <= 1e-9 * max(tr.final_cost, 1e-300) + 1e-18, (rep.final_cost, tr.final_cost)
+    # every iteration's cost, candidate cost, model cost change and radius (entry 0 = the initial evaluation)
+    trace = rep.trace()
+    for key in ("cost", "candidate_cost", "model_cost_change", "radius"):
+        ref = np.asarray(getattr(tr, key), dtype=np.float64)
+        assert len(ref) == tr.num_iterations + 1, key
+        assert np.all(np.abs(trace[key] - ref) <= 1e-9 * np.abs(ref) + 1e-18), (key, trace[key], ref)
     assert np.abs(out[:, 1:] - x[:, 1:]).max() < 1e-7
     assert np.abs(pg_ref.normalize_angle(out[:, 0] - x[:, 0])).max() < 1e-6
     return out, rep
@@ -241,3 +303,132 @@ def test_gpu_pose_graph_argument_checks():
     assert rc == abi.UVS_ERR_CAPACITY
     rc, _, _ = pg.optimize_raw(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])                    # the handle still works
     assert rc == abi.UVS_OK
+
+
+# ---------------------------------------------------------------- one damped solve against the extended-precision reference (GPU)
+STEP_RADII = [1e-2, 1.0, 1e4, 8.1e5]            # 8.1e5 = 1e4 * 3^4: the largest radius the LM controller reaches in five iterations
+# (nf, nu): the 32-row chunk edges of k_pg_factor / k_pg_back, the 64-column U tiles (16 loops: the -g column alone in its tile), capacity
+SIZED_STEP = [(1, 0), (2, 1), (3, 0), (4, 15), (5, 16), (31, 17), (32, 0), (33, 1), (36, 16), (37, 64), (64, 17), (65, 15), (65, 256),
+              (222, 0), (222, 256)]
+
+
+def _step_cases():
+    cases = {"interleaved_constants": pc.interleaved_constants_case, "three_sequence": pc.three_sequence_case,
+             "band_overlap": pc.band_overlap_case, "mh05_2hz": lambda: pc.mh05_case(2.0), "outliers": lambda: pc.mh05_case(2.0, outliers=6),
+             "two_sequences": pc.two_sequence_case}
+    cases.update({f"sized_{nf}_{nu}": (lambda nf=nf, nu=nu: pc.sized_case(nf, nu)) for nf, nu in SIZED_STEP})
+    return cases
+
+
+STEP_CASES = _step_cases()
+
+
+@pytest.fixture(scope="module")
+def pg_big():
+    pg = uvs.api.PoseGraphSolver(max_keyframes=2048, max_loops=256)
+    yield pg
+    pg.close()
+
+
+def _dense_fp64_error(M, b, s, ref):
+    """Relative error of FP64 dense solves (np.linalg.solve) of the same system, the largest over three elimination orders of the unknowns
+    (natural, reversed, one fixed shuffle): one order alone can land far below the usual level by luck of rounding."""
+    m = len(b)
+    worst = 0.0
+    for perm in (np.arange(m), np.arange(m)[::-1], np.random.default_rng(0).permutation(m)):
+        y = np.empty(m)
+        y[perm] = np.linalg.solve(M[np.ix_(perm, perm)], b[perm])
+        worst = max(worst, np.linalg.norm(s * y - ref) / np.linalg.norm(ref))
+    return worst
+
+
+def _check_step(pg, w, radii):
+    """uvs_pg_debug_step against pg_ref.damped_step: relative error <= max(10 x the error of an FP64 dense solve of the same system, 1e-12).
+    The floor is that of the linearization, not of the solve: the device and numpy round the residuals of the sequential edges at the initial
+    poses (exact cancellations, ~1e-16 m) differently, so the two systems differ in g at that level; at small radii the step is about
+    radius D^-1 g, and the two steps differ by up to ~2e-13 relative (MI355X, no loop column at all) however exact the solves."""
+    pb = pg_ref.Problem(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+    st = pc.structure(w)
+    rows = []
+    for radius in radii:
+        delta, info = pg.debug_step(w["t"], w["q"], w["sequence"], w["constant"], w["loops"], radius)
+        assert info["factor_fail"] == 0 and info["capacitance_fail"] == 0, (radius, info)
+        assert info["n_free"] == st["nf"] and info["n_loop_columns"] == st["n_loop_columns"]
+        M, b, s = pg_ref.damped_system(pb, radius)
+        ref = (s.astype(np.longdouble) * pg_ref.solve_ld(M, b)).astype(np.float64)
+        err = np.linalg.norm(delta - ref) / np.linalg.norm(ref)
+        err64 = _dense_fp64_error(M, b, s, ref)
+        rows.append((radius, err, err64))
+        assert err <= max(10.0 * err64, 1e-12), (radius, err, err64)
+    return rows
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(STEP_CASES))
+def test_gpu_pose_graph_step_matches_extended_reference(pg_big, name):
+    _check_step(pg_big, STEP_CASES[name](), STEP_RADII)
+
+
+@pytest.mark.gpu
+def test_gpu_pose_graph_step_three_sequences_large_radius(pg_big):
+    """Sequence 2 hangs on U alone: cond(A) grows with the radius while cond(A + U U^T + D / radius) does not.  The plain Woodbury solve
+    loses accuracy in proportion to cond(A); the refinement step must hold the dense-solve level."""
+    _check_step(pg_big, pc.three_sequence_case(), [1e8, 1e10, 1e12])
+
+
+@pytest.mark.gpu
+def test_gpu_pose_graph_step_argument_checks(pg_big):
+    w = pc.sized_case(5, 1)
+    for radius in (0.0, -1.0, float("inf"), float("nan")):
+        rc, _, _ = pg_big.debug_step_raw(w["t"], w["q"], w["sequence"], w["constant"], w["loops"], radius)
+        assert rc == abi.UVS_ERR_INVALID_ARG, radius
+    rc, _, _ = pg_big.debug_step_raw(w["t"], w["q"], w["sequence"], w["constant"], [(3, 5, [0, 0, 0], 0.0)], 1e4)
+    assert rc == abi.UVS_ERR_INVALID_ARG
+    rc, delta, scal = pg_big.debug_step_raw(w["t"], w["q"], w["sequence"], w["constant"], w["loops"], 1e4)
+    assert rc == abi.UVS_OK and len(delta) == 20 and scal[3] == 5 and scal[2] == 4
+    a = pc.all_constant_case()
+    delta, info = pg_big.debug_step(a["t"], a["q"], a["sequence"], a["constant"], a["loops"], 1e4)
+    assert len(delta) == 0 and info["n_free"] == 0
+
+
+# ---------------------------------------------------------------- full parity of the new structures (GPU)
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["interleaved_constants", "three_sequence", "band_overlap", "sized_1_0", "sized_33_1", "sized_36_16",
+                                  "sized_64_17", "sized_222_256"])
+def test_gpu_pose_graph_parity_structures(pg_big, name):
+    w = STEP_CASES[name]()
+    _, rep = _check_parity(w, pg_big)
+    assert rep.n_loop_columns == pc.structure(w)["n_loop_columns"]
+
+
+@pytest.mark.gpu
+def test_gpu_pose_graph_all_constant():
+    w = pc.all_constant_case()
+    pg = uvs.api.PoseGraphSolver(max_keyframes=16, max_loops=4)
+    out, rep = pg.optimize(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+    x, tr = pg_ref.optimize(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+    pb = pg_ref.Problem(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+    assert rep.status == abi.UVS_OK and rep.n_free == 0 and rep.n_edges == 0 and rep.n_loop_columns == 0
+    assert rep.num_iterations == 0 and rep.termination == pg_ref.TERM["FUNCTION_TOL"] == tr.termination
+    assert np.array_equal(out[:, 1:], w["t"])
+    assert np.abs(out[:, 0] - pb.x0[:, 0]).max() < 1e-12
+    assert rep.initial_cost == tr.initial_cost == 0.0 and rep.final_cost == tr.final_cost == 0.0
+
+
+@pytest.mark.gpu
+def test_gpu_pose_graph_handle_reuse_is_bitwise_fresh():
+    """One handle through problems of different n and ncols (rows of W before a wave's start are never written and stay from the call
+    before): every output and report equals that of a fresh handle, bit for bit."""
+    seqs = [pc.mh05_case(10.0), pc.chain_case(12, 8), pc.sized_case(40, 0), pc.sized_case(36, 16), pc.mh05_case(10.0)]
+    pg = uvs.api.PoseGraphSolver(max_keyframes=2048, max_loops=256)
+    for w in seqs:
+        a, ra = pg.optimize(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+        fresh = uvs.api.PoseGraphSolver(max_keyframes=2048, max_loops=256)
+        b, rb = fresh.optimize(w["t"], w["q"], w["sequence"], w["constant"], w["loops"])
+        fresh.close()
+        assert a.tobytes() == b.tobytes()
+        assert bytes(ra) == bytes(rb)
+    # a handle without loop capacity on a problem without loops
+    w = pc.chain_case(20, 10); w["loops"] = []
+    pg0 = uvs.api.PoseGraphSolver(max_keyframes=32, max_loops=0)
+    _check_parity(w, pg0)

@@ -376,6 +376,7 @@ class Eval:
 # ---- 4-DoF pose graph of loop closure (uvs_pg_*, include/uvs_solver.h) ------------------------------------------------
 PG_MAX_KEYFRAMES = 65536
 PG_MAX_LOOPS = 256
+PG_DEBUG_SCAL_LEN = 4
 
 
 class PgLoop(C.Structure):

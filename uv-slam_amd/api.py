@@ -19,7 +19,7 @@ _lib = None
 EXPORTS = [
     "uvs_abi_version", "uvs_default_options", "uvs_create", "uvs_destroy", "uvs_last_error", "uvs_status_string",
     "uvs_solve_window", "uvs_batch_upload", "uvs_batch_solve", "uvs_batch_download", "uvs_batch_stream", "uvs_evaluate", "uvs_marginalize", "uvs_marginalize_resident", "uvs_marginalize_batch",
-    "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize",
+    "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step",
 ]
 
 
@@ -76,6 +76,8 @@ def lib():
         L.uvs_pg_destroy.argtypes = [C.c_void_p]; L.uvs_pg_destroy.restype = None
         L.uvs_pg_last_error.argtypes = [C.c_void_p]; L.uvs_pg_last_error.restype = C.c_char_p
         L.uvs_pg_optimize.argtypes = [C.c_void_p, C.POINTER(abi.PgProblem), abi.c_double_p, C.POINTER(abi.PgReport)]; L.uvs_pg_optimize.restype = C.c_int
+        L.uvs_pg_debug_step.argtypes = [C.c_void_p, C.POINTER(abi.PgProblem), C.c_double, abi.c_double_p, abi.c_double_p]
+        L.uvs_pg_debug_step.restype = C.c_int
         _lib = L
     return _lib
 
@@ -354,3 +356,18 @@ class PoseGraphSolver:
         if rc not in (abi.UVS_OK, abi.UVS_ERR_NUMERIC):
             raise RuntimeError(f"uvs_pg_optimize: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
         return out, rep
+
+    def debug_step_raw(self, t, q, sequence, constant, loops, radius):
+        """-> (return code, delta [4 n_free], scal [UVS_PG_DEBUG_SCAL_LEN]) without raising."""
+        p, keep = abi.pg_problem(t, q, sequence, constant, loops)
+        delta = np.zeros(max(4 * int(np.count_nonzero(keep["constant"] == 0)), 1)); scal = np.zeros(abi.PG_DEBUG_SCAL_LEN)
+        rc = lib().uvs_pg_debug_step(self._h, C.byref(p), float(radius), abi._dp(delta), abi._dp(scal))
+        return rc, delta[:4 * int(scal[3])], scal
+
+    def debug_step(self, t, q, sequence, constant, loops, radius):
+        """Diagnostic: one damped solve of the first LM iteration at `radius` through the product's kernels (uvs_pg_debug_step).
+        -> (delta [4 n_free] = the unscaled step in free-keyframe order, dict(factor_fail, capacitance_fail, n_loop_columns, n_free))."""
+        rc, delta, scal = self.debug_step_raw(t, q, sequence, constant, loops, radius)
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_pg_debug_step: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
+        return delta, dict(factor_fail=int(scal[0]), capacitance_fail=int(scal[1]), n_loop_columns=int(scal[2]), n_free=int(scal[3]))

@@ -17,6 +17,11 @@
 //   k_pg_capsolve  1 workgroup     v = Lc^-T l = C^-1 U^T A^-1 (-g)
 //   k_pg_wv        wave per row    u = z - W v      (Woodbury: (A + U U^T)^-1 = L^-T (I - W C^-1 W^T) L^-1)
 //   k_pg_back      1 wave          y = L^-T u
+//   (nu > 0: one step of iterative refinement with the same factors)
+//   k_pg_resid     per free kf     r = b - (A + U U^T) y in FP64, fixed order
+//   k_pg_forward   1 wave          w = L^-1 r into the z column of W
+//   k_pg_wtz + k_pg_capsolve       v = C^-1 W_U^T w
+//   k_pg_wv + k_pg_back            y += L^-T (w - W_U v)
 //   k_pg_step      per free kf     delta = s y, candidate plus with the yaw wrap, |step|^2, |x|^2
 //   k_pg_lin<1>    per edge        candidate cost and the model cost change -(J delta).(r + J delta / 2)
 //   k_pg_reduce    1 workgroup     fixed-order sums / maxima of the per-edge and per-keyframe partials
@@ -40,6 +45,14 @@ constexpr int kRow = kBand * 16;    // doubles per band row
 constexpr int kTile = 64;           // Gram / capacitance block size
 constexpr double kHuberA = 0.1;     // HuberLoss(0.1), pose_graph.cpp:437
 constexpr double kD2R = M_PI / 180.0;
+constexpr double kMinDiag = 1e-6, kMaxDiag = 1e32;   // Ceres' min / max_lm_diagonal
+
+// One step of iterative refinement after the Woodbury solve when the problem has loop edges with two free ends (nu > 0): A alone can be
+// near singular (a sequence anchored only through U has a gauge null space that only the damping closes), and the Woodbury formula then
+// loses accuracy in proportion to cond(A).  0 leaves the plain Woodbury solve (A/B builds only).
+#ifndef UVS_PG_REFINE
+#define UVS_PG_REFINE 1
+#endif
 
 __device__ __host__ inline double normalize_angle(double a) {     // pose_graph.h NormalizeAngle: ONE wrap
     return a > 180.0 ? a - 360.0 : (a < -180.0 ? a + 360.0 : a);
@@ -363,14 +376,17 @@ __global__ void __launch_bounds__(kWave) k_pg_factor(int nf, const double* __res
 }
 
 // Forward substitution W = L^-1 B for many right-hand sides, one column per lane.  Column q < 4 nu: scaled U column (loop edge ucol[q / 4], row q % 4
-// of its corrected Jacobian); column zc = 4 nu: -g (scaled); the rest: zero padding.  A wave starts at the smallest first-nonzero row of its
-// columns (the U columns are sorted by their older end), wstart[wave] records it; rows of a column before its wave's start are never written.
-__global__ void __launch_bounds__(kWave) k_pg_forward(int nf, int ncols, int nu, const double* __restrict__ L, const int* __restrict__ ucol,
-                                                      const Edge* __restrict__ E, const double* __restrict__ eJ, const double* __restrict__ s,
-                                                      const double* __restrict__ g, const int* __restrict__ wstart, double* __restrict__ W) {
+// of its corrected Jacobian); column zc = 4 nu: zsign * z (z = g, zsign = -1 for the step; the residual, +1, in the refinement pass); the rest:
+// zero padding.  A wave starts at the smallest first-nonzero row of its columns (the U columns are sorted by their older end), wstart[wave]
+// records it; rows of a column before its wave's start are never written.  Block b runs wave wave0 + b; zonly: only column zc is written.
+__global__ void __launch_bounds__(kWave) k_pg_forward(int nf, int ncols, int nu, int wave0, int zonly, const double* __restrict__ L,
+                                                      const int* __restrict__ ucol, const Edge* __restrict__ E, const double* __restrict__ eJ,
+                                                      const double* __restrict__ s, const double* __restrict__ z, double zsign,
+                                                      const int* __restrict__ wstart, double* __restrict__ W) {
     __shared__ double rows[kChunk * kRow], gch[kChunk * 4];
-    const int lane = threadIdx.x, q = blockIdx.x * kWave + lane;
+    const int lane = threadIdx.x, wave = wave0 + blockIdx.x, q = wave * kWave + lane;
     const int zc = 4 * nu;
+    const bool write = q < ncols && (!zonly || q == zc);
     int fa = -1, fb = -1;
     double ja[4] = {}, jb[4] = {};
     if (q < zc) {
@@ -379,12 +395,12 @@ __global__ void __launch_bounds__(kWave) k_pg_forward(int nf, int ncols, int nu,
         for (int c = 0; c < 4; ++c) { ja[c] = eJ[32 * e + 8 * rr + c] * s[4 * fa + c]; jb[c] = eJ[32 * e + 8 * rr + 4 + c] * s[4 * fb + c]; }
     }
     double w1[4] = {}, w2[4] = {}, w3[4] = {}, w4[4] = {};
-    const int a_begin = wstart[blockIdx.x];
+    const int a_begin = wstart[wave];
     for (int a0 = a_begin; a0 < nf; a0 += kChunk) {
         const int cnt = min(kChunk, nf - a0);
         __syncthreads();
         for (int k = lane; k < cnt * kRow; k += kWave) rows[k] = L[(size_t)a0 * kRow + k];
-        for (int k = lane; k < cnt * 4; k += kWave) gch[k] = -g[4 * a0 + k];        // off the dependency chain: no global load per row
+        for (int k = lane; k < cnt * 4; k += kWave) gch[k] = zsign * z[4 * a0 + k];  // off the dependency chain: no global load per row
         __syncthreads();
         for (int rr = 0; rr < cnt; ++rr) {
             const int a = a0 + rr;
@@ -402,7 +418,7 @@ __global__ void __launch_bounds__(kWave) k_pg_forward(int nf, int ncols, int nu,
                 b[k] = v / R[5 * k];
             }
             for (int k = 0; k < 4; ++k) { w4[k] = w3[k]; w3[k] = w2[k]; w2[k] = w1[k]; w1[k] = b[k]; }
-            if (q < ncols) for (int k = 0; k < 4; ++k) W[(size_t)(4 * a + k) * ncols + q] = b[k];
+            if (write) for (int k = 0; k < 4; ++k) W[(size_t)(4 * a + k) * ncols + q] = b[k];
         }
     }
 }
@@ -511,12 +527,21 @@ __global__ void __launch_bounds__(256) k_pg_syrk(int ncols, int k, int nb, doubl
         for (int j = 0; j < 4; ++j) G[(size_t)(Ib * kTile + 4 * tr + i) * ncols + Jb * kTile + 4 * tc + j] -= acc[i][j];
 }
 
-// v = Lc^-T l, l = row zc of the factor (columns 0 .. zc-1); v padded with zeros to ncols.
-__global__ void __launch_bounds__(1024) k_pg_capsolve(int ncols, int zc, const double* __restrict__ G, double* __restrict__ v) {
+// v = Lc^-T l, l = row zc of the factor (columns 0 .. zc-1); v padded with zeros to ncols.  rhs != nullptr (refinement pass): l = Lc^-1 rhs.
+__global__ void __launch_bounds__(1024) k_pg_capsolve(int ncols, int zc, const double* __restrict__ G, const double* __restrict__ rhs,
+                                                      double* __restrict__ v) {
     __shared__ double l[1088];
     const int tid = threadIdx.x;
-    for (int k = tid; k < ncols; k += 1024) l[k] = k < zc ? G[(size_t)zc * ncols + k] : 0.0;
+    for (int k = tid; k < ncols; k += 1024) l[k] = k < zc ? (rhs ? rhs[k] : G[(size_t)zc * ncols + k]) : 0.0;
     __syncthreads();
+    if (rhs)
+        for (int k = 0; k < zc; ++k) {
+            if (tid == 0) l[k] /= G[(size_t)k * ncols + k];
+            __syncthreads();
+            const double lk = l[k];
+            for (int j = k + 1 + tid; j < zc; j += 1024) l[j] -= G[(size_t)j * ncols + k] * lk;
+            __syncthreads();
+        }
     for (int k = zc - 1; k >= 0; --k) {
         if (tid == 0) l[k] /= G[(size_t)k * ncols + k];
         __syncthreads();
@@ -542,8 +567,9 @@ __global__ void __launch_bounds__(256) k_pg_wv(int m, int ncols, int zc, int nwa
     if (lane == 0) u[r] = W[(size_t)r * ncols + zc] - acc;
 }
 
-// y = L^-T u, one wave: band rows staged in LDS from the bottom up, lane 0 runs the chain.
-__global__ void __launch_bounds__(kWave) k_pg_back(int nf, const double* __restrict__ L, const double* __restrict__ u, double* __restrict__ y) {
+// y = L^-T u (accumulate: y += L^-T u), one wave: band rows staged in LDS from the bottom up, lane 0 runs the chain.
+__global__ void __launch_bounds__(kWave) k_pg_back(int nf, int accumulate, const double* __restrict__ L, const double* __restrict__ u,
+                                                   double* __restrict__ y) {
     __shared__ double rows[(kChunk + 4) * kRow], uch[kChunk * 4];
     const int lane = threadIdx.x;
     double y1[4] = {}, y2[4] = {}, y3[4] = {}, y4[4] = {};
@@ -571,10 +597,54 @@ __global__ void __launch_bounds__(kWave) k_pg_back(int nf, const double* __restr
                     for (int m = k + 1; m < 4; ++m) v -= D[4 * m + k] * b[m];
                     b[k] = v / D[5 * k];
                 }
-                for (int k = 0; k < 4; ++k) { y4[k] = y3[k]; y3[k] = y2[k]; y2[k] = y1[k]; y1[k] = b[k]; y[4 * a + k] = b[k]; }
+                for (int k = 0; k < 4; ++k) { y4[k] = y3[k]; y3[k] = y2[k]; y2[k] = y1[k]; y1[k] = b[k]; y[4 * a + k] = accumulate ? y[4 * a + k] + b[k] : b[k]; }
             }
         }
     }
+}
+
+// Residual of the damped scaled system at y, per free keyframe a: r_a = -g_a - (A y)_a - (lmdiag_a / radius) y_a - (U U^T y)_a.  A from the band
+// rows (blocks (a, a-d) of row a and the transposed blocks (a+d, a) of rows a+d); U U^T y from the loop edges with two free ends in loop order,
+// as k_pg_forward scales them.  No atomics: two calls give the same bits.
+__global__ void k_pg_resid(int n, int nf, int n_loops, const Edge* __restrict__ E, const double* __restrict__ eJ, const double* __restrict__ s,
+                           const double* __restrict__ A, const double* __restrict__ lmdiag, double inv_radius, const double* __restrict__ g,
+                           const double* __restrict__ y, double* __restrict__ res) {
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= nf) return;
+    double acc[4];
+    for (int k = 0; k < 4; ++k) acc[k] = -g[4 * a + k] - lmdiag[4 * a + k] * inv_radius * y[4 * a + k];
+    const double* row = A + (size_t)a * kRow;
+    for (int d = 0; d < kBand && a - d >= 0; ++d)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) acc[r] -= row[16 * d + 4 * r + c] * y[4 * (a - d) + c];
+    for (int d = 1; d < kBand && a + d < nf; ++d) {
+        const double* B = A + (size_t)(a + d) * kRow + 16 * d;
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) acc[r] -= B[4 * c + r] * y[4 * (a + d) + c];
+    }
+    for (int l = 0; l < n_loops; ++l) {
+        const int e = 4 * n + l;
+        const Edge ed = E[e];
+        if (ed.a < 0 || ed.fa < 0 || ed.fb < 0 || (ed.fa != a && ed.fb != a)) continue;
+        for (int rr = 0; rr < 4; ++rr) {
+            double ja[4], jb[4], t = 0.0;
+            for (int c = 0; c < 4; ++c) { ja[c] = eJ[32 * e + 8 * rr + c] * s[4 * ed.fa + c]; jb[c] = eJ[32 * e + 8 * rr + 4 + c] * s[4 * ed.fb + c]; }
+            for (int c = 0; c < 4; ++c) t += ja[c] * y[4 * ed.fa + c] + jb[c] * y[4 * ed.fb + c];
+            const double* jm = ed.fa == a ? ja : jb;
+            for (int k = 0; k < 4; ++k) acc[k] -= jm[k] * t;
+        }
+    }
+    for (int k = 0; k < 4; ++k) res[4 * a + k] = acc[k];
+}
+
+// t(q) = sum_r W(r, q) W(r, zc) for q < zc over the rows column q's wave wrote (r >= 4 wstart), one lane per column, fixed row order.
+__global__ void __launch_bounds__(kWave) k_pg_wtz(int nf, int ncols, int zc, const double* __restrict__ W, const int* __restrict__ wstart,
+                                                  double* __restrict__ t) {
+    const int q = blockIdx.x * kWave + threadIdx.x;
+    if (q >= zc) return;
+    double acc = 0.0;
+    for (int r = 4 * wstart[q / kTile]; r < 4 * nf; ++r) acc += W[(size_t)r * ncols + q] * W[(size_t)r * ncols + zc];
+    t[q] = acc;
 }
 
 // candidate x + delta (free keyframes; yaw through NormalizeAngle), |x_c - x|^2 and |x|^2 partials over the free variables
@@ -641,6 +711,7 @@ struct uvs_pose_graph {
     double *er = nullptr, *eJ = nullptr, *ecost = nullptr, *emcc = nullptr;
     double *band = nullptr, *L = nullptr, *g = nullptr, *hdiag = nullptr, *lmdiag = nullptr, *s = nullptr, *gproj = nullptr;
     double *W = nullptr, *G = nullptr, *v = nullptr, *u = nullptr, *y = nullptr, *delta = nullptr, *part_step = nullptr, *part_x = nullptr;
+    double *res = nullptr, *wz = nullptr;           // refinement pass: residual, W_U^T L^-1 r
     double* scal = nullptr; int* fail = nullptr;     // device scalars
     double* h_scal = nullptr;                        // pinned: 8 doubles + fail flags
 };
@@ -654,6 +725,118 @@ int hip_fail(uvs_pose_graph* pg, hipError_t e, const char* what) {
 #define PG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(pg, e_, #call); } while (0)
 
 inline int grid_of(int n, int b) { return (n + b - 1) / b; }
+
+// Sizes of one problem, from the host bookkeeping of pg_setup.
+struct PgPlan {
+    int n = 0, nl = 0, nf = 0, nu = 0, zc = 0, ncols = 0, nwaves = 0, n_slots = 0, m = 0, n_edges = 0;
+};
+
+// Checks `p`, numbers the free keyframes, orders the loop edges with two free ends (U columns, sorted by the older end's free index),
+// uploads the problem and runs k_pg_prep + k_pg_meas.  `who` prefixes the error messages.
+int pg_setup(uvs_pose_graph* pg, const uvs_pg_problem* p, const char* who, PgPlan& P) {
+    if (!p || p->n < 1 || p->n_loops < 0 || !p->t || !p->q || !p->sequence || !p->constant || (p->n_loops > 0 && !p->loops)) {
+        pg->err = std::string(who) + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG;
+    }
+    const int n = p->n, nl = p->n_loops;
+    if (n > pg->max_n || nl > pg->max_l) { pg->err = std::string(who) + ": problem exceeds the capacity given to uvs_pg_create"; return UVS_ERR_CAPACITY; }
+    for (int l = 0; l < nl; ++l) {
+        const uvs_pg_loop& L = p->loops[l];
+        if (L.cur < 0 || L.cur >= n || L.old < 0 || L.old >= n || L.old >= L.cur) {
+            pg->err = std::string(who) + ": loop " + std::to_string(l) + " needs 0 <= old < cur < n"; return UVS_ERR_INVALID_ARG;
+        }
+    }
+    std::vector<int> fidx(n), kf_of_free; kf_of_free.reserve(n);
+    for (int i = 0; i < n; ++i) { fidx[i] = p->constant[i] ? -1 : (int)kf_of_free.size(); if (!p->constant[i]) kf_of_free.push_back(i); }
+    const int nf = (int)kf_of_free.size();
+    std::vector<int> ucol;
+    for (int l = 0; l < nl; ++l) if (fidx[p->loops[l].old] >= 0 && fidx[p->loops[l].cur] >= 0) ucol.push_back(4 * n + l);
+    std::stable_sort(ucol.begin(), ucol.end(), [&](int a, int b) { return fidx[p->loops[a - 4 * n].old] < fidx[p->loops[b - 4 * n].old]; });
+    const int nu = (int)ucol.size(), zc = 4 * nu, ncols = ((zc + 1 + kTile - 1) / kTile) * kTile, nwaves = ncols / kTile;
+    std::vector<int> wstart(nwaves, nf);
+    for (int q = 0; q < zc; ++q) wstart[q / kTile] = std::min(wstart[q / kTile], fidx[p->loops[ucol[q / 4] - 4 * n].old]);
+    wstart[zc / kTile] = 0;                                      // the -g column starts at row 0
+    int n_edges = 0;
+    for (int i = 0; i < n; ++i)
+        for (int j = 1; j <= 4; ++j) if (i - j >= 0 && p->sequence[i] == p->sequence[i - j] && (fidx[i] >= 0 || fidx[i - j] >= 0)) ++n_edges;
+    for (int l = 0; l < nl; ++l) if (fidx[p->loops[l].old] >= 0 || fidx[p->loops[l].cur] >= 0) ++n_edges;
+    P.n = n; P.nl = nl; P.nf = nf; P.nu = nu; P.zc = zc; P.ncols = ncols; P.nwaves = nwaves; P.n_slots = 4 * n + nl; P.m = 4 * nf; P.n_edges = n_edges;
+
+    PG_HIP(hipSetDevice(pg->device));
+    hipStream_t st = pg->st;
+    PG_HIP(hipMemcpyAsync(pg->t, p->t, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemcpyAsync(pg->q, p->q, (size_t)n * 4 * 8, hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemcpyAsync(pg->seq, p->sequence, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemcpyAsync(pg->fidx, fidx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (nf) PG_HIP(hipMemcpyAsync(pg->kf_of_free, kf_of_free.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+    if (nl) PG_HIP(hipMemcpyAsync(pg->loops, p->loops, (size_t)nl * sizeof(uvs_pg_loop), hipMemcpyHostToDevice, st));
+    if (nu) PG_HIP(hipMemcpyAsync(pg->ucol, ucol.data(), (size_t)nu * 4, hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemcpyAsync(pg->wstart, wstart.data(), (size_t)nwaves * 4, hipMemcpyHostToDevice, st));
+    PG_HIP(hipMemsetAsync(pg->fail, 0, 4 * 4, st));
+    k_pg_prep<<<grid_of(n, 256), 256, 0, st>>>(n, pg->t, pg->q, pg->x, pg->pr);
+    k_pg_meas<<<grid_of(P.n_slots, 256), 256, 0, st>>>(n, nl, pg->t, pg->q, pg->seq, pg->fidx, pg->x, pg->pr, pg->loops, pg->E);
+    // the host vectors above go out of scope: the copies must have read them
+    PG_HIP(hipStreamSynchronize(st));
+    return UVS_OK;
+}
+
+// Fixed-order reduction of up to four partial arrays into h_scal[0..3]; the fail flags into h_scal + 8.  Synchronizes the stream.
+int pg_reduce(uvs_pose_graph* pg, RedArgs ra) {
+    hipStream_t st = pg->st;
+    k_pg_reduce<<<1, 1024, 0, st>>>(ra, pg->scal);
+    PG_HIP(hipMemcpyAsync(pg->h_scal, pg->scal, 4 * 8, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    return UVS_OK;
+}
+
+// Linearize at x: h_scal = {cost, gradient max norm, |x|^2}.  first: the Jacobi scaling from this Jacobian.
+int pg_linearize(uvs_pose_graph* pg, const PgPlan& P, bool first) {
+    hipStream_t st = pg->st;
+    const int n = P.n, nf = P.nf, m = P.m, n_slots = P.n_slots;
+    k_pg_lin<0><<<grid_of(n_slots, 256), 256, 0, st>>>(n_slots, 4 * n, pg->E, pg->x, nullptr, pg->er, pg->eJ, pg->ecost, nullptr);
+    if (nf) {
+        k_pg_assemble<<<grid_of(nf, 128), 128, 0, st>>>(n, nf, P.nl, pg->kf_of_free, pg->fidx, pg->E, pg->er, pg->eJ, pg->x, pg->band, pg->g, pg->hdiag, pg->gproj);
+        if (first) k_pg_jacobi<<<grid_of(m, 256), 256, 0, st>>>(m, pg->hdiag, pg->s);
+        k_pg_scale<<<grid_of(nf, 256), 256, 0, st>>>(nf, pg->s, pg->band, pg->g, pg->hdiag, pg->lmdiag, kMinDiag, kMaxDiag);
+        k_pg_xnorm<<<grid_of(n, 256), 256, 0, st>>>(n, pg->fidx, pg->x, pg->part_x);
+    }
+    RedArgs ra = {{pg->ecost, nf ? pg->gproj : nullptr, nf ? pg->part_x : nullptr, nullptr}, {n_slots, nf, nf, 0}, {0, 1, 0, 0}};
+    return pg_reduce(pg, ra);
+}
+
+// The damped scaled system (A + U U^T + diag(lmdiag) / radius) y = -g -> pg->y (nf > 0); fail flags on the device.  Asynchronous.
+int pg_solve(uvs_pose_graph* pg, const PgPlan& P, double radius) {
+    hipStream_t st = pg->st;
+    const int nf = P.nf, nu = P.nu, zc = P.zc, ncols = P.ncols, nwaves = P.nwaves, m = P.m;
+    PG_HIP(hipMemsetAsync(pg->fail, 0, 4, st));
+    k_pg_factor<<<1, kWave, 0, st>>>(nf, pg->band, pg->lmdiag, 1.0 / radius, pg->L, pg->fail);
+    k_pg_forward<<<nwaves, kWave, 0, st>>>(nf, ncols, nu, 0, 0, pg->L, pg->ucol, pg->E, pg->eJ, pg->s, pg->g, -1.0, pg->wstart, pg->W);
+    if (nu) {
+        k_pg_gram<<<nwaves * (nwaves + 1) / 2, 256, 0, st>>>(nf, ncols, pg->W, pg->wstart, pg->G);
+        for (int k = 0; k < nwaves; ++k) {
+            k_pg_potrf<<<1, 256, 0, st>>>(ncols, k, pg->G, pg->fail + 1);
+            const int rest = nwaves - k - 1;
+            if (rest > 0) {
+                k_pg_trsm<<<rest, kTile, 0, st>>>(ncols, k, pg->G);
+                k_pg_syrk<<<rest * (rest + 1) / 2, 256, 0, st>>>(ncols, k, nwaves, pg->G);
+            }
+        }
+        k_pg_capsolve<<<1, 1024, 0, st>>>(ncols, zc, pg->G, nullptr, pg->v);
+    } else {
+        PG_HIP(hipMemsetAsync(pg->v, 0, (size_t)ncols * 8, st));
+    }
+    k_pg_wv<<<grid_of(m, 4), 256, 0, st>>>(m, ncols, zc, nwaves, pg->W, pg->wstart, pg->v, pg->u);
+    k_pg_back<<<1, kWave, 0, st>>>(nf, 0, pg->L, pg->u, pg->y);
+    if (UVS_PG_REFINE && nu) {       // y += (A + U U^T)^-1 r with the same L and capacitance factor, r = the FP64 residual at y
+        k_pg_resid<<<grid_of(nf, 128), 128, 0, st>>>(P.n, nf, P.nl, pg->E, pg->eJ, pg->s, pg->band, pg->lmdiag, 1.0 / radius, pg->g, pg->y, pg->res);
+        k_pg_forward<<<1, kWave, 0, st>>>(nf, ncols, nu, zc / kTile, 1, pg->L, pg->ucol, pg->E, pg->eJ, pg->s, pg->res, 1.0, pg->wstart, pg->W);
+        k_pg_wtz<<<grid_of(zc, kWave), kWave, 0, st>>>(nf, ncols, zc, pg->W, pg->wstart, pg->wz);
+        k_pg_capsolve<<<1, 1024, 0, st>>>(ncols, zc, pg->G, pg->wz, pg->v);
+        k_pg_wv<<<grid_of(m, 4), 256, 0, st>>>(m, ncols, zc, nwaves, pg->W, pg->wstart, pg->v, pg->u);
+        k_pg_back<<<1, kWave, 0, st>>>(nf, 1, pg->L, pg->u, pg->y);
+    }
+    return UVS_OK;
+}
 
 }  // namespace
 
@@ -682,7 +865,7 @@ int uvs_pg_create(int device, int max_keyframes, int max_loops, uvs_pose_graph**
         {(void**)&pg->band, N * kRow * 8}, {(void**)&pg->L, N * kRow * 8}, {(void**)&pg->g, M * 8}, {(void**)&pg->hdiag, M * 8},
         {(void**)&pg->lmdiag, M * 8}, {(void**)&pg->s, M * 8}, {(void**)&pg->gproj, N * 8},
         {(void**)&pg->W, M * C * 8}, {(void**)&pg->G, C * C * 8}, {(void**)&pg->v, C * 8}, {(void**)&pg->u, M * 8}, {(void**)&pg->y, M * 8},
-        {(void**)&pg->delta, M * 8}, {(void**)&pg->part_step, N * 8}, {(void**)&pg->part_x, N * 8},
+        {(void**)&pg->delta, M * 8}, {(void**)&pg->part_step, N * 8}, {(void**)&pg->part_x, N * 8}, {(void**)&pg->res, M * 8}, {(void**)&pg->wz, C * 8},
         {(void**)&pg->scal, 16 * 8}, {(void**)&pg->fail, 4 * 4},
     };
     for (auto& a : al)
@@ -698,7 +881,7 @@ void uvs_pg_destroy(uvs_pose_graph* pg) {
     if (pg->st) hipStreamSynchronize(pg->st);
     void* ptrs[] = {pg->t, pg->q, pg->seq, pg->fidx, pg->kf_of_free, pg->ucol, pg->wstart, pg->loops, pg->x, pg->xc, pg->pr, pg->E, pg->er, pg->eJ,
                     pg->ecost, pg->emcc, pg->band, pg->L, pg->g, pg->hdiag, pg->lmdiag, pg->s, pg->gproj, pg->W, pg->G, pg->v, pg->u, pg->y,
-                    pg->delta, pg->part_step, pg->part_x, pg->scal, pg->fail};
+                    pg->delta, pg->part_step, pg->part_x, pg->res, pg->wz, pg->scal, pg->fail};
     for (void* p : ptrs) if (p) hipFree(p);
     if (pg->h_scal) hipHostFree(pg->h_scal);
     if (pg->st) hipStreamDestroy(pg->st);
@@ -710,79 +893,22 @@ const char* uvs_pg_last_error(const uvs_pose_graph* pg) { return pg ? pg->err.c_
 int uvs_pg_optimize(uvs_pose_graph* pg, const uvs_pg_problem* p, double* out_yaw_t, uvs_pg_report* rep) {
     if (!pg) return UVS_ERR_INVALID_ARG;
     pg->err.clear();
-    if (!p || !out_yaw_t || p->n < 1 || p->n_loops < 0 || !p->t || !p->q || !p->sequence || !p->constant || (p->n_loops > 0 && !p->loops)) {
-        pg->err = "uvs_pg_optimize: null pointer or bad count"; return UVS_ERR_INVALID_ARG;
-    }
-    const int n = p->n, nl = p->n_loops;
-    if (n > pg->max_n || nl > pg->max_l) { pg->err = "uvs_pg_optimize: problem exceeds the capacity given to uvs_pg_create"; return UVS_ERR_CAPACITY; }
-    for (int l = 0; l < nl; ++l) {
-        const uvs_pg_loop& L = p->loops[l];
-        if (L.cur < 0 || L.cur >= n || L.old < 0 || L.old >= n || L.old >= L.cur) {
-            pg->err = "uvs_pg_optimize: loop " + std::to_string(l) + " needs 0 <= old < cur < n"; return UVS_ERR_INVALID_ARG;
-        }
-    }
-    uvs_pg_report R; std::memset(&R, 0, sizeof(R));
-    // host bookkeeping: free numbering, the loop edges with two free ends (U columns, sorted by the older end's free index)
-    std::vector<int> fidx(n), kf_of_free; kf_of_free.reserve(n);
-    for (int i = 0; i < n; ++i) { fidx[i] = p->constant[i] ? -1 : (int)kf_of_free.size(); if (!p->constant[i]) kf_of_free.push_back(i); }
-    const int nf = (int)kf_of_free.size();
-    std::vector<int> ucol;
-    for (int l = 0; l < nl; ++l) if (fidx[p->loops[l].old] >= 0 && fidx[p->loops[l].cur] >= 0) ucol.push_back(4 * n + l);
-    std::stable_sort(ucol.begin(), ucol.end(), [&](int a, int b) { return fidx[p->loops[a - 4 * n].old] < fidx[p->loops[b - 4 * n].old]; });
-    const int nu = (int)ucol.size(), zc = 4 * nu, ncols = ((zc + 1 + kTile - 1) / kTile) * kTile, nwaves = ncols / kTile;
-    std::vector<int> wstart(nwaves, nf);
-    for (int q = 0; q < zc; ++q) wstart[q / kTile] = std::min(wstart[q / kTile], fidx[p->loops[ucol[q / 4] - 4 * n].old]);
-    wstart[zc / kTile] = 0;                                      // the -g column starts at row 0
-    int n_edges = 0;
-    for (int i = 0; i < n; ++i)
-        for (int j = 1; j <= 4; ++j) if (i - j >= 0 && p->sequence[i] == p->sequence[i - j] && (fidx[i] >= 0 || fidx[i - j] >= 0)) ++n_edges;
-    for (int l = 0; l < nl; ++l) if (fidx[p->loops[l].old] >= 0 || fidx[p->loops[l].cur] >= 0) ++n_edges;
-    R.n_free = nf; R.n_edges = n_edges; R.n_loop_columns = zc;
-
-    PG_HIP(hipSetDevice(pg->device));
+    if (!out_yaw_t) { pg->err = "uvs_pg_optimize: null pointer or bad count"; return UVS_ERR_INVALID_ARG; }
+    PgPlan P;
+    int rc = pg_setup(pg, p, "uvs_pg_optimize", P);
+    if (rc) return rc;
+    const int n = P.n, nf = P.nf, n_slots = P.n_slots;
     hipStream_t st = pg->st;
-    PG_HIP(hipMemcpyAsync(pg->t, p->t, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->q, p->q, (size_t)n * 4 * 8, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->seq, p->sequence, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->fidx, fidx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (nf) PG_HIP(hipMemcpyAsync(pg->kf_of_free, kf_of_free.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    if (nl) PG_HIP(hipMemcpyAsync(pg->loops, p->loops, (size_t)nl * sizeof(uvs_pg_loop), hipMemcpyHostToDevice, st));
-    if (nu) PG_HIP(hipMemcpyAsync(pg->ucol, ucol.data(), (size_t)nu * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->wstart, wstart.data(), (size_t)nwaves * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemsetAsync(pg->fail, 0, 4 * 4, st));
-
-    const int n_slots = 4 * n + nl, m = 4 * nf;
-    k_pg_prep<<<grid_of(n, 256), 256, 0, st>>>(n, pg->t, pg->q, pg->x, pg->pr);
-    k_pg_meas<<<grid_of(n_slots, 256), 256, 0, st>>>(n, nl, pg->t, pg->q, pg->seq, pg->fidx, pg->x, pg->pr, pg->loops, pg->E);
+    uvs_pg_report R; std::memset(&R, 0, sizeof(R));
+    R.n_free = nf; R.n_edges = P.n_edges; R.n_loop_columns = P.zc;
 
     // Ceres' defaults, max_num_iterations = 5 (pose_graph.cpp:433)
     const int max_iter = 5;
-    const double init_radius = 1e4, max_radius = 1e16, min_radius = 1e-32, min_rel_dec = 1e-3, min_d = 1e-6, max_d = 1e32;
+    const double init_radius = 1e4, max_radius = 1e16, min_radius = 1e-32, min_rel_dec = 1e-3;
     const double ftol = 1e-6, gtol = 1e-10, ptol = 1e-8;
     const int max_invalid = 5;
 
-    auto reduce = [&](RedArgs ra) -> int {
-        k_pg_reduce<<<1, 1024, 0, st>>>(ra, pg->scal);
-        PG_HIP(hipMemcpyAsync(pg->h_scal, pg->scal, 4 * 8, hipMemcpyDeviceToHost, st));
-        PG_HIP(hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
-        PG_HIP(hipStreamSynchronize(st));
-        return UVS_OK;
-    };
-    // linearize at x: cost, gradient max norm, |x|
-    auto linearize = [&](bool first) -> int {
-        k_pg_lin<0><<<grid_of(n_slots, 256), 256, 0, st>>>(n_slots, 4 * n, pg->E, pg->x, nullptr, pg->er, pg->eJ, pg->ecost, nullptr);
-        if (nf) {
-            k_pg_assemble<<<grid_of(nf, 128), 128, 0, st>>>(n, nf, nl, pg->kf_of_free, pg->fidx, pg->E, pg->er, pg->eJ, pg->x, pg->band, pg->g, pg->hdiag, pg->gproj);
-            if (first) k_pg_jacobi<<<grid_of(m, 256), 256, 0, st>>>(m, pg->hdiag, pg->s);
-            k_pg_scale<<<grid_of(nf, 256), 256, 0, st>>>(nf, pg->s, pg->band, pg->g, pg->hdiag, pg->lmdiag, min_d, max_d);
-            k_pg_xnorm<<<grid_of(n, 256), 256, 0, st>>>(n, pg->fidx, pg->x, pg->part_x);
-        }
-        RedArgs ra = {{pg->ecost, nf ? pg->gproj : nullptr, nf ? pg->part_x : nullptr, nullptr}, {n_slots, nf, nf, 0}, {0, 1, 0, 0}};
-        return reduce(ra);
-    };
-
-    int rc = linearize(true);
-    if (rc) return rc;
+    if ((rc = pg_linearize(pg, P, true))) return rc;
     double cost = pg->h_scal[0], gmax = pg->h_scal[1], x_norm = std::sqrt(pg->h_scal[2]);
     R.initial_cost = cost; R.cost[0] = cost; R.radius[0] = init_radius; R.accepted[0] = 1;
     double radius = init_radius, decrease_factor = 2.0;
@@ -795,30 +921,11 @@ int uvs_pg_optimize(uvs_pose_graph* pg, const uvs_pg_problem* p, double* out_yaw
             if (gmax <= gtol) { term = UVS_TERM_GRADIENT_TOL; break; }
             if (radius <= min_radius) { term = UVS_TERM_MIN_RADIUS; break; }
             ++it;
-            // damped system -> y (scaled step)
-            PG_HIP(hipMemsetAsync(pg->fail, 0, 4, st));
-            k_pg_factor<<<1, kWave, 0, st>>>(nf, pg->band, pg->lmdiag, 1.0 / radius, pg->L, pg->fail);
-            k_pg_forward<<<nwaves, kWave, 0, st>>>(nf, ncols, nu, pg->L, pg->ucol, pg->E, pg->eJ, pg->s, pg->g, pg->wstart, pg->W);
-            if (nu) {
-                k_pg_gram<<<nwaves * (nwaves + 1) / 2, 256, 0, st>>>(nf, ncols, pg->W, pg->wstart, pg->G);
-                for (int k = 0; k < nwaves; ++k) {
-                    k_pg_potrf<<<1, 256, 0, st>>>(ncols, k, pg->G, pg->fail + 1);
-                    const int rest = nwaves - k - 1;
-                    if (rest > 0) {
-                        k_pg_trsm<<<rest, kTile, 0, st>>>(ncols, k, pg->G);
-                        k_pg_syrk<<<rest * (rest + 1) / 2, 256, 0, st>>>(ncols, k, nwaves, pg->G);
-                    }
-                }
-                k_pg_capsolve<<<1, 1024, 0, st>>>(ncols, zc, pg->G, pg->v);
-            } else {
-                PG_HIP(hipMemsetAsync(pg->v, 0, (size_t)ncols * 8, st));
-            }
-            k_pg_wv<<<grid_of(m, 4), 256, 0, st>>>(m, ncols, zc, nwaves, pg->W, pg->wstart, pg->v, pg->u);
-            k_pg_back<<<1, kWave, 0, st>>>(nf, pg->L, pg->u, pg->y);
+            if ((rc = pg_solve(pg, P, radius))) return rc;       // damped system -> y (scaled step)
             k_pg_step<<<grid_of(n, 256), 256, 0, st>>>(n, pg->fidx, pg->s, pg->y, pg->x, pg->delta, pg->xc, pg->part_step);
             k_pg_lin<1><<<grid_of(n_slots, 256), 256, 0, st>>>(n_slots, 4 * n, pg->E, pg->xc, pg->delta, pg->er, pg->eJ, pg->ecost, pg->emcc);
             RedArgs ra = {{pg->ecost, pg->emcc, pg->part_step, nullptr}, {n_slots, n_slots, nf, 0}, {0, 0, 0, 0}};
-            if ((rc = reduce(ra))) return rc;
+            if ((rc = pg_reduce(pg, ra))) return rc;
             const double cand_raw = pg->h_scal[0], mcc = pg->h_scal[1], step_norm = std::sqrt(pg->h_scal[2]);
             const int* hf = reinterpret_cast<const int*>(pg->h_scal + 8);
             const bool solve_ok = hf[0] == 0 && hf[1] == 0;
@@ -841,7 +948,7 @@ int uvs_pg_optimize(uvs_pose_graph* pg, const uvs_pg_problem* p, double* out_yaw
             if (stop >= 0) { R.accepted[it] = 0; R.radius[it] = radius; R.cost[it] = cost; term = stop; break; }
             if (successful) {
                 std::swap(pg->x, pg->xc);
-                if ((rc = linearize(false))) return rc;
+                if ((rc = pg_linearize(pg, P, false))) return rc;
                 cost = pg->h_scal[0]; gmax = pg->h_scal[1]; x_norm = std::sqrt(pg->h_scal[2]);
                 radius = std::min(max_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
                 decrease_factor = 2.0;
@@ -859,6 +966,29 @@ int uvs_pg_optimize(uvs_pose_graph* pg, const uvs_pg_problem* p, double* out_yaw
     PG_HIP(hipStreamSynchronize(st));
     if (rep) *rep = R;
     return R.status;
+}
+
+int uvs_pg_debug_step(uvs_pose_graph* pg, const uvs_pg_problem* p, double radius, double* delta, double* scal) {
+    if (!pg) return UVS_ERR_INVALID_ARG;
+    pg->err.clear();
+    if (!delta || !scal) { pg->err = "uvs_pg_debug_step: null pointer or bad count"; return UVS_ERR_INVALID_ARG; }
+    if (!std::isfinite(radius) || !(radius > 0.0)) { pg->err = "uvs_pg_debug_step: radius must be finite and > 0"; return UVS_ERR_INVALID_ARG; }
+    PgPlan P;
+    int rc = pg_setup(pg, p, "uvs_pg_debug_step", P);
+    if (rc) return rc;
+    if ((rc = pg_linearize(pg, P, true))) return rc;
+    for (int k = 0; k < UVS_PG_DEBUG_SCAL_LEN; ++k) scal[k] = 0.0;
+    scal[2] = P.zc; scal[3] = P.nf;
+    if (P.nf == 0) return UVS_OK;
+    hipStream_t st = pg->st;
+    if ((rc = pg_solve(pg, P, radius))) return rc;
+    k_pg_step<<<grid_of(P.n, 256), 256, 0, st>>>(P.n, pg->fidx, pg->s, pg->y, pg->x, pg->delta, pg->xc, pg->part_step);
+    PG_HIP(hipMemcpyAsync(delta, pg->delta, (size_t)P.m * 8, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    const int* hf = reinterpret_cast<const int*>(pg->h_scal + 8);
+    scal[0] = hf[0]; scal[1] = hf[1];
+    return UVS_OK;
 }
 
 }  // extern "C"
