@@ -454,6 +454,67 @@ int uvs_pg_optimize(uvs_pose_graph *pg, const uvs_pg_problem *problem, double *o
 #define UVS_PG_DEBUG_SCAL_LEN 4
 int uvs_pg_debug_step(uvs_pose_graph *pg, const uvs_pg_problem *problem, double radius, double *delta, double *scal);
 
+/* ---- loop verification of loop closure (reference pose_graph/src/keyframe.cpp:259-521, KeyFrame::findConnection) ----
+ * Verifies a batch of candidate pairs (current keyframe, old keyframe as place recognition proposed it) in one call; a pair gives the same
+ * bits alone or in a batch.  Per pair: each window point of the current keyframe is matched to the old keypoint of smallest Hamming distance
+ * over its 256-bit BRIEF descriptor (ties: the first index; kept when the distance is < 80); with > 25 matches, a PnP-RANSAC (100 hypotheses
+ * of 5 points, each an LM from the VIO prior, inlier threshold 10 / 460 in normalized coordinates, OpenCV's adaptive iteration rule) and an
+ * LM refinement on the chosen hypothesis's inliers give the old keyframe's body pose; with > 25 inliers, loop_info as the reference builds it,
+ * accepted when |relative yaw| < 30 deg and |relative t| < 20 m.  The numerics (sample generator, LM, selection) are spelled out in
+ * csrc/uvs_loop_verify.hip and restated in tests/lc_ref.py; DESIGN.md 3.7 lists where they deviate from OpenCV.
+ * No CPU path: uvs_lc_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_LC_MAX_PAIRS 4096                 /* largest max_pairs uvs_lc_create takes            */
+#define UVS_LC_MAX_QUERY 1024                 /* largest max_query (window points of a keyframe)  */
+#define UVS_LC_MAX_OLD 4096                   /* largest max_old (keypoints of an old keyframe)   */
+#define UVS_LC_N_HYPOTHESES 100               /* solvePnPRansac iterationsCount (keyframe.cpp:232) */
+typedef struct uvs_loop_verifier uvs_loop_verifier;  /* opaque: device buffers, pinned staging, stream */
+
+enum {
+    UVS_LC_ACCEPTED = 0,
+    UVS_LC_NO_MATCHES = 1,         /* no window point matched (also n_query = 0 or n_old = 0) */
+    UVS_LC_FEW_MATCHES = 2,        /* matches <= MIN_LOOP_NUM (25) */
+    UVS_LC_RANSAC_FAILED = 3,      /* no hypothesis with >= 5 inliers */
+    UVS_LC_FEW_INLIERS = 4,        /* inliers <= 25 */
+    UVS_LC_YAW_GATE = 5,           /* |relative yaw| >= 30 deg */
+    UVS_LC_T_GATE = 6              /* |relative t| >= 20 m */
+};
+
+typedef struct uvs_lc_pair {
+    int32_t n_query;                   /* window points of the current keyframe, 0 .. max_query */
+    int32_t n_old;                     /* keypoints of the old keyframe, 0 .. max_old */
+    const double *p3d;                 /* [n_query][3] point_3d, in the current keyframe's VIO world frame */
+    const uint64_t *desc;              /* [n_query][4] window_brief_descriptors */
+    double vio_t[3];                   /* origin_vio_T of the current keyframe */
+    double vio_q[4];                   /* origin_vio_R as a unit quaternion (x, y, z, w) */
+    const double *old_uv_norm;         /* [n_old][2] keypoints_norm of the old keyframe */
+    const uint64_t *old_desc;          /* [n_old][4] brief_descriptors of the old keyframe */
+    uint64_t seed;                     /* keys the RANSAC sample generator */
+} uvs_lc_pair;
+
+typedef struct uvs_lc_result {
+    int32_t accepted;                  /* 1: the loop passes every gate */
+    int32_t reason;                    /* UVS_LC_* */
+    int32_t n_matches;
+    int32_t n_inliers;                 /* inliers of the chosen hypothesis (0 before RANSAC) */
+    int32_t best_hypothesis;           /* -1: none */
+    int32_t ransac_iters;              /* hypotheses the sequential adaptive rule examined */
+    double loop_info[8];               /* relative t (3), relative q (w, x, y, z), relative yaw (deg): keyframe.cpp:485 order */
+    double PnP_T_old[3];               /* body pose of the old keyframe from PnP */
+    double PnP_q_old[4];               /* (x, y, z, w) */
+    int32_t hyp_inliers[UVS_LC_N_HYPOTHESES];   /* inlier count of every hypothesis, -1 invalid (all -1 when RANSAC did not run) */
+} uvs_lc_result;
+
+int uvs_lc_create(int device, int max_pairs, int max_query, int max_old, uvs_loop_verifier **out);
+void uvs_lc_destroy(uvs_loop_verifier *lc);
+const char *uvs_lc_last_error(const uvs_loop_verifier *lc);
+/* tic[3], qic_xyzw[4]: the camera-IMU extrinsic.  match_old[] and inlier[] hold one entry per window point, concatenated over the pairs in
+ * order: the matched old keypoint index or -1, and 1 for a match that is an inlier of the chosen hypothesis.  results[n_pairs].
+ * UVS_ERR_INVALID_ARG: null pointer, n_pairs < 1, a negative count, a null array behind a positive count, or qic / a vio_q that is not a
+ * unit quaternion (|norm - 1| > 1e-6); UVS_ERR_CAPACITY: n_pairs, n_query or n_old above the handle's capacity.  A pair with n_query = 0
+ * or n_old = 0 is rejected (UVS_LC_NO_MATCHES), not an error. */
+int uvs_lc_verify(uvs_loop_verifier *lc, int n_pairs, const uvs_lc_pair *pairs, const double tic[3], const double qic_xyzw[4],
+                  int32_t *match_old, uint8_t *inlier, uvs_lc_result *results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -421,3 +421,53 @@ def pg_problem(t, q, sequence, constant, loops):
     p.t, p.q, p.sequence, p.constant = _dp(k["t"]), _dp(k["q"]), _ip(k["sequence"]), _ip(k["constant"])
     p.loops = C.cast(arr, C.POINTER(PgLoop))
     return p, k
+
+
+# ---- loop verification of loop closure (uvs_lc_*, include/uvs_solver.h) ------------------------------------------------
+LC_MAX_PAIRS = 4096
+LC_MAX_QUERY = 1024
+LC_MAX_OLD = 4096
+LC_N_HYPOTHESES = 100
+LC_REASONS = ["ACCEPTED", "NO_MATCHES", "FEW_MATCHES", "RANSAC_FAILED", "FEW_INLIERS", "YAW_GATE", "T_GATE"]      # uvs_lc_result.reason
+c_u64_p = C.POINTER(C.c_uint64)
+
+
+class LcPair(C.Structure):
+    _fields_ = [("n_query", C.c_int32), ("n_old", C.c_int32), ("p3d", c_double_p), ("desc", c_u64_p), ("vio_t", C.c_double * 3),
+                ("vio_q", C.c_double * 4), ("old_uv_norm", c_double_p), ("old_desc", c_u64_p), ("seed", C.c_uint64)]
+
+
+class LcResult(C.Structure):
+    _fields_ = [
+        ("accepted", C.c_int32), ("reason", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32),
+        ("best_hypothesis", C.c_int32), ("ransac_iters", C.c_int32),
+        ("loop_info", C.c_double * 8), ("PnP_T_old", C.c_double * 3), ("PnP_q_old", C.c_double * 4),
+        ("hyp_inliers", C.c_int32 * LC_N_HYPOTHESES),
+    ]
+
+    def as_dict(self):
+        return dict(accepted=int(self.accepted), reason=int(self.reason), n_matches=int(self.n_matches), n_inliers=int(self.n_inliers),
+                    best_hypothesis=int(self.best_hypothesis), ransac_iters=int(self.ransac_iters), loop_info=np.array(self.loop_info[:]),
+                    PnP_T_old=np.array(self.PnP_T_old[:]), PnP_q_old=np.array(self.PnP_q_old[:]),
+                    hyp_inliers=np.array(self.hyp_inliers[:], np.int32))
+
+
+def lc_pairs(pairs):
+    """(LcPair array, keepalive) from dicts with p3d [nq,3], qdesc [nq,4] uint64, vio_t [3], vio_q [4] (x,y,z,w), uv [no,2], odesc [no,4] uint64,
+    seed."""
+    arr = (LcPair * max(len(pairs), 1))()
+    keep = []
+    for b, d in enumerate(pairs):
+        p3d = np.ascontiguousarray(d["p3d"], dtype=np.float64).reshape(-1, 3); qd = np.ascontiguousarray(d["qdesc"], dtype=np.uint64).reshape(-1, 4)
+        uv = np.ascontiguousarray(d["uv"], dtype=np.float64).reshape(-1, 2); od = np.ascontiguousarray(d["odesc"], dtype=np.uint64).reshape(-1, 4)
+        keep += [p3d, qd, uv, od]
+        e = arr[b]
+        e.n_query, e.n_old = len(p3d), len(uv)
+        e.p3d, e.desc = _dp(p3d), qd.ctypes.data_as(c_u64_p)
+        e.old_uv_norm, e.old_desc = _dp(uv), od.ctypes.data_as(c_u64_p)
+        for c in range(3):
+            e.vio_t[c] = float(d["vio_t"][c])
+        for c in range(4):
+            e.vio_q[c] = float(d["vio_q"][c])
+        e.seed = int(d["seed"]) & ((1 << 64) - 1)
+    return arr, keep

@@ -20,6 +20,7 @@ EXPORTS = [
     "uvs_abi_version", "uvs_default_options", "uvs_create", "uvs_destroy", "uvs_last_error", "uvs_status_string",
     "uvs_solve_window", "uvs_batch_upload", "uvs_batch_solve", "uvs_batch_download", "uvs_batch_stream", "uvs_evaluate", "uvs_marginalize", "uvs_marginalize_resident", "uvs_marginalize_batch",
     "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step",
+    "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify",
 ]
 
 
@@ -78,6 +79,12 @@ def lib():
         L.uvs_pg_optimize.argtypes = [C.c_void_p, C.POINTER(abi.PgProblem), abi.c_double_p, C.POINTER(abi.PgReport)]; L.uvs_pg_optimize.restype = C.c_int
         L.uvs_pg_debug_step.argtypes = [C.c_void_p, C.POINTER(abi.PgProblem), C.c_double, abi.c_double_p, abi.c_double_p]
         L.uvs_pg_debug_step.restype = C.c_int
+        L.uvs_lc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_lc_create.restype = C.c_int
+        L.uvs_lc_destroy.argtypes = [C.c_void_p]; L.uvs_lc_destroy.restype = None
+        L.uvs_lc_last_error.argtypes = [C.c_void_p]; L.uvs_lc_last_error.restype = C.c_char_p
+        L.uvs_lc_verify.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LcPair), abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_uint8), C.POINTER(abi.LcResult)]
+        L.uvs_lc_verify.restype = C.c_int
         _lib = L
     return _lib
 
@@ -371,3 +378,57 @@ class PoseGraphSolver:
         if rc != abi.UVS_OK:
             raise RuntimeError(f"uvs_pg_debug_step: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
         return delta, dict(factor_fail=int(scal[0]), capacitance_fail=int(scal[1]), n_loop_columns=int(scal[2]), n_free=int(scal[3]))
+
+
+class LoopVerifier:
+    """Owns one `uvs_loop_verifier` handle: loop verification of loop closure (KeyFrame::findConnection: BRIEF matching + PnP-RANSAC) on
+    one GPU, a batch of candidate pairs per call.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    def __init__(self, device=0, max_pairs=64, max_query=1024, max_old=4096):
+        self._h = C.c_void_p()
+        rc = lib().uvs_lc_create(device, max_pairs, max_query, max_old, C.byref(self._h))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_lc_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
+
+    def close(self):
+        if self._h:
+            lib().uvs_lc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def verify_raw(self, pairs, tic, qic, n_pairs=None, null=()):
+        """-> (return code, [result dict], [match_old per pair], [inlier per pair]) without raising: for the tests of the argument checks.
+        n_pairs overrides the count passed; `null` names arguments passed as NULL ("pairs", "tic", "qic", "match_old", "inlier", "results")."""
+        arr, keep = abi.lc_pairs(pairs)
+        nq = [int(arr[b].n_query) for b in range(len(pairs))]
+        tq = max(sum(nq), 1)
+        tic = np.ascontiguousarray(tic, dtype=np.float64); qic = np.ascontiguousarray(qic, dtype=np.float64)
+        mo = np.zeros(tq, np.int32); inl = np.zeros(tq, np.uint8)
+        res = (abi.LcResult * max(len(pairs), 1))()
+        args = dict(pairs=C.cast(arr, C.POINTER(abi.LcPair)), tic=abi._dp(tic), qic=abi._dp(qic), match_old=mo.ctypes.data_as(C.POINTER(C.c_int32)),
+                    inlier=inl.ctypes.data_as(C.POINTER(C.c_uint8)), results=C.cast(res, C.POINTER(abi.LcResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_lc_verify(self._h, len(pairs) if n_pairs is None else int(n_pairs), args["pairs"], args["tic"], args["qic"],
+                                 args["match_old"], args["inlier"], args["results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernel, download
+        off = np.r_[0, np.cumsum(nq)].astype(int)
+        return (rc, [res[b].as_dict() for b in range(len(pairs))], [mo[off[b]:off[b + 1]].copy() for b in range(len(pairs))],
+                [inl[off[b]:off[b + 1]].copy() for b in range(len(pairs))])
+
+    def verify(self, pairs, tic, qic):
+        """pairs: list of dicts (p3d [nq,3] in the current keyframe's VIO frame, qdesc [nq,4] uint64, vio_t [3], vio_q [4] (x,y,z,w) of its
+        origin_vio pose, uv [no,2] normalized keypoints and odesc [no,4] uint64 of the old keyframe, seed); tic [3], qic [4] (x,y,z,w) the
+        extrinsic.  -> (results: list of dicts with the uvs_lc_result fields, match_old: list of int32 [nq], inlier: list of uint8 [nq])."""
+        rc, res, mo, inl = self.verify_raw(pairs, tic, qic)
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_lc_verify: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
+        return res, mo, inl

@@ -1,6 +1,8 @@
 // pose_graph.cpp -- see pose_graph.h.  Reference line numbers are those of pose_graph/src/pose_graph.cpp.
 #include "pose_graph.h"
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <stdexcept>
 #include "utility.h"
@@ -9,14 +11,50 @@ void KeyFrame::updateLoop(const LoopInfo& info) {          // keyframe.cpp:571-5
     if (std::fabs(info[7]) < 30.0 && std::sqrt(info[0] * info[0] + info[1] * info[1] + info[2] * info[2]) < 20.0) loop_info = info;
 }
 
+bool KeyFrame::findConnection(KeyFrame* old_kf, uvs_loop_verifier* lc, const Eigen::Vector3d& tic, const Eigen::Quaterniond& qic) {
+    const int n = (int)point_3d.size();
+    std::vector<double> p3d(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) { p3d[3 * i] = point_3d[i].x(); p3d[3 * i + 1] = point_3d[i].y(); p3d[3 * i + 2] = point_3d[i].z(); }
+    const Eigen::Quaterniond q = Eigen::Quaterniond(origin_vio_R).normalized();
+    uvs_lc_pair p;
+    p.n_query = n; p.n_old = (int)old_kf->keypoints_norm.size();
+    p.p3d = p3d.data(); p.desc = window_brief_descriptors.empty() ? nullptr : window_brief_descriptors[0].data();
+    p.vio_t[0] = origin_vio_T.x(); p.vio_t[1] = origin_vio_T.y(); p.vio_t[2] = origin_vio_T.z();
+    p.vio_q[0] = q.x(); p.vio_q[1] = q.y(); p.vio_q[2] = q.z(); p.vio_q[3] = q.w();
+    p.old_uv_norm = old_kf->keypoints_norm.empty() ? nullptr : old_kf->keypoints_norm[0].data();
+    p.old_desc = old_kf->brief_descriptors.empty() ? nullptr : old_kf->brief_descriptors[0].data();
+    p.seed = ((uint64_t)(uint32_t)index << 32) | (uint64_t)(uint32_t)old_kf->index;
+    const double t[3] = {tic.x(), tic.y(), tic.z()}, qx[4] = {qic.x(), qic.y(), qic.z(), qic.w()};
+    std::vector<int32_t> match_old(std::max(n, 1));
+    std::vector<uint8_t> inlier(std::max(n, 1));
+    if ((int)window_brief_descriptors.size() != n || old_kf->brief_descriptors.size() != old_kf->keypoints_norm.size() ||
+        uvs_lc_verify(lc, 1, &p, t, qx, match_old.data(), inlier.data(), &last_verify) != UVS_OK) {
+        last_verify = uvs_lc_result{}; last_verify.reason = -1;
+        return false;
+    }
+    matched_2d_old_norm.clear(); matched_id.clear();                 // :392-399, the PnP inliers in query order
+    for (int i = 0; i < n; ++i)
+        if (inlier[i]) {
+            matched_2d_old_norm.push_back(old_kf->keypoints_norm[match_old[i]]);
+            matched_id.push_back(i < (int)point_id.size() ? point_id[i] : (double)i);
+        }
+    if (!last_verify.accepted) return false;
+    has_loop = true; loop_index = old_kf->index;                     // :478-487
+    for (int k = 0; k < 8; ++k) loop_info[k] = last_verify.loop_info[k];
+    return true;
+}
+
 PoseGraph::PoseGraph(int device, int max_keyframes, int max_loops) {
     sequence_loop.push_back(0);                             // :14
-    const int rc = uvs_pg_create(device, max_keyframes, max_loops, &pg_);
+    int rc = uvs_pg_create(device, max_keyframes, max_loops, &pg_);
     if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_pg_create: ") + uvs_status_string(rc));
+    rc = uvs_lc_create(device, 1, UVS_LC_MAX_QUERY, UVS_LC_MAX_OLD, &lc_);
+    if (rc != UVS_OK) { uvs_pg_destroy(pg_); throw std::runtime_error(std::string("uvs_lc_create: ") + uvs_status_string(rc)); }
 }
 
 PoseGraph::~PoseGraph() {
     uvs_pg_destroy(pg_);
+    uvs_lc_destroy(lc_);
     for (KeyFrame* kf : keyframelist) delete kf;
 }
 
@@ -26,6 +64,15 @@ KeyFrame* PoseGraph::getKeyFrame(int index) {
 }
 
 void PoseGraph::addKeyFrame(KeyFrame* cur_kf, int loop_index, const LoopInfo* loop_info) {
+    addKeyFrameImpl(cur_kf, -1, loop_index, loop_info);
+}
+
+bool PoseGraph::addKeyFrameWithCandidate(KeyFrame* cur_kf, int candidate_index) {
+    addKeyFrameImpl(cur_kf, candidate_index, -1, nullptr);
+    return cur_kf->has_loop;
+}
+
+void PoseGraph::addKeyFrameImpl(KeyFrame* cur_kf, int candidate_index, int loop_index, const LoopInfo* loop_info) {
     Eigen::Vector3d vio_P_cur;
     Eigen::Matrix3d vio_R_cur;
     if (sequence_cnt != cur_kf->sequence) {                 // :45-56 a new sequence starts in its own VIO frame
@@ -39,6 +86,10 @@ void PoseGraph::addKeyFrame(KeyFrame* cur_kf, int loop_index, const LoopInfo* lo
     vio_R_cur = w_r_vio * vio_R_cur;
     cur_kf->updateVioPose(vio_P_cur, vio_R_cur);
     cur_kf->index = global_index++;
+    if (candidate_index >= 0) {                             // :64-77 detectLoop's candidate, then findConnection
+        KeyFrame* cand = getKeyFrame(candidate_index);
+        if (cand && cur_kf->findConnection(cand, lc_, tic_, qic_)) { loop_index = candidate_index; loop_info = &cur_kf->loop_info; }
+    }
     KeyFrame* old_kf = loop_index >= 0 ? getKeyFrame(loop_index) : nullptr;
     if (old_kf && loop_info) {                               // :75-121, with findConnection's outcome given
         cur_kf->has_loop = true; cur_kf->loop_index = loop_index; cur_kf->loop_info = *loop_info;

@@ -1,7 +1,10 @@
 // pose_graph.h -- mirror of the optimizer half of pose_graph/src/pose_graph.{h,cpp} and keyframe.{h,cpp} (loop closure): the keyframe list,
 // the sequence shift and drift bookkeeping of addKeyFrame (:42-211), updateKeyFrameLoop (:888-...) / KeyFrame::updateLoop (keyframe.cpp:571-578)
-// and a synchronous optimize4DoF (:403-579) whose ceres::Solve is uvs_pg_optimize().  Loop DETECTION (BRIEF, DBoW2, findConnection's PnP-RANSAC)
-// is not mirrored: addKeyFrame takes the loop as the caller found it.  No polling thread, no save / load, no visualization.
+// and a synchronous optimize4DoF (:403-579) whose ceres::Solve is uvs_pg_optimize(); KeyFrame::findConnection (keyframe.cpp:259-521: BRIEF
+// matching, PnP-RANSAC, the loop_info gates) runs on the GPU through uvs_lc_verify().  Place recognition (DBoW2 detectLoop) and BRIEF / FAST
+// extraction are not mirrored: addKeyFrameWithCandidate takes the candidate detectLoop would return, keyframes carry their descriptors and
+// normalized keypoints as the caller extracted them, and addKeyFrame still takes a loop as the caller found it.  No polling thread, no save /
+// load, no visualization.
 #pragma once
 #include <array>
 #include <list>
@@ -21,9 +24,23 @@ struct KeyFrame {
     bool has_loop = false;
     int loop_index = -1;
     LoopInfo loop_info{};
+    // what findConnection reads (keyframe.h): the VIO pose at creation (never shifted), the window points with their 3-D positions in that
+    // VIO frame, their normalized coordinates, ids and BRIEF descriptors, and the keyframe's own keypoints (as an old keyframe)
+    Eigen::Vector3d origin_vio_T;
+    Eigen::Matrix3d origin_vio_R = Eigen::Matrix3d::Identity();
+    std::vector<Eigen::Vector3d> point_3d;
+    std::vector<std::array<double, 2>> point_2d_norm;
+    std::vector<double> point_id;
+    std::vector<std::array<uint64_t, 4>> window_brief_descriptors;
+    std::vector<std::array<double, 2>> keypoints_norm;
+    std::vector<std::array<uint64_t, 4>> brief_descriptors;
+    // findConnection's inlier matches (matched_2d_old_norm, matched_id: what Estimator::setReloFrame takes) and its verdict
+    std::vector<std::array<double, 2>> matched_2d_old_norm;
+    std::vector<double> matched_id;
+    uvs_lc_result last_verify{};
 
     KeyFrame(double stamp, int seq, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R)
-        : time_stamp(stamp), sequence(seq), vio_T_w_i(vio_T), T_w_i(vio_T), vio_R_w_i(vio_R), R_w_i(vio_R) {}
+        : time_stamp(stamp), sequence(seq), vio_T_w_i(vio_T), T_w_i(vio_T), vio_R_w_i(vio_R), R_w_i(vio_R), origin_vio_T(vio_T), origin_vio_R(vio_R) {}
     void getVioPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = vio_T_w_i; R = vio_R_w_i; }
     void getPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = T_w_i; R = R_w_i; }
     void updatePose(const Eigen::Vector3d& P, const Eigen::Matrix3d& R) { T_w_i = P; R_w_i = R; }
@@ -32,6 +49,9 @@ struct KeyFrame {
     Eigen::Quaterniond getLoopRelativeQ() const { return Eigen::Quaterniond(loop_info[3], loop_info[4], loop_info[5], loop_info[6]); }
     double getLoopRelativeYaw() const { return loop_info[7]; }
     void updateLoop(const LoopInfo& info);
+    // keyframe.cpp:259-521 through uvs_lc_verify (one pair); true: has_loop, loop_index and loop_info are set.  The RANSAC seed is
+    // (index << 32) | old_kf->index.  Returns false also when the call fails (the status is left in last_verify.reason = -1).
+    bool findConnection(KeyFrame* old_kf, uvs_loop_verifier* lc, const Eigen::Vector3d& tic, const Eigen::Quaterniond& qic);
 };
 
 class PoseGraph {
@@ -45,6 +65,11 @@ class PoseGraph {
     // takes ownership of cur_kf; loop_index = -1: no loop, else the loop (old keyframe, loop_info) as findConnection would have accepted it
     void addKeyFrame(KeyFrame* cur_kf, int loop_index = -1, const LoopInfo* loop_info = nullptr);
     void updateKeyFrameLoop(int index, const LoopInfo& loop_info);
+    // addKeyFrame of the reference with place recognition's answer given: candidate_index = what detectLoop returned (-1: none).  The
+    // sequence shift first, then cur_kf->findConnection(candidate) on the GPU, then addKeyFrame's loop bookkeeping (:75-121) when it passes.
+    // Returns whether a loop was accepted.  Needs setExtrinsic() first.
+    bool addKeyFrameWithCandidate(KeyFrame* cur_kf, int candidate_index);
+    void setExtrinsic(const Eigen::Vector3d& tic, const Eigen::Quaterniond& qic) { tic_ = tic; qic_ = qic; }
     // one pass of the reference's optimize4DoF loop body for cur_index (first_looped_index = earliest_loop_index); returns the uvs status
     int optimize4DoF(int cur_index);
     KeyFrame* getKeyFrame(int index);
@@ -61,5 +86,9 @@ class PoseGraph {
     std::string last_error;
 
   private:
+    void addKeyFrameImpl(KeyFrame* cur_kf, int candidate_index, int loop_index, const LoopInfo* loop_info);
     uvs_pose_graph* pg_ = nullptr;
+    uvs_loop_verifier* lc_ = nullptr;
+    Eigen::Vector3d tic_;
+    Eigen::Quaterniond qic_;
 };

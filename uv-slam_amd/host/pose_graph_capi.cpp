@@ -2,6 +2,7 @@
 // Keyframes 0 .. n_before-1 are added (with their loops), optimize4DoF(cur_index) runs, then the rest are added (they take the drift);
 // out_pose[n][7] = corrected (P, q x y z w) of every keyframe, out_drift[4] = (yaw_drift, t_drift), out_yaw_t[m][4] = the solve's raw output
 // for the m keyframes first_looped_index .. cur_index (m returned through *out_m); tum_path (may be NULL) receives the corrected path.
+// uvs_host_pose_graph_verify_run (below): the same stream with loop candidates instead of loops, verified on the GPU by findConnection.
 #include <cstdio>
 #include <stdexcept>
 #include "pose_graph.h"
@@ -34,6 +35,57 @@ extern "C" int uvs_host_pose_graph_run(int device, int n, const double* stamps, 
             ++k;
         }
         if (tum_path && !graph.writeTum(tum_path)) return UVS_ERR_INVALID_ARG;
+    } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return UVS_ERR_NO_DEVICE;
+    }
+    return UVS_OK;
+}
+
+// Test hook: loop DETECTION through the mirrored PoseGraph.  Keyframe k carries its window points (n_query[k] of them: p3d[.][3] in its VIO
+// frame, desc[.][4]) and its keypoints (n_kp[k]: uv_norm[.][2], kp_desc[.][4]), concatenated over k; candidate[k] = what detectLoop would
+// return (-1: none).  Every keyframe goes through addKeyFrameWithCandidate (findConnection on the GPU); then optimize4DoF runs at the last
+// keyframe with an accepted loop.  out_accepted[n], out_loop_info[n][8] (zeros without a loop), out_pose[n][7] = corrected (P, q x y z w).
+extern "C" int uvs_host_pose_graph_verify_run(int device, int n, const double* stamps, const double* t, const double* q_xyzw, const int* sequence,
+                                              const double* tic, const double* qic_xyzw, const int* n_query, const double* p3d, const uint64_t* desc,
+                                              const int* n_kp, const double* uv_norm, const uint64_t* kp_desc, const int* candidate,
+                                              int* out_accepted, double* out_loop_info, double* out_pose) {
+    if (n < 1 || !stamps || !t || !q_xyzw || !sequence || !tic || !qic_xyzw || !n_query || !n_kp || !candidate || !out_accepted || !out_loop_info || !out_pose)
+        return UVS_ERR_INVALID_ARG;
+    try {
+        PoseGraph graph(device, n, 256);
+        graph.setExtrinsic(Eigen::Vector3d(tic[0], tic[1], tic[2]), Eigen::Quaterniond(qic_xyzw[3], qic_xyzw[0], qic_xyzw[1], qic_xyzw[2]));
+        size_t qo = 0, ko = 0;
+        int last_loop = -1;
+        for (int k = 0; k < n; ++k) {
+            const Eigen::Quaterniond Q(q_xyzw[4 * k + 3], q_xyzw[4 * k], q_xyzw[4 * k + 1], q_xyzw[4 * k + 2]);
+            KeyFrame* kf = new KeyFrame(stamps[k], sequence[k], Eigen::Vector3d(t[3 * k], t[3 * k + 1], t[3 * k + 2]), Q.toRotationMatrix());
+            for (int i = 0; i < n_query[k]; ++i, ++qo) {
+                kf->point_3d.push_back(Eigen::Vector3d(p3d[3 * qo], p3d[3 * qo + 1], p3d[3 * qo + 2]));
+                kf->point_id.push_back((double)i);
+                kf->window_brief_descriptors.push_back({desc[4 * qo], desc[4 * qo + 1], desc[4 * qo + 2], desc[4 * qo + 3]});
+            }
+            for (int i = 0; i < n_kp[k]; ++i, ++ko) {
+                kf->keypoints_norm.push_back({uv_norm[2 * ko], uv_norm[2 * ko + 1]});
+                kf->brief_descriptors.push_back({kp_desc[4 * ko], kp_desc[4 * ko + 1], kp_desc[4 * ko + 2], kp_desc[4 * ko + 3]});
+            }
+            const bool acc = graph.addKeyFrameWithCandidate(kf, candidate[k]);
+            if (kf->last_verify.reason < 0) { std::fprintf(stderr, "findConnection: uvs_lc_verify failed at keyframe %d\n", k); return UVS_ERR_INVALID_ARG; }
+            out_accepted[k] = acc;
+            for (int c = 0; c < 8; ++c) out_loop_info[8 * k + c] = acc ? kf->loop_info[c] : 0.0;
+            if (acc) last_loop = kf->index;
+        }
+        if (last_loop >= 0) {
+            const int rc = graph.optimize4DoF(last_loop);
+            if (rc != UVS_OK) { std::fprintf(stderr, "optimize4DoF: %s\n", graph.last_error.c_str()); return rc; }
+        }
+        int k = 0;
+        for (const KeyFrame* kf : graph.keyframelist) {
+            const Eigen::Quaterniond Q(kf->R_w_i);
+            const double v[7] = {kf->T_w_i.x(), kf->T_w_i.y(), kf->T_w_i.z(), Q.x(), Q.y(), Q.z(), Q.w()};
+            for (int c = 0; c < 7; ++c) out_pose[7 * k + c] = v[c];
+            ++k;
+        }
     } catch (const std::runtime_error& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return UVS_ERR_NO_DEVICE;
