@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "uvs_solve_kernel.h"
+#include "uvs_hip_buf.h"
 
 namespace uvsdev {
 
@@ -106,10 +107,9 @@ __global__ __launch_bounds__(NT) void k_evaluate(char* blob, double* ws, KOpts o
 
 // device + pinned-host staging of one evaluation, kept by the solver handle (no allocation on the per-call path once it has grown)
 struct EvalScratch {
-    double* d = nullptr; size_t cap = 0;       // device, doubles
-    double* h = nullptr; size_t hcap = 0;      // pinned host, doubles
+    DevBuf<double> d;                          // device
+    PinnedBuf<double> h;                       // pinned host
     std::vector<double> work[11];              // host work arrays of the marginalization, kept between calls (a fresh 160 KB vector per call is an mmap / page-fault / munmap round trip)
-    void release() { if (d) (void)hipFree(d); if (h) (void)hipHostFree(h); d = h = nullptr; cap = hcap = 0; }
 };
 
 // host driver: blob of window 0 must already be on the device (uvs_batch_upload)
@@ -117,33 +117,22 @@ struct EvalScratch {
 // call on this handle), and the device buffer is not cleared first -- the subset mode writes, and the caller reads, only the selected blocks.
 static int run_evaluate(int device, hipStream_t stream, char* d_blob, double* d_ws, const DevWin& h, const KOpts& ko, int robust, uvs_eval* out, std::string& err, EvalScratch& sc,
                         bool view = false) {
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return false; } return true; };
-    if (!chk(hipSetDevice(device), "hipSetDevice")) return UVS_ERR_HIP;
+    UVS_HIP(err, hipSetDevice(device));
     const size_t npo = (size_t)std::max(h.n_pt_obs, 1), nlo = (size_t)std::max(h.n_ln_obs, 1), ni = (size_t)std::max(h.n_imu, 1);
     const size_t sizes[11] = {2 * npo, 38 * npo, 2 * nlo, 20 * nlo, nlo, 10 * nlo, 15 * ni, 450 * ni, (size_t)UVS_MAX_PRIOR_DIM, 8, 2 * npo};
     size_t tot = 0; for (size_t v : sizes) tot += v;
-    if (sc.cap < tot) {
-        if (sc.d) (void)hipFree(sc.d);
-        sc.d = nullptr; sc.cap = 0;
-        if (!chk(hipMalloc((void**)&sc.d, tot * 8), "hipMalloc(eval)")) return UVS_ERR_HIP;
-        sc.cap = tot;
-    }
-    if (sc.hcap < tot) {
-        if (sc.h) (void)hipHostFree(sc.h);
-        sc.h = nullptr; sc.hcap = 0;
-        if (!chk(hipHostMalloc((void**)&sc.h, tot * 8, hipHostMallocDefault), "hipHostMalloc(eval)")) return UVS_ERR_HIP;
-        sc.hcap = tot;
-    }
+    int rc;
+    if ((rc = sc.d.ensure(tot * 8, err)) != UVS_OK || (rc = sc.h.ensure(tot * 8, err)) != UVS_OK) return rc;
     double* d = sc.d;
-    if (!view && !chk(hipMemsetAsync(d, 0, tot * 8, stream), "memset(eval)")) return UVS_ERR_HIP;
+    if (!view) UVS_HIP(err, hipMemsetAsync(d, 0, tot * 8, stream));
     EvalOut eo; double* p = d;
     eo.pt_r = p; p += sizes[0]; eo.pt_J = p; p += sizes[1]; eo.ln_r = p; p += sizes[2]; eo.ln_J = p; p += sizes[3]; eo.vp_r = p; p += sizes[4];
     eo.vp_J = p; p += sizes[5]; eo.imu_r = p; p += sizes[6]; eo.imu_J = p; p += sizes[7]; eo.prior_r = p; p += sizes[8]; eo.cost = p; p += sizes[9]; eo.pt_Jtd = p;
     hipLaunchKernelGGL(k_evaluate, dim3(1), dim3(NT), LDS_BYTES, stream, d_blob, d_ws, ko, robust, eo);
     // ONE device-to-host copy into pinned memory, then plain host copies into the caller's arrays
-    const bool ok = chk(hipGetLastError(), "k_evaluate launch") && chk(hipMemcpyAsync(sc.h, d, tot * 8, hipMemcpyDeviceToHost, stream), "memcpy D2H(eval)") &&
-                    chk(hipStreamSynchronize(stream), "k_evaluate");
-    if (!ok) return UVS_ERR_HIP;
+    UVS_HIP(err, hipGetLastError());
+    UVS_HIP(err, hipMemcpyAsync(sc.h, d, tot * 8, hipMemcpyDeviceToHost, stream));
+    UVS_HIP(err, hipStreamSynchronize(stream));
     if (view) {
         auto at = [&](const double* dsrc) { return sc.h + (dsrc - d); };
         out->pt_r = at(eo.pt_r); out->pt_J = at(eo.pt_J); out->ln_r = at(eo.ln_r); out->ln_J = at(eo.ln_J); out->vp_r = at(eo.vp_r); out->vp_J = at(eo.vp_J);

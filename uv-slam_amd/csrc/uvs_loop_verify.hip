@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_hip_buf.h"
 
 namespace uvslc {
 
@@ -560,17 +561,12 @@ struct uvs_loop_verifier {
     hipStream_t st = nullptr;
     std::string err;
     size_t in_bytes = 0, out_bytes = 0;
-    char *d_in = nullptr, *d_out = nullptr;     // packed inputs / outputs of one call
-    char *h_in = nullptr, *h_out = nullptr;     // pinned staging
+    DevBuf<char> d_in, d_out;                   // packed inputs / outputs of one call
+    PinnedBuf<char> h_in, h_out;                // pinned staging
+    ~uvs_loop_verifier() { if (st) (void)hipStreamDestroy(st); }
 };
 
 namespace {
-
-int lc_hip_fail(uvs_loop_verifier* lc, hipError_t e, const char* what) {
-    lc->err = std::string(what) + ": " + hipGetErrorString(e);
-    return UVS_ERR_HIP;
-}
-#define LC_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return lc_hip_fail(lc, e_, #call); } while (0)
 
 inline size_t align8(size_t b) { return (b + 7) & ~size_t(7); }
 
@@ -594,27 +590,20 @@ int uvs_lc_create(int device, int max_pairs, int max_query, int max_old, uvs_loo
     const size_t B = max_pairs, Q = B * max_query, O = B * max_old;
     lc->in_bytes = align8(B * sizeof(LcPair)) + 12 * 8 + Q * (3 * 8 + 4 * 8) + O * (2 * 8 + 4 * 8);
     lc->out_bytes = align8(B * sizeof(uvs_lc_result)) + align8(Q * 4) + align8(Q);
-    auto fail = [&](hipError_t e, const char* what) { lc_hip_fail(lc, e, what); uvs_lc_destroy(lc); return UVS_ERR_HIP; };
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipStreamCreateWithFlags(&lc->st, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
-    if ((e = hipMalloc((void**)&lc->d_in, lc->in_bytes)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&lc->d_out, lc->out_bytes)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipHostMalloc((void**)&lc->h_in, lc->in_bytes)) != hipSuccess) return fail(e, "hipHostMalloc");
-    if ((e = hipHostMalloc((void**)&lc->h_out, lc->out_bytes)) != hipSuccess) return fail(e, "hipHostMalloc");
+    hipError_t e; int rc = UVS_OK;
+    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(lc->err, e, "hipSetDevice");
+    else if ((e = hipStreamCreateWithFlags(&lc->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(lc->err, e, "hipStreamCreate");
+    else if ((rc = lc->d_in.ensure(lc->in_bytes, lc->err)) == UVS_OK && (rc = lc->d_out.ensure(lc->out_bytes, lc->err)) == UVS_OK &&
+             (rc = lc->h_in.ensure(lc->in_bytes, lc->err)) == UVS_OK) rc = lc->h_out.ensure(lc->out_bytes, lc->err);
+    if (rc != UVS_OK) { uvs_lc_destroy(lc); return rc; }
     *out = lc;
     return UVS_OK;
 }
 
 void uvs_lc_destroy(uvs_loop_verifier* lc) {
     if (!lc) return;
-    hipSetDevice(lc->device);
-    if (lc->st) hipStreamSynchronize(lc->st);
-    if (lc->d_in) hipFree(lc->d_in);
-    if (lc->d_out) hipFree(lc->d_out);
-    if (lc->h_in) hipHostFree(lc->h_in);
-    if (lc->h_out) hipHostFree(lc->h_out);
-    if (lc->st) hipStreamDestroy(lc->st);
+    (void)hipSetDevice(lc->device);
+    if (lc->st) (void)hipStreamSynchronize(lc->st);
     delete lc;
 }
 
@@ -643,7 +632,7 @@ int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, 
     // packed input: pairs | tic, R(qic) | p3d | query desc | old uv | old desc
     const size_t o_ex = align8(n_pairs * sizeof(LcPair)), o_p3d = o_ex + 12 * 8, o_qd = o_p3d + tq * 24, o_uv = o_qd + tq * 32, o_od = o_uv + to * 16;
     const size_t in_used = o_od + to * 32;
-    LcPair* hp = reinterpret_cast<LcPair*>(lc->h_in);
+    LcPair* hp = reinterpret_cast<LcPair*>(lc->h_in.get());
     double* hex = reinterpret_cast<double*>(lc->h_in + o_ex);
     size_t qo = 0, oo = 0;
     for (int b = 0; b < n_pairs; ++b) {
@@ -673,16 +662,16 @@ int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, 
     }
     const size_t r_bytes = align8(n_pairs * sizeof(uvs_lc_result)), o_mo = r_bytes, o_in = o_mo + align8(tq * 4), out_used = o_in + tq;
     hipStream_t st = lc->st;
-    LC_HIP(hipSetDevice(lc->device));
-    LC_HIP(hipMemcpyAsync(lc->d_in, lc->h_in, in_used, hipMemcpyHostToDevice, st));
-    k_lc_verify<<<n_pairs, kThreads, 0, st>>>(reinterpret_cast<const LcPair*>(lc->d_in), reinterpret_cast<const double*>(lc->d_in + o_ex),
+    UVS_HIP(lc->err, hipSetDevice(lc->device));
+    UVS_HIP(lc->err, hipMemcpyAsync(lc->d_in, lc->h_in, in_used, hipMemcpyHostToDevice, st));
+    k_lc_verify<<<n_pairs, kThreads, 0, st>>>(reinterpret_cast<const LcPair*>(lc->d_in.get()), reinterpret_cast<const double*>(lc->d_in + o_ex),
                                              reinterpret_cast<const double*>(lc->d_in + o_p3d), reinterpret_cast<const unsigned long long*>(lc->d_in + o_qd),
                                              reinterpret_cast<const double*>(lc->d_in + o_uv), reinterpret_cast<const unsigned long long*>(lc->d_in + o_od),
-                                             reinterpret_cast<uvs_lc_result*>(lc->d_out), reinterpret_cast<int32_t*>(lc->d_out + o_mo),
+                                             reinterpret_cast<uvs_lc_result*>(lc->d_out.get()), reinterpret_cast<int32_t*>(lc->d_out + o_mo),
                                              reinterpret_cast<uint8_t*>(lc->d_out + o_in));
-    LC_HIP(hipGetLastError());
-    LC_HIP(hipMemcpyAsync(lc->h_out, lc->d_out, out_used, hipMemcpyDeviceToHost, st));
-    LC_HIP(hipStreamSynchronize(st));
+    UVS_HIP(lc->err, hipGetLastError());
+    UVS_HIP(lc->err, hipMemcpyAsync(lc->h_out, lc->d_out, out_used, hipMemcpyDeviceToHost, st));
+    UVS_HIP(lc->err, hipStreamSynchronize(st));
     std::memcpy(results, lc->h_out, n_pairs * sizeof(uvs_lc_result));
     if (tq) {
         std::memcpy(match_old, lc->h_out + o_mo, tq * 4);

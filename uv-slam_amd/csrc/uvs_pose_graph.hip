@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_hip_buf.h"
 
 namespace uvspg {
 
@@ -703,26 +704,21 @@ struct uvs_pose_graph {
     hipStream_t st = nullptr;
     std::string err;
     // inputs
-    double *t = nullptr, *q = nullptr; int *seq = nullptr, *fidx = nullptr, *kf_of_free = nullptr, *ucol = nullptr, *wstart = nullptr;
-    uvs_pg_loop* loops = nullptr;
+    DevBuf<double> t, q; DevBuf<int> seq, fidx, kf_of_free, ucol, wstart;
+    DevBuf<uvs_pg_loop> loops;
     // state
-    double *x = nullptr, *xc = nullptr, *pr = nullptr;
-    Edge* E = nullptr;
-    double *er = nullptr, *eJ = nullptr, *ecost = nullptr, *emcc = nullptr;
-    double *band = nullptr, *L = nullptr, *g = nullptr, *hdiag = nullptr, *lmdiag = nullptr, *s = nullptr, *gproj = nullptr;
-    double *W = nullptr, *G = nullptr, *v = nullptr, *u = nullptr, *y = nullptr, *delta = nullptr, *part_step = nullptr, *part_x = nullptr;
-    double *res = nullptr, *wz = nullptr;           // refinement pass: residual, W_U^T L^-1 r
-    double* scal = nullptr; int* fail = nullptr;     // device scalars
-    double* h_scal = nullptr;                        // pinned: 8 doubles + fail flags
+    DevBuf<double> x, xc, pr;
+    DevBuf<Edge> E;
+    DevBuf<double> er, eJ, ecost, emcc;
+    DevBuf<double> band, L, g, hdiag, lmdiag, s, gproj;
+    DevBuf<double> W, G, v, u, y, delta, part_step, part_x;
+    DevBuf<double> res, wz;                     // refinement pass: residual, W_U^T L^-1 r
+    DevBuf<double> scal; DevBuf<int> fail;      // device scalars
+    PinnedBuf<double> h_scal;                   // pinned: 8 doubles + fail flags
+    ~uvs_pose_graph() { if (st) (void)hipStreamDestroy(st); }
 };
 
 namespace {
-
-int hip_fail(uvs_pose_graph* pg, hipError_t e, const char* what) {
-    pg->err = std::string(what) + ": " + hipGetErrorString(e);
-    return UVS_ERR_HIP;
-}
-#define PG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(pg, e_, #call); } while (0)
 
 inline int grid_of(int n, int b) { return (n + b - 1) / b; }
 
@@ -761,21 +757,21 @@ int pg_setup(uvs_pose_graph* pg, const uvs_pg_problem* p, const char* who, PgPla
     for (int l = 0; l < nl; ++l) if (fidx[p->loops[l].old] >= 0 || fidx[p->loops[l].cur] >= 0) ++n_edges;
     P.n = n; P.nl = nl; P.nf = nf; P.nu = nu; P.zc = zc; P.ncols = ncols; P.nwaves = nwaves; P.n_slots = 4 * n + nl; P.m = 4 * nf; P.n_edges = n_edges;
 
-    PG_HIP(hipSetDevice(pg->device));
+    UVS_HIP(pg->err, hipSetDevice(pg->device));
     hipStream_t st = pg->st;
-    PG_HIP(hipMemcpyAsync(pg->t, p->t, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->q, p->q, (size_t)n * 4 * 8, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->seq, p->sequence, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->fidx, fidx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (nf) PG_HIP(hipMemcpyAsync(pg->kf_of_free, kf_of_free.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    if (nl) PG_HIP(hipMemcpyAsync(pg->loops, p->loops, (size_t)nl * sizeof(uvs_pg_loop), hipMemcpyHostToDevice, st));
-    if (nu) PG_HIP(hipMemcpyAsync(pg->ucol, ucol.data(), (size_t)nu * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemcpyAsync(pg->wstart, wstart.data(), (size_t)nwaves * 4, hipMemcpyHostToDevice, st));
-    PG_HIP(hipMemsetAsync(pg->fail, 0, 4 * 4, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->t, p->t, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->q, p->q, (size_t)n * 4 * 8, hipMemcpyHostToDevice, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->seq, p->sequence, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->fidx, fidx.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (nf) UVS_HIP(pg->err, hipMemcpyAsync(pg->kf_of_free, kf_of_free.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st));
+    if (nl) UVS_HIP(pg->err, hipMemcpyAsync(pg->loops, p->loops, (size_t)nl * sizeof(uvs_pg_loop), hipMemcpyHostToDevice, st));
+    if (nu) UVS_HIP(pg->err, hipMemcpyAsync(pg->ucol, ucol.data(), (size_t)nu * 4, hipMemcpyHostToDevice, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->wstart, wstart.data(), (size_t)nwaves * 4, hipMemcpyHostToDevice, st));
+    UVS_HIP(pg->err, hipMemsetAsync(pg->fail, 0, 4 * 4, st));
     k_pg_prep<<<grid_of(n, 256), 256, 0, st>>>(n, pg->t, pg->q, pg->x, pg->pr);
     k_pg_meas<<<grid_of(P.n_slots, 256), 256, 0, st>>>(n, nl, pg->t, pg->q, pg->seq, pg->fidx, pg->x, pg->pr, pg->loops, pg->E);
     // the host vectors above go out of scope: the copies must have read them
-    PG_HIP(hipStreamSynchronize(st));
+    UVS_HIP(pg->err, hipStreamSynchronize(st));
     return UVS_OK;
 }
 
@@ -783,9 +779,9 @@ int pg_setup(uvs_pose_graph* pg, const uvs_pg_problem* p, const char* who, PgPla
 int pg_reduce(uvs_pose_graph* pg, RedArgs ra) {
     hipStream_t st = pg->st;
     k_pg_reduce<<<1, 1024, 0, st>>>(ra, pg->scal);
-    PG_HIP(hipMemcpyAsync(pg->h_scal, pg->scal, 4 * 8, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->h_scal, pg->scal, 4 * 8, hipMemcpyDeviceToHost, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
+    UVS_HIP(pg->err, hipStreamSynchronize(st));
     return UVS_OK;
 }
 
@@ -808,7 +804,7 @@ int pg_linearize(uvs_pose_graph* pg, const PgPlan& P, bool first) {
 int pg_solve(uvs_pose_graph* pg, const PgPlan& P, double radius) {
     hipStream_t st = pg->st;
     const int nf = P.nf, nu = P.nu, zc = P.zc, ncols = P.ncols, nwaves = P.nwaves, m = P.m;
-    PG_HIP(hipMemsetAsync(pg->fail, 0, 4, st));
+    UVS_HIP(pg->err, hipMemsetAsync(pg->fail, 0, 4, st));
     k_pg_factor<<<1, kWave, 0, st>>>(nf, pg->band, pg->lmdiag, 1.0 / radius, pg->L, pg->fail);
     k_pg_forward<<<nwaves, kWave, 0, st>>>(nf, ncols, nu, 0, 0, pg->L, pg->ucol, pg->E, pg->eJ, pg->s, pg->g, -1.0, pg->wstart, pg->W);
     if (nu) {
@@ -823,7 +819,7 @@ int pg_solve(uvs_pose_graph* pg, const PgPlan& P, double radius) {
         }
         k_pg_capsolve<<<1, 1024, 0, st>>>(ncols, zc, pg->G, nullptr, pg->v);
     } else {
-        PG_HIP(hipMemsetAsync(pg->v, 0, (size_t)ncols * 8, st));
+        UVS_HIP(pg->err, hipMemsetAsync(pg->v, 0, (size_t)ncols * 8, st));
     }
     k_pg_wv<<<grid_of(m, 4), 256, 0, st>>>(m, ncols, zc, nwaves, pg->W, pg->wstart, pg->v, pg->u);
     k_pg_back<<<1, kWave, 0, st>>>(nf, 0, pg->L, pg->u, pg->y);
@@ -851,40 +847,31 @@ int uvs_pg_create(int device, int max_keyframes, int max_loops, uvs_pose_graph**
     uvs_pose_graph* pg = new uvs_pose_graph();
     pg->device = device; pg->max_n = max_keyframes; pg->max_l = max_loops;
     pg->max_cols = ((4 * max_loops + 1 + kTile - 1) / kTile) * kTile;
-    auto fail = [&](hipError_t e, const char* what) { hip_fail(pg, e, what); uvs_pg_destroy(pg); return UVS_ERR_HIP; };
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipStreamCreateWithFlags(&pg->st, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+    hipError_t e; int rc = UVS_OK;
+    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(pg->err, e, "hipSetDevice");
+    else if ((e = hipStreamCreateWithFlags(&pg->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(pg->err, e, "hipStreamCreate");
     const size_t N = max_keyframes, Lm = std::max(1, max_loops), ES = 4 * N + Lm, C = pg->max_cols, M = 4 * N;
-    struct { void** p; size_t bytes; } al[] = {
-        {(void**)&pg->t, N * 3 * 8}, {(void**)&pg->q, N * 4 * 8}, {(void**)&pg->seq, N * 4}, {(void**)&pg->fidx, N * 4},
-        {(void**)&pg->kf_of_free, N * 4}, {(void**)&pg->ucol, Lm * 4}, {(void**)&pg->wstart, (C / kTile) * 4},
-        {(void**)&pg->loops, Lm * sizeof(uvs_pg_loop)},
-        {(void**)&pg->x, N * 4 * 8}, {(void**)&pg->xc, N * 4 * 8}, {(void**)&pg->pr, N * 2 * 8}, {(void**)&pg->E, ES * sizeof(Edge)},
-        {(void**)&pg->er, ES * 4 * 8}, {(void**)&pg->eJ, ES * 32 * 8}, {(void**)&pg->ecost, ES * 8}, {(void**)&pg->emcc, ES * 8},
-        {(void**)&pg->band, N * kRow * 8}, {(void**)&pg->L, N * kRow * 8}, {(void**)&pg->g, M * 8}, {(void**)&pg->hdiag, M * 8},
-        {(void**)&pg->lmdiag, M * 8}, {(void**)&pg->s, M * 8}, {(void**)&pg->gproj, N * 8},
-        {(void**)&pg->W, M * C * 8}, {(void**)&pg->G, C * C * 8}, {(void**)&pg->v, C * 8}, {(void**)&pg->u, M * 8}, {(void**)&pg->y, M * 8},
-        {(void**)&pg->delta, M * 8}, {(void**)&pg->part_step, N * 8}, {(void**)&pg->part_x, N * 8}, {(void**)&pg->res, M * 8}, {(void**)&pg->wz, C * 8},
-        {(void**)&pg->scal, 16 * 8}, {(void**)&pg->fail, 4 * 4},
-    };
-    for (auto& a : al)
-        if ((e = hipMalloc(a.p, a.bytes)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipHostMalloc((void**)&pg->h_scal, 32 * 8)) != hipSuccess) return fail(e, "hipHostMalloc");
+    const auto al = [&](auto& buf, size_t bytes) { if (rc == UVS_OK) rc = buf.ensure(bytes, pg->err); };
+    al(pg->t, N * 3 * 8); al(pg->q, N * 4 * 8); al(pg->seq, N * 4); al(pg->fidx, N * 4);
+    al(pg->kf_of_free, N * 4); al(pg->ucol, Lm * 4); al(pg->wstart, (C / kTile) * 4);
+    al(pg->loops, Lm * sizeof(uvs_pg_loop));
+    al(pg->x, N * 4 * 8); al(pg->xc, N * 4 * 8); al(pg->pr, N * 2 * 8); al(pg->E, ES * sizeof(Edge));
+    al(pg->er, ES * 4 * 8); al(pg->eJ, ES * 32 * 8); al(pg->ecost, ES * 8); al(pg->emcc, ES * 8);
+    al(pg->band, N * kRow * 8); al(pg->L, N * kRow * 8); al(pg->g, M * 8); al(pg->hdiag, M * 8);
+    al(pg->lmdiag, M * 8); al(pg->s, M * 8); al(pg->gproj, N * 8);
+    al(pg->W, M * C * 8); al(pg->G, C * C * 8); al(pg->v, C * 8); al(pg->u, M * 8); al(pg->y, M * 8);
+    al(pg->delta, M * 8); al(pg->part_step, N * 8); al(pg->part_x, N * 8); al(pg->res, M * 8); al(pg->wz, C * 8);
+    al(pg->scal, 16 * 8); al(pg->fail, 4 * 4);
+    al(pg->h_scal, 32 * 8);
+    if (rc != UVS_OK) { uvs_pg_destroy(pg); return rc; }
     *out = pg;
     return UVS_OK;
 }
 
 void uvs_pg_destroy(uvs_pose_graph* pg) {
     if (!pg) return;
-    hipSetDevice(pg->device);
-    if (pg->st) hipStreamSynchronize(pg->st);
-    void* ptrs[] = {pg->t, pg->q, pg->seq, pg->fidx, pg->kf_of_free, pg->ucol, pg->wstart, pg->loops, pg->x, pg->xc, pg->pr, pg->E, pg->er, pg->eJ,
-                    pg->ecost, pg->emcc, pg->band, pg->L, pg->g, pg->hdiag, pg->lmdiag, pg->s, pg->gproj, pg->W, pg->G, pg->v, pg->u, pg->y,
-                    pg->delta, pg->part_step, pg->part_x, pg->res, pg->wz, pg->scal, pg->fail};
-    for (void* p : ptrs) if (p) hipFree(p);
-    if (pg->h_scal) hipHostFree(pg->h_scal);
-    if (pg->st) hipStreamDestroy(pg->st);
+    (void)hipSetDevice(pg->device);
+    if (pg->st) (void)hipStreamSynchronize(pg->st);
     delete pg;
 }
 
@@ -962,8 +949,8 @@ int uvs_pg_optimize(uvs_pose_graph* pg, const uvs_pg_problem* p, double* out_yaw
         }
     }
     R.num_iterations = it; R.num_successful = num_successful; R.termination = term; R.final_cost = cost;
-    PG_HIP(hipMemcpyAsync(out_yaw_t, pg->x, (size_t)n * 4 * 8, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
+    UVS_HIP(pg->err, hipMemcpyAsync(out_yaw_t, pg->x, (size_t)n * 4 * 8, hipMemcpyDeviceToHost, st));
+    UVS_HIP(pg->err, hipStreamSynchronize(st));
     if (rep) *rep = R;
     return R.status;
 }
@@ -983,9 +970,9 @@ int uvs_pg_debug_step(uvs_pose_graph* pg, const uvs_pg_problem* p, double radius
     hipStream_t st = pg->st;
     if ((rc = pg_solve(pg, P, radius))) return rc;
     k_pg_step<<<grid_of(P.n, 256), 256, 0, st>>>(P.n, pg->fidx, pg->s, pg->y, pg->x, pg->delta, pg->xc, pg->part_step);
-    PG_HIP(hipMemcpyAsync(delta, pg->delta, (size_t)P.m * 8, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
+    UVS_HIP(pg->err, hipMemcpyAsync(delta, pg->delta, (size_t)P.m * 8, hipMemcpyDeviceToHost, st));
+    UVS_HIP(pg->err, hipMemcpyAsync(pg->h_scal + 8, pg->fail, 4 * 4, hipMemcpyDeviceToHost, st));
+    UVS_HIP(pg->err, hipStreamSynchronize(st));
     const int* hf = reinterpret_cast<const int*>(pg->h_scal + 8);
     scal[0] = hf[0]; scal[1] = hf[1];
     return UVS_OK;

@@ -23,9 +23,11 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_hip_buf.h"
 #include "uvs_layout.h"
 #include "uvs_factors.h"
 #include "uvs_solve_kernel.h"
@@ -101,80 +103,75 @@ struct PackPool {
 // straight to where the one host -> device copy starts; off = -1 afterwards: no room, the blob is in the vector)
 struct PackDst { std::atomic<size_t>* bump; char* base; size_t cap; long long off = -1; };
 struct PackCache;
-static void free_pack_cache(PackCache* c);
 struct MargDevScratch;
-static void free_marg_scratch(MargDevScratch* m);
 struct MargBatchBuf;
-static void free_marg_batch(MargBatchBuf* m);
 struct MargWorker;
-static void free_marg_worker(MargWorker* w);
 static bool marg_in_flight(const uvs_solver* s);
+struct DestroySolver { void operator()(uvs_solver* s) const { uvs_destroy(s); } };
+// Every buffer of a handle is an owning member; ~uvs_solver (defined below the types it owns) releases what has no owner type, uvs_destroy what must go first.
 struct uvs_solver {
     uvs_options opts;
     int device;
     int max_batch;
     int max_points = 0, max_point_obs = 0, max_lines = 0, max_line_obs = 0;      // per-window capacities promised at uvs_create
-    uvs_solver* twin = nullptr;              // second buffer set of uvs_batch_stream (created on first use, destroyed with this handle)
-    uvs_solver* twin2 = nullptr;             // ... and the third (in flight at once: a batch being packed, one being copied, one being solved)
-    uvs_solver* twin3 = nullptr;             // ... and a fourth (UVS_STREAM_SETS=4: one more batch of slack for a host whose packing threads get descheduled)
+    std::unique_ptr<uvs_solver, DestroySolver> twin;       // second buffer set of uvs_batch_stream (created on first use, destroyed with this handle)
+    std::unique_ptr<uvs_solver, DestroySolver> twin2;      // ... and the third (in flight at once: a batch being packed, one being copied, one being solved)
+    std::unique_ptr<uvs_solver, DestroySolver> twin3;      // ... and a fourth (UVS_STREAM_SETS=4: one more batch of slack for a host whose packing threads get descheduled)
     hipEvent_t ev_done = nullptr;            // recorded behind a set's k_solve in the stream: the next set's launch waits for it (the kernels of consecutive batches run one after the other)
     int n_cus = 256;                         // compute units of the device
     int large_solve_nt = 512;                // ... and for k_large_solve (UVS_LARGE_SOLVE_NT=256)
     int large_chunks_nt = 512;               // likewise for k_large_chunks (UVS_LARGE_CHUNKS_NT=256 selects the 256-thread kernel of this file)
     int ksolve_nt = 512;                     // which instantiation of the persistent kernel launch_solve uses (uvs_solve512.hip / this file's 256-thread one)
     int chunk_wgs() const { return std::max(1, n_cus - 1); }      // chunk workgroups of the persistent large-window kernels: one compute unit stays free for the frame-terms workgroup of the same launch
-    hipStream_t stream;
-    hipEvent_t ev0, ev1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
     // batch state
     int n_loaded = 0;
     std::vector<DevWin> hdrs;                // host copies of the per-window headers
     std::vector<long long> blob_off, ws_off;
     std::vector<char> host_blobs;
-    MargDevScratch* marg_dev = nullptr;   // buffers of the device marginalization (sub-window blob, its workspace, the reduced system)
-    struct MargBatchBuf* marg_batch = nullptr;      // ... and of uvs_marginalize_batch (allocated on first use)
-    struct MargWorker* marg_worker = nullptr;      // uvs_marginalize_resident_begin(): the marginalization runs on this handle's worker thread (created on first use, kept: a thread per call was
+    std::unique_ptr<MargDevScratch> marg_dev;      // buffers of the device marginalization (sub-window blob, its workspace, the reduced system)
+    std::unique_ptr<MargBatchBuf> marg_batch;      // ... and of uvs_marginalize_batch (allocated on first use)
+    std::unique_ptr<MargWorker> marg_worker;       // uvs_marginalize_resident_begin(): the marginalization runs on this handle's worker thread (created on first use, kept: a thread per call was
     uvs_prior marg_job_out;                        // 30 - 60 us of every optimization() of a replay); its result waits in marg_job_out
-    PackCache* pack_cache = nullptr;      // structure of the last large single window (allocated on first use)
+    std::unique_ptr<PackCache> pack_cache;         // structure of the last large single window (allocated on first use)
     std::vector<std::vector<char>> slot_blobs;      // batch uploads: one packing buffer per batch slot, kept (with its pages) from batch to batch
     PackPool* pool = nullptr;                       // ... and the worker threads that fill them (created on the first threaded batch)
     bool pool_borrowed = false;                     // (a buffer set of uvs_batch_stream uses its owner's pool)
     // ONE host -> device copy per upload: [blobs | blob_off[n] | ws_off[n] | out_tab[3 n]] staged in pinned memory; the three tables
     // live behind the blobs in the same device allocation (d_blob_off / d_ws_off / d_out_tab point into it)
-    char* d_blobs = nullptr; size_t d_blobs_cap = 0;
-    char* h_up = nullptr; size_t h_up_cap = 0;            // pinned upload staging
-    double* d_ws = nullptr; size_t d_ws_cap = 0;
+    DevBuf<char> d_blobs;
+    PinnedBuf<char> h_up;                    // pinned upload staging
+    DevBuf<double> d_ws;
     long long* d_blob_off = nullptr; long long* d_ws_off = nullptr;
     // ONE device -> host copy per download: per window {source offset in d_ws, doubles, destination offset} -> k_pack_outputs gathers the
     // final states AND the reports into one contiguous device buffer [states | reports[n]] -> pinned host buffer
-    std::vector<long long> out_tab; long long* d_out_tab = nullptr; double* d_outpack = nullptr; size_t d_outpack_cap = 0; long long out_total = 0;
-    char* h_out = nullptr; size_t h_out_cap = 0;          // pinned download staging
-    uvs_report* d_reports = nullptr; size_t d_rep_cap = 0;
-    double* d_dbg = nullptr;
+    std::vector<long long> out_tab; long long* d_out_tab = nullptr; DevBuf<double> d_outpack; long long out_total = 0;
+    PinnedBuf<char> h_out;                   // pinned download staging
+    DevBuf<uvs_report> d_reports;
+    DevBuf<double> d_dbg;
     EvalScratch eval_scratch;                // uvs_evaluate / uvs_marginalize staging
-    // large-window (configs[3]) run state
+    // large-window (configs[3]) run state: value-initialized at the start of every solve (large_prologue) ...
     struct Large {
         bool active = false; int n_chunks = 0, sel = 0, it = 0, invalid = 0, nsucc = 0, pending = 0, term = 0, status = 0;
         bool need_lin = true, first = true, done = false;
         double radius = 0, decr = 2, cost = 0, gmax = 0, x_norm = 0, local_x2 = 0;
-        double *d_state = nullptr, *d_partials = nullptr, *d_reduced = nullptr, *d_bsums = nullptr, *d_out = nullptr, *d_sc5 = nullptr;
-        size_t cap_partials = 0, cap_bsums = 0;
         uvs_report rep;
         double frame_x2 = 0;                                    // frame part of ||x||^2 (the landmark part is per rank: local_x2)
-        double* d_ctl = nullptr; uvs_report* d_rep = nullptr;   // fused loop: trust-region state and report on the device
-        void* comm = nullptr; int rank = 0, nranks = 1;         // RCCL communicator owned by the handle (uvs_large_comm_init)
         double relo_pose_in[7] = {0, 0, 0, 0, 0, 0, 0};      // passes through to uvs_large_finish (this path takes no relocalization blocks)
         int grid = 0;                                           // chunk workgroups of k_large_chunks / k_large_backsub = partial rows (min(n_chunks, compute units)); every launch adds ONE for the frame terms
-        double* d_fimg = nullptr;                               // frame image of the reduced system (k_large_chunks' extra workgroup -> k_large_solve)
         std::chrono::steady_clock::time_point t_begin;          // start of the host-driven loop (options.max_solver_time_in_seconds)
     } L;
+    // ... and what one solve leaves to the next: the device buffers of the loop and the communicator
+    struct LargeBufs {
+        DevBuf<double> d_state, d_partials, d_reduced, d_bsums, d_out, d_sc5;
+        DevBuf<double> d_ctl; DevBuf<uvs_report> d_rep;         // fused loop: trust-region state and report on the device
+        DevBuf<double> d_fimg;                                  // frame image of the reduced system (k_large_chunks' extra workgroup -> k_large_solve)
+        void* comm = nullptr; int rank = 0, nranks = 1;         // RCCL communicator owned by the handle (uvs_large_comm_init)
+    } LB;
+    ~uvs_solver();
 };
-
-#define HIPCHK(s, call)                                                                              \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) { (s)->err = std::string(#call) + ": " + hipGetErrorString(e_); return UVS_ERR_HIP; } \
-    } while (0)
 
 static KOpts make_kopts(const uvs_options& o, int debug) {
     KOpts k;
@@ -256,52 +253,22 @@ int uvs_create(const uvs_options* opts, int device, int max_batch, int max_point
     uvs_solver* s = new uvs_solver();
     s->opts = *opts; s->device = device; s->max_batch = max_batch;
     s->max_points = max_points; s->max_point_obs = max_point_obs; s->max_lines = max_lines; s->max_line_obs = max_line_obs;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) { delete s; return UVS_ERR_HIP; }
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) { uvs_destroy(s); return UVS_ERR_HIP; }
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) s->n_cus = cus; }
     // block table for the output-stationary gather
     unsigned char fa[UVS_NBLK], fb[UVS_NBLK];
     for (int i = 0, b = 0; i < UVS_NF; ++i) for (int j = 0; j <= i; ++j, ++b) { fa[b] = (unsigned char)i; fb[b] = (unsigned char)j; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, sizeof(fa)) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, sizeof(fb)) != hipSuccess) { delete s; return UVS_ERR_HIP; }
-    if (uvs_k_solve512_arg_bytes(0) != sizeof(KOpts) || uvs_k_solve512_arg_bytes(1) != sizeof(DebugOut) || uvs_k_solve512_init(fa, fb, UVS_NBLK) != UVS_OK) { delete s; return UVS_ERR_HIP; }
+    if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, sizeof(fa)) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, sizeof(fb)) != hipSuccess) { uvs_destroy(s); return UVS_ERR_HIP; }
+    if (uvs_k_solve512_arg_bytes(0) != sizeof(KOpts) || uvs_k_solve512_arg_bytes(1) != sizeof(DebugOut) || uvs_k_solve512_init(fa, fb, UVS_NBLK) != UVS_OK) { uvs_destroy(s); return UVS_ERR_HIP; }
     { const char* e = std::getenv("UVS_KSOLVE_NT"); s->ksolve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
     { const char* e = std::getenv("UVS_LARGE_CHUNKS_NT"); s->large_chunks_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
     { const char* e = std::getenv("UVS_LARGE_SOLVE_NT"); s->large_solve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }      // A/B switch: 256 = the one-wave-per-SIMD instantiation of the persistent kernel
     // the LDS opt-in is a per-device function attribute: every handle sets it for its own device (the current one since hipSetDevice above)
     for (const void* fn : {(const void*)k_solve, (const void*)k_evaluate, (const void*)k_large_chunks, (const void*)k_large_solve, (const void*)k_large_backsub, (const void*)k_marg_linearize, (const void*)k_marg_linearize_batch})
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) { delete s; return UVS_ERR_HIP; }
-    if (hipFuncSetAttribute((const void*)uvsmarg::k_marg_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)uvsmarg::MF_LDS_BYTES) != hipSuccess) { delete s; return UVS_ERR_HIP; }
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) { uvs_destroy(s); return UVS_ERR_HIP; }
+    if (hipFuncSetAttribute((const void*)uvsmarg::k_marg_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)uvsmarg::MF_LDS_BYTES) != hipSuccess) { uvs_destroy(s); return UVS_ERR_HIP; }
     *out = s;
     return UVS_OK;
-}
-
-void uvs_destroy(uvs_solver* s) {
-    if (s) { free_marg_worker(s->marg_worker); s->marg_worker = nullptr; }      // (waits for a marginalization begun and never waited for: it still uses the handle)
-    if (!s) return;
-    if (s->twin) { uvs_destroy(s->twin); s->twin = nullptr; }
-    if (s->twin2) { uvs_destroy(s->twin2); s->twin2 = nullptr; }
-    if (s->twin3) { uvs_destroy(s->twin3); s->twin3 = nullptr; }
-    if (s->ev_done) { (void)hipEventDestroy(s->ev_done); s->ev_done = nullptr; }
-    free_pack_cache(s->pack_cache); s->pack_cache = nullptr;
-    if (!s->pool_borrowed) delete s->pool;
-    s->pool = nullptr;
-    free_marg_scratch(s->marg_dev); s->marg_dev = nullptr;
-    free_marg_batch(s->marg_batch); s->marg_batch = nullptr;
-    (void)hipSetDevice(s->device);      // teardown: nothing useful to do with an error
-    if (s->d_blobs) (void)hipFree(s->d_blobs);
-    if (s->d_ws) (void)hipFree(s->d_ws);
-    if (s->h_up) (void)hipHostFree(s->h_up);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    uvs_large_comm_destroy(s);
-    if (s->L.d_ctl) (void)hipFree(s->L.d_ctl);
-    if (s->L.d_fimg) (void)hipFree(s->L.d_fimg);
-    if (s->L.d_rep) (void)hipFree(s->L.d_rep);
-    if (s->d_outpack) (void)hipFree(s->d_outpack);
-    if (s->d_reports) (void)hipFree(s->d_reports);
-    if (s->d_dbg) (void)hipFree(s->d_dbg);
-    s->eval_scratch.release();
-    (void)hipEventDestroy(s->ev0); (void)hipEventDestroy(s->ev1);
-    (void)hipStreamDestroy(s->stream);
-    delete s;
 }
 
 }  // extern "C"
@@ -420,7 +387,6 @@ struct PackCache {
         hdr = h;
     }
 };
-static void free_pack_cache(PackCache* c) { delete c; }
 static constexpr int kPackCacheMinObs = 20000;      // windows at least this large use the structure cache (and the inner packing threads)
 
 // the VALUE sections of a blob (everything that is not index bookkeeping): header, frame states, landmark parameters, measurements, IMU blocks, prior
@@ -994,25 +960,6 @@ static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vec
     return UVS_OK;
 }
 
-static int ensure(uvs_solver* s, void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return UVS_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(s, hipMalloc(p, need));
-    *cap = need;
-    return UVS_OK;
-}
-
-static int ensure_pinned(uvs_solver* s, char** p, size_t* cap, size_t need) {      // grow-only (pinning costs milliseconds: never per call)
-    if (*cap >= need) return UVS_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = need + need / 2 + 4096;
-    HIPCHK(s, hipHostMalloc((void**)p, want, hipHostMallocDefault));
-    *cap = want;
-    return UVS_OK;
-}
-
 // gathers the per-window outputs into one contiguous buffer: tab[3 b] = {source offset in ws, doubles, destination offset}; the reports
 // follow the states (rep_dst = offset of the report array in `out`, in doubles; sizeof(uvs_report) is a multiple of 8)
 static_assert(sizeof(uvs_report) % 8 == 0, "uvs_report is copied as doubles");
@@ -1028,7 +975,7 @@ __global__ void k_pack_outputs(const double* ws, const long long* tab, double* o
 static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, bool wait, int chunk_grid = 0, bool out_direct = false) {
     if (!s || n < 1 || !ws) return UVS_ERR_INVALID_ARG;
     if (n > s->max_batch) { s->err = "batch larger than max_batch"; return UVS_ERR_CAPACITY; }
-    HIPCHK(s, hipSetDevice(s->device));
+    UVS_HIP(s->err, hipSetDevice(s->device));
     s->hdrs.resize(n); s->blob_off.resize(n); s->ws_off.resize(n);
     long long wtot = 0;
     for (int b = 0; b < n; ++b)
@@ -1051,10 +998,10 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
     }
     bool values_only = false;      // structure-cache hit AND the device still holds this window's tables: only the value sections travel
     if (n == 1 && ws[0] && ws[0]->n_point_obs + ws[0]->n_line_obs >= kPackCacheMinObs && !std::getenv("UVS_NO_PACK_CACHE")) {
-        if (!s->pack_cache) s->pack_cache = new PackCache();
+        if (!s->pack_cache) s->pack_cache = std::make_unique<PackCache>();
         const bool was_valid = s->pack_cache->valid, dev = s->pack_cache->device_holds_tables;
         s->blob_off[0] = 0;
-        int rc = pack_window(ws[0], s->opts, s->host_blobs, s->hdrs[0], s->err, chunk_grid, s->pack_cache);
+        int rc = pack_window(ws[0], s->opts, s->host_blobs, s->hdrs[0], s->err, chunk_grid, s->pack_cache.get());
         if (rc != UVS_OK) { s->n_loaded = 0; return rc; }
         values_only = !out_direct && was_valid && dev && s->pack_cache->valid && s->pack_cache->device_holds_tables;      // (a miss resets both flags; the stream patches every staged header -- DevWin::out_host -- so the whole blob travels)
     } else if (nthreads == 1) {
@@ -1074,12 +1021,12 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
         // The windows go STRAIGHT into the pinned staging buffer when it is large enough (it is from the second batch of a size on: the first one takes the vectors and
         // sizes the buffer): every worker claims room with an atomic bump, so the blobs sit in completion order -- the kernel finds them through blob_off.  The buffer
         // may still feed the previous upload's copy: drain first.
-        HIPCHK(s, hipStreamSynchronize(s->stream));
+        UVS_HIP(s->err, hipStreamSynchronize(s->stream));
         std::atomic<size_t> bump{0};
-        const size_t direct_cap = s->h_up_cap > (size_t)n * 40 + 64 ? s->h_up_cap - (size_t)n * 40 - 64 : 0;
+        const size_t direct_cap = s->h_up.cap() > (size_t)n * 40 + 64 ? s->h_up.cap() - (size_t)n * 40 - 64 : 0;
         const auto job = [&](int t) {
             for (int b = t; b < n; b += nthreads) {
-                PackDst d{&bump, direct_cap ? s->h_up : nullptr, direct_cap, -1};
+                PackDst d{&bump, direct_cap ? s->h_up.get() : nullptr, direct_cap, -1};
                 s->slot_blobs[b].clear();
                 rcs[b] = pack_window(ws[b], s->opts, s->slot_blobs[b], s->hdrs[b], errs[b], chunk_grid, nullptr, &d);
                 placed[b] = d.off;
@@ -1115,18 +1062,18 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
     const size_t raw_bytes = packed_total ? packed_total : s->host_blobs.size();
     const size_t blob_bytes = (raw_bytes + 7) & ~(size_t)7, up_bytes = blob_bytes + (size_t)n * 40;
     // the staging buffer may still feed the previous upload's copy (the single-window path does not wait for it): drain before reuse
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     tp2_ = std::chrono::steady_clock::now();
     // every upload is staged in pinned memory together with its tables: ONE DMA copy that the host need not wait for (a copy from the pageable vector
     // is staged by the runtime anyway, synchronously and on one thread); a large blob (configs[3]: 13 MB) is moved there by several threads
     const bool staged = true;
-    if ((rc = ensure_pinned(s, &s->h_up, &s->h_up_cap, staged ? up_bytes + (packed_total && !packed_direct ? up_bytes / 8 + 4096 : 0) : (size_t)n * 40)) != UVS_OK) return rc;      // (slack: the next batch of this size packs in place)
-    { char* before = s->d_blobs; if ((rc = ensure(s, (void**)&s->d_blobs, &s->d_blobs_cap, up_bytes)) != UVS_OK) return rc; if (s->d_blobs != before) values_only = false; }
+    if ((rc = s->h_up.ensure(staged ? up_bytes + (packed_total && !packed_direct ? up_bytes / 8 + 4096 : 0) : (size_t)n * 40, s->err, grow_pinned)) != UVS_OK) return rc;      // (slack: the next batch of this size packs in place)
+    { char* before = s->d_blobs; if ((rc = s->d_blobs.ensure(up_bytes, s->err)) != UVS_OK) return rc; if (s->d_blobs != before) values_only = false; }
     // all doubles of a blob precede its int tables (pack_window: i = 2 d), so the value sections are ONE prefix
     const size_t value_bytes = values_only ? (size_t)4 * (size_t)s->hdrs[0].i_pt_lm : 0;
-    if ((rc = ensure(s, (void**)&s->d_outpack, &s->d_outpack_cap, (size_t)s->out_total * 8 + (size_t)n * sizeof(uvs_report))) != UVS_OK) return rc;
-    if ((rc = ensure(s, (void**)&s->d_ws, &s->d_ws_cap, (size_t)wtot * 8)) != UVS_OK) return rc;
-    if ((rc = ensure(s, (void**)&s->d_reports, &s->d_rep_cap, (size_t)n * sizeof(uvs_report))) != UVS_OK) return rc;
+    if ((rc = s->d_outpack.ensure((size_t)s->out_total * 8 + (size_t)n * sizeof(uvs_report), s->err)) != UVS_OK) return rc;
+    if ((rc = s->d_ws.ensure((size_t)wtot * 8, s->err)) != UVS_OK) return rc;
+    if ((rc = s->d_reports.ensure((size_t)n * sizeof(uvs_report), s->err)) != UVS_OK) return rc;
     if (packed_direct) { /* the blobs are in the staging buffer already */ }
     else if (packed_total) {      // every packing thread moves its own windows (67 MB for 256 canonical windows: one core would need ~10 ms)
         const auto cp = [&](int t) { for (int b = t; b < n; b += nthreads) std::memcpy(s->h_up + s->blob_off[b], s->slot_blobs[b].data(), s->slot_blobs[b].size()); };
@@ -1137,8 +1084,8 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
     } else std::memcpy(s->h_up, s->host_blobs.data(), s->host_blobs.size());
     tp3_ = std::chrono::steady_clock::now();
     if (out_direct) {
-        if ((rc = ensure_pinned(s, &s->h_out, &s->h_out_cap, (size_t)s->out_total * 8 + (size_t)n * sizeof(uvs_report))) != UVS_OK) return rc;
-        void* dp = nullptr; HIPCHK(s, hipHostGetDevicePointer(&dp, s->h_out, 0));
+        if ((rc = s->h_out.ensure((size_t)s->out_total * 8 + (size_t)n * sizeof(uvs_report), s->err, grow_pinned)) != UVS_OK) return rc;
+        void* dp = nullptr; UVS_HIP(s->err, hipHostGetDevicePointer(&dp, s->h_out, 0));
         for (int b = 0; b < n; ++b) ((DevWin*)(s->h_up + s->blob_off[b]))->out_host = (int64_t)(uintptr_t)((double*)dp + s->out_tab[3 * (size_t)b + 2]);
     }
     long long* tabs = (long long*)(s->h_up + (staged ? blob_bytes : 0));
@@ -1147,12 +1094,12 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
     std::memcpy(tabs + 2 * (size_t)n, s->out_tab.data(), (size_t)n * 24);
     s->d_blob_off = (long long*)(s->d_blobs + blob_bytes); s->d_ws_off = s->d_blob_off + n; s->d_out_tab = s->d_blob_off + 2 * (size_t)n;
     if (values_only) {      // the tables of this window are on the device already (structure cache): the value prefix and the three small offset tables
-        HIPCHK(s, hipMemcpyAsync(s->d_blobs, s->h_up, value_bytes, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(s, hipMemcpyAsync(s->d_blobs + blob_bytes, s->h_up + blob_bytes, (size_t)n * 40, hipMemcpyHostToDevice, s->stream));
-    } else if (staged) HIPCHK(s, hipMemcpyAsync(s->d_blobs, s->h_up, up_bytes, hipMemcpyHostToDevice, s->stream));
+        UVS_HIP(s->err, hipMemcpyAsync(s->d_blobs, s->h_up, value_bytes, hipMemcpyHostToDevice, s->stream));
+        UVS_HIP(s->err, hipMemcpyAsync(s->d_blobs + blob_bytes, s->h_up + blob_bytes, (size_t)n * 40, hipMemcpyHostToDevice, s->stream));
+    } else if (staged) UVS_HIP(s->err, hipMemcpyAsync(s->d_blobs, s->h_up, up_bytes, hipMemcpyHostToDevice, s->stream));
     else {
-        HIPCHK(s, hipMemcpyAsync(s->d_blobs, s->host_blobs.data(), s->host_blobs.size(), hipMemcpyHostToDevice, s->stream));
-        HIPCHK(s, hipMemcpyAsync(s->d_blobs + blob_bytes, s->h_up, (size_t)n * 40, hipMemcpyHostToDevice, s->stream));
+        UVS_HIP(s->err, hipMemcpyAsync(s->d_blobs, s->host_blobs.data(), s->host_blobs.size(), hipMemcpyHostToDevice, s->stream));
+        UVS_HIP(s->err, hipMemcpyAsync(s->d_blobs + blob_bytes, s->h_up, (size_t)n * 40, hipMemcpyHostToDevice, s->stream));
         wait = true;      // host_blobs is reused by the next upload
     }
     if (sprof_ && n > 1) {
@@ -1160,7 +1107,7 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
         auto ms_ = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "upload n=%d threads=%d bytes=%zu: pack %.3f ms, tables + drain of the stream %.3f, copy to pinned %.3f, enqueue %.3f\n", n, nthreads, up_bytes, ms_(tp0_, tp1_), ms_(tp1_, tp2_), ms_(tp2_, tp3_), ms_(tp3_, tp4_));
     }
-    if (wait) HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (wait) UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     if (s->pack_cache && s->pack_cache->valid && n == 1) s->pack_cache->device_holds_tables = true;
     s->n_loaded = n;
     return UVS_OK;
@@ -1176,15 +1123,8 @@ struct MargDevScratch {
     std::vector<int32_t> pt_lm, pt_fi, pt_fj, ln_lm, ln_fj, ln_vpf; std::vector<double> pt_pi, pt_pj, pt_vi, pt_vj, pt_tdi, pt_tdj, invd, ln_sp, ln_ep, ln_vp, lorth;
     std::vector<uvs_imu_block> imu; std::vector<int> pmap, lmap, lstart;
     std::vector<char> blob;
-    char* d_blob = nullptr; size_t d_blob_cap = 0; double* d_ws = nullptr; size_t d_ws_cap = 0; double* d_out = nullptr; char* h_out = nullptr; size_t h_out_cap = 0;
-    char* h_up = nullptr; size_t h_up_cap = 0;
+    DevBuf<char> d_blob; DevBuf<double> d_ws, d_out; PinnedBuf<char> h_out, h_up;
 };
-static void free_marg_scratch(MargDevScratch* m) {
-    if (!m) return;
-    if (m->d_blob) (void)hipFree(m->d_blob); if (m->d_ws) (void)hipFree(m->d_ws); if (m->d_out) (void)hipFree(m->d_out);
-    if (m->h_out) (void)hipHostFree(m->h_out); if (m->h_up) (void)hipHostFree(m->h_up);
-    delete m;
-}
 // The sub-window of the factors MARGIN_OLD reads (estimator.cpp:1002-1135): the prior, the IMU link of frame 0, the observations of the points anchored in frame 0 and of the lines
 // that start there (without their anchor observation).  Its arrays live in M; used[] = the frame blocks (ids: pose f -> f ; speedbias f -> 11 + f ; ex -> 22 ; td -> 23) it touches.
 static int marg_build_sub(uvs_solver* s, const uvs_window* w, MargDevScratch& M, bool used[24], uvs_window& sub, std::string& err_) {
@@ -1257,7 +1197,7 @@ static int marginalize_old_device(uvs_solver* s, const uvs_window* w, uvs_prior*
     if (std::getenv("UVS_MARG_HOST")) return kMargFallback;      // (relocalization blocks are not marginalized, estimator.cpp:1002-1228: the sub-window simply leaves them out)
     const bool prof = std::getenv("UVS_MARG_PROFILE") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!s->marg_dev) s->marg_dev = new MargDevScratch();
+    if (!s->marg_dev) s->marg_dev = std::make_unique<MargDevScratch>();
     MargDevScratch& M = *s->marg_dev;
     bool used[24]; uvs_window sub;
     { const int rb = marg_build_sub(s, w, M, used, sub, s->err); if (rb != UVS_OK) return rb; }
@@ -1269,29 +1209,26 @@ static int marginalize_old_device(uvs_solver* s, const uvs_window* w, uvs_prior*
     const auto tp1 = std::chrono::steady_clock::now();
     if (rc == UVS_ERR_UNSUPPORTED || rc == UVS_ERR_CAPACITY) return kMargFallback;
     if (rc != UVS_OK) return rc;
-    HIPCHK(s, hipSetDevice(s->device));
-    const auto ens = [&](void** p, size_t* cap, size_t need) -> int { if (*cap >= need) return UVS_OK; if (*p) (void)hipFree(*p); *p = nullptr; *cap = 0; HIPCHK(s, hipMalloc(p, need + need / 2)); *cap = need + need / 2; return UVS_OK; };
-    if ((rc = ens((void**)&M.d_blob, &M.d_blob_cap, M.blob.size())) != UVS_OK) return rc;
-    if ((rc = ens((void**)&M.d_ws, &M.d_ws_cap, (size_t)h.ws_doubles * 8)) != UVS_OK) return rc;
-    if (!M.d_out) HIPCHK(s, hipMalloc((void**)&M.d_out, MARG_OUT * 8));
-    if (!M.h_out) { HIPCHK(s, hipHostMalloc((void**)&M.h_out, MARG_OUT * 8, hipHostMallocDefault)); M.h_out_cap = MARG_OUT * 8; }
-    if ((rc = ensure_pinned(s, &M.h_up, &M.h_up_cap, M.blob.size())) != UVS_OK) return rc;
-    HIPCHK(s, hipStreamSynchronize(s->stream));      // the staging buffer may still feed the previous call's copy
+    UVS_HIP(s->err, hipSetDevice(s->device));
+    if ((rc = M.d_blob.ensure(M.blob.size(), s->err, grow_half)) != UVS_OK || (rc = M.d_ws.ensure((size_t)h.ws_doubles * 8, s->err, grow_half)) != UVS_OK ||
+        (rc = M.d_out.ensure(MARG_OUT * 8, s->err)) != UVS_OK || (rc = M.h_out.ensure(MARG_OUT * 8, s->err)) != UVS_OK ||
+        (rc = M.h_up.ensure(M.blob.size(), s->err, grow_pinned)) != UVS_OK) return rc;
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));      // the staging buffer may still feed the previous call's copy
     const auto tq0 = std::chrono::steady_clock::now();
     std::memcpy(M.h_up, M.blob.data(), M.blob.size());
     const auto tq1 = std::chrono::steady_clock::now();
-    HIPCHK(s, hipMemcpyAsync(M.d_blob, M.h_up, M.blob.size(), hipMemcpyHostToDevice, s->stream));
+    UVS_HIP(s->err, hipMemcpyAsync(M.d_blob, M.h_up, M.blob.size(), hipMemcpyHostToDevice, s->stream));
     const KOpts ko = make_kopts(o, 0);
     hipLaunchKernelGGL(k_marg_linearize, dim3(1), dim3(NT), LDS_BYTES, s->stream, M.d_blob, M.d_ws, ko, M.d_out);
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipMemcpyAsync(M.h_out, M.d_out, MARG_OUT * 8, hipMemcpyDeviceToHost, s->stream));
+    UVS_HIP(s->err, hipGetLastError());
+    UVS_HIP(s->err, hipMemcpyAsync(M.h_out, M.d_out, MARG_OUT * 8, hipMemcpyDeviceToHost, s->stream));
     const auto tq2 = std::chrono::steady_clock::now();
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     const auto t1 = std::chrono::steady_clock::now();
     if (prof) { auto us = [](auto a_, auto b_) { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(b_ - a_).count() * 1e-3; };
                 std::fprintf(stderr, "[uvs_marginalize] device path: sub-window %.0f us, pack %.0f us (%zu bytes), upload + kernel + download %.0f us (allocations + drain %.0f, copy into pinned %.0f, three enqueues %.0f, wait %.0f)\n",
                              us(t0, tp0), us(tp0, tp1), M.blob.size(), us(tp1, t1), us(tp1, tq0), us(tq0, tq1), us(tq1, tq2), us(tq2, t1)); }
-    const double* S = (const double*)M.h_out; const double* g = S + UVS_RD * (UVS_RD + 1) / 2; const double* scal = g + UVS_RD;
+    const double* S = (const double*)M.h_out.get(); const double* g = S + UVS_RD * (UVS_RD + 1) / 2; const double* scal = g + UVS_RD;
     if (scal[1] != 0.0 || !std::isfinite(scal[0])) return kMargFallback;      // a landmark block the reference's eps cut would touch: the host path applies that cut
     // ---- ordering: the dropped frame blocks (Pose[0], SpeedBias[0]) first, then the kept ones in id order
     std::vector<int> pos, keep_ids, map; int md = 0, n = 0;
@@ -1319,26 +1256,26 @@ int uvs_batch_upload(uvs_solver* s, int n, const uvs_window* const* ws) { return
 // rep_direct: (uvs_batch_stream after upload_windows(out_direct)) the reports go into the pinned result buffer as well
 static int launch_solve(uvs_solver* s, int debug, float* elapsed_ms, bool wait = true, bool rep_direct = false) {
     if (s->n_loaded < 1) { s->err = "no batch uploaded"; return UVS_ERR_INVALID_ARG; }
-    HIPCHK(s, hipSetDevice(s->device));
+    UVS_HIP(s->err, hipSetDevice(s->device));
     KOpts ko = make_kopts(s->opts, debug);
     uvs_report* d_reports = s->d_reports;
     if (rep_direct) {
-        void* dp = nullptr; HIPCHK(s, hipHostGetDevicePointer(&dp, s->h_out, 0));
+        void* dp = nullptr; UVS_HIP(s->err, hipHostGetDevicePointer(&dp, s->h_out, 0));
         d_reports = (uvs_report*)((double*)dp + s->out_total);
     }
     DebugOut dbg; std::memset(&dbg, 0, sizeof(dbg));
     if (debug) {
-        if (!s->d_dbg) HIPCHK(s, hipMalloc((void**)&s->d_dbg, sizeof(double) * (UVS_RD * UVS_RD + 5 * UVS_RD + 40)));
+        if (const int rc = s->d_dbg.ensure(sizeof(double) * (UVS_RD * UVS_RD + 5 * UVS_RD + 40), s->err)) return rc;
         dbg.S = s->d_dbg; dbg.g = dbg.S + UVS_RD * UVS_RD; dbg.hd = dbg.g + UVS_RD; dbg.dd = dbg.hd + UVS_RD; dbg.step = dbg.dd + UVS_RD; dbg.scal = dbg.step + UVS_RD;
     }
-    HIPCHK(s, hipEventRecord(s->ev0, s->stream));
+    UVS_HIP(s->err, hipEventRecord(s->ev0, s->stream));
     if (s->ksolve_nt == 512) { if (uvs_k_solve512_launch(s->n_loaded, s->stream, s->d_blobs, s->d_blob_off, s->d_ws, s->d_ws_off, &ko, sizeof(ko), d_reports, &dbg, sizeof(dbg)) != UVS_OK) { s->err = "k_solve (512 threads): argument layout mismatch between the translation units"; return UVS_ERR_HIP; } }
     else hipLaunchKernelGGL(k_solve, dim3(s->n_loaded), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_blob_off, s->d_ws, s->d_ws_off, ko, d_reports, dbg);
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipEventRecord(s->ev1, s->stream));
+    UVS_HIP(s->err, hipGetLastError());
+    UVS_HIP(s->err, hipEventRecord(s->ev1, s->stream));
     if (!wait) return UVS_OK;
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    if (elapsed_ms) HIPCHK(s, hipEventElapsedTime(elapsed_ms, s->ev0, s->ev1));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
+    if (elapsed_ms) UVS_HIP(s->err, hipEventElapsedTime(elapsed_ms, s->ev0, s->ev1));
     return UVS_OK;
 }
 
@@ -1355,16 +1292,16 @@ static int download_enqueue(uvs_solver* s, int n, bool direct = false) {
     const size_t nst = (size_t)(s->out_tab[3 * (size_t)(n - 1) + 2] + s->out_tab[3 * (size_t)(n - 1) + 1]);      // doubles of the first n states
     const size_t tot = nst * 8 + (size_t)n * sizeof(uvs_report);
     int rc;
-    if ((rc = ensure_pinned(s, &s->h_out, &s->h_out_cap, tot)) != UVS_OK) return rc;
+    if ((rc = s->h_out.ensure(tot, s->err, grow_pinned)) != UVS_OK) return rc;
     double* out = s->d_outpack;
-    if (direct) { void* dp = nullptr; HIPCHK(s, hipHostGetDevicePointer(&dp, s->h_out, 0)); out = (double*)dp; }
+    if (direct) { void* dp = nullptr; UVS_HIP(s->err, hipHostGetDevicePointer(&dp, s->h_out, 0)); out = (double*)dp; }
     hipLaunchKernelGGL(k_pack_outputs, dim3(n), dim3(256), 0, s->stream, s->d_ws, s->d_out_tab, out, s->d_reports, (long long)nst);
-    HIPCHK(s, hipGetLastError());
-    if (!direct) HIPCHK(s, hipMemcpyAsync(s->h_out, s->d_outpack, tot, hipMemcpyDeviceToHost, s->stream));
+    UVS_HIP(s->err, hipGetLastError());
+    if (!direct) UVS_HIP(s->err, hipMemcpyAsync(s->h_out, s->d_outpack, tot, hipMemcpyDeviceToHost, s->stream));
     return UVS_OK;
 }
 static int download_finish(uvs_solver* s, int n, uvs_state* states, uvs_report* reps) {
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     const size_t nst = (size_t)(s->out_tab[3 * (size_t)(n - 1) + 2] + s->out_tab[3 * (size_t)(n - 1) + 1]);
     int worst = UVS_OK;
     const uvs_report* hr = (const uvs_report*)(s->h_out + nst * 8);
@@ -1372,7 +1309,7 @@ static int download_finish(uvs_solver* s, int n, uvs_state* states, uvs_report* 
     if (reps) std::memcpy(reps, hr, sizeof(uvs_report) * (size_t)n);
     for (int b = 0; states && b < n; ++b) {
         const DevWin& h = s->hdrs[b];
-        const double* buf = (const double*)s->h_out + s->out_tab[3 * (size_t)b + 2];
+        const double* buf = (const double*)s->h_out.get() + s->out_tab[3 * (size_t)b + 2];
         uvs_state& st = states[b];
         std::memcpy(st.pose, buf, sizeof(double) * 77);
         std::memcpy(st.speedbias, buf + 77, sizeof(double) * 99);
@@ -1387,7 +1324,7 @@ static int download_finish(uvs_solver* s, int n, uvs_state* states, uvs_report* 
 
 int uvs_batch_download(uvs_solver* s, int n, uvs_state* states, uvs_report* reps) {
     if (!s || n < 1 || n > s->n_loaded) return UVS_ERR_INVALID_ARG;
-    HIPCHK(s, hipSetDevice(s->device));
+    UVS_HIP(s->err, hipSetDevice(s->device));
     const int rc = download_enqueue(s, n);      // (written by the gather kernel instead -- as the stream does -- the call takes as long: 1.370 ms either way for one window, 0.17 ms for 256 states)
     if (rc != UVS_OK) return rc;
     return download_finish(s, n, states, reps);
@@ -1417,20 +1354,24 @@ int uvs_batch_stream(uvs_solver* s, int n_batches, int per_batch, const uvs_wind
     // in four alternating A/Bs on busy and quiet hosts (profiles/r06_stream_ab_four_sets.txt): medians 172.5 / 173.6 / 150.8 k against 173.5 / 175.8 / 174.8 k, tighter quartiles in one of
     // them, wider in another -- the host's noise decides, not the set count; the default stays three.
     const int NS = [] { const char* e = std::getenv("UVS_STREAM_SETS"); const int v = e ? std::atoi(e) : 3; return v == 2 || v == 4 ? v : 3; }();
-    for (uvs_solver** t : {&s->twin, &s->twin2, &s->twin3}) {
+    for (auto* t : {&s->twin, &s->twin2, &s->twin3}) {
         if ((t == &s->twin2 && NS < 3) || (t == &s->twin3 && NS < 4)) break;
-        if (!*t) { const int rc = uvs_create(&s->opts, s->device, s->max_batch, s->max_points, s->max_point_obs, s->max_lines, s->max_line_obs, t); if (rc != UVS_OK) { s->err = "uvs_batch_stream: could not create a buffer set"; return rc; } }
+        if (!*t) {
+            uvs_solver* ts = nullptr; const int rc = uvs_create(&s->opts, s->device, s->max_batch, s->max_points, s->max_point_obs, s->max_lines, s->max_line_obs, &ts);
+            if (rc != UVS_OK) { s->err = "uvs_batch_stream: could not create a buffer set"; return rc; }
+            t->reset(ts);
+        }
         if (!s->pool) s->pool = new PackPool();
         if (!(*t)->pool) { (*t)->pool = s->pool; (*t)->pool_borrowed = true; }      // one pool of packing threads for all sets (they pack one after the other)
     }
     const auto t0 = std::chrono::steady_clock::now();
-    uvs_solver* set[4] = {s, s->twin, s->twin2, s->twin3};
+    uvs_solver* set[4] = {s, s->twin.get(), s->twin2.get(), s->twin3.get()};
     // UVS_STREAM_CHAIN=1: the kernels of consecutive batches chained by events (round 5's default).  Round 6 measured both forms alternately in one process, ten runs of 32 batches each
     // (tools/stream_ab.py, profiles/r06_stream_ab.txt): un-chained 175.4 k solves/s median (quartiles 171.3 - 175.9 k), chained 167.5 k (167.3 - 167.8 k) -- the chain is steadier and
     // 4.5 % slower (a batch's kernel then never starts under the tail of the previous one, whose last workgroups leave compute units idle), so the default is un-chained.
     const bool chain_ = [] { const char* e = std::getenv("UVS_STREAM_CHAIN"); return e && e[0] == '1'; }();
     const int d2h_ = [] { const char* e = std::getenv("UVS_STREAM_D2H_COPY"); return e ? std::atoi(e) : 0; }();      // 0: k_solve writes the results into the pinned buffer; 1: gather kernel + device-to-host copy; 2: the gather kernel writes them
-    for (int j = 0; j < NS; ++j) if (!set[j]->ev_done) HIPCHK(s, hipEventCreateWithFlags(&set[j]->ev_done, hipEventDisableTiming));
+    for (int j = 0; j < NS; ++j) if (!set[j]->ev_done) UVS_HIP(s->err, hipEventCreateWithFlags(&set[j]->ev_done, hipEventDisableTiming));
     int pending[4] = {-1, -1, -1, -1};      // batch index in flight on each set
     // the resident blobs of this call carry addresses into its pinned result buffers (DevWin::out_host): whatever way the call ends, a later uvs_batch_solve needs its own upload
     struct Invalidate { uvs_solver** set; int n; bool on; ~Invalidate() { if (on) for (int j = 0; j < n; ++j) set[j]->n_loaded = 0; } } invalidate_{set, NS, d2h_ == 0};
@@ -1503,12 +1444,12 @@ int uvs_debug_first_iteration(uvs_solver* s, const uvs_window* w, double* S_lowe
         if ((s->ksolve_nt == 512 ? uvs_k_solve512_timeline(tl.data(), tl.size()) == UVS_OK : hipMemcpyFromSymbol(tl.data(), HIP_SYMBOL(g_lin_tl), tl.size() * 8) == hipSuccess)) { if (FILE* f = std::fopen(tl_path, "wb")) { std::fwrite(tl.data(), 8, tl.size(), f); std::fclose(f); } }
     }
     const size_t nS = (size_t)UVS_RD * UVS_RD;
-    if (S_lower) HIPCHK(s, hipMemcpy(S_lower, s->d_dbg, nS * 8, hipMemcpyDeviceToHost));
-    if (g) HIPCHK(s, hipMemcpy(g, s->d_dbg + nS, UVS_RD * 8, hipMemcpyDeviceToHost));
-    if (hd) HIPCHK(s, hipMemcpy(hd, s->d_dbg + nS + UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
-    if (dd) HIPCHK(s, hipMemcpy(dd, s->d_dbg + nS + 2 * UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
-    if (step) HIPCHK(s, hipMemcpy(step, s->d_dbg + nS + 3 * UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
-    if (scal) HIPCHK(s, hipMemcpy(scal, s->d_dbg + nS + 4 * UVS_RD, UVS_DEBUG_SCAL_LEN * 8, hipMemcpyDeviceToHost));
+    if (S_lower) UVS_HIP(s->err, hipMemcpy(S_lower, s->d_dbg, nS * 8, hipMemcpyDeviceToHost));
+    if (g) UVS_HIP(s->err, hipMemcpy(g, s->d_dbg + nS, UVS_RD * 8, hipMemcpyDeviceToHost));
+    if (hd) UVS_HIP(s->err, hipMemcpy(hd, s->d_dbg + nS + UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
+    if (dd) UVS_HIP(s->err, hipMemcpy(dd, s->d_dbg + nS + 2 * UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
+    if (step) UVS_HIP(s->err, hipMemcpy(step, s->d_dbg + nS + 3 * UVS_RD, UVS_RD * 8, hipMemcpyDeviceToHost));
+    if (scal) UVS_HIP(s->err, hipMemcpy(scal, s->d_dbg + nS + 4 * UVS_RD, UVS_DEBUG_SCAL_LEN * 8, hipMemcpyDeviceToHost));
     return UVS_OK;
 }
 
@@ -1540,17 +1481,23 @@ struct MargWorker {
             cv_done.notify_all();
         }
     }
+    ~MargWorker() {      // waits for a marginalization begun and never waited for: it still uses the handle
+        if (in_flight) { std::unique_lock<std::mutex> lk(m); cv_done.wait(lk, [&] { return done; }); }
+        { std::lock_guard<std::mutex> lk(m); stop = true; }
+        cv_job.notify_one();
+        if (th.joinable()) th.join();
+    }
 };
 static bool marg_in_flight(const uvs_solver* s) { return s->marg_worker && s->marg_worker->in_flight; }      // (only the caller's thread reads / writes in_flight)
 static int marg_worker_begin(uvs_solver* s, const uvs_window* w, int flag) {
     if (!s->marg_worker) {
-        MargWorker* mw = new MargWorker(); mw->s = s;
-        try { mw->th = std::thread([mw] { mw->loop(); }); }
+        auto mw = std::make_unique<MargWorker>(); mw->s = s;
+        try { mw->th = std::thread([w_ = mw.get()] { w_->loop(); }); }
         catch (const std::exception& e) {      // (std::system_error when no thread can be created: nothing may cross the C boundary)
-            delete mw; s->err = std::string("uvs_marginalize_resident_begin: could not start the worker thread: ") + e.what();
+            s->err = std::string("uvs_marginalize_resident_begin: could not start the worker thread: ") + e.what();
             return UVS_ERR_HIP;
         }
-        s->marg_worker = mw;
+        s->marg_worker = std::move(mw);
     }
     MargWorker& mw = *s->marg_worker;
     { std::lock_guard<std::mutex> lk(mw.m); mw.w = w; mw.flag = flag; mw.has_job = true; mw.done = false; }
@@ -1564,14 +1511,6 @@ static int marg_worker_wait(uvs_solver* s) {
     mw.cv_done.wait(lk, [&] { return mw.done; });
     mw.done = false; mw.in_flight = false;
     return mw.rc;
-}
-static void free_marg_worker(MargWorker* mw) {
-    if (!mw) return;
-    if (mw->in_flight) { std::unique_lock<std::mutex> lk(mw->m); mw->cv_done.wait(lk, [&] { return mw->done; }); }
-    { std::lock_guard<std::mutex> lk(mw->m); mw->stop = true; }
-    mw->cv_job.notify_one();
-    if (mw->th.joinable()) mw->th.join();
-    delete mw;
 }
 
 // MARGIN_SECOND_NEW (estimator.cpp:1159-1228) marginalizes Pose[WINDOW_SIZE - 1] out of the OLD PRIOR and reads nothing else: no factor is evaluated, so no kernel runs and nothing is
@@ -1608,21 +1547,21 @@ int uvs_marginalize_resident(uvs_solver* s, const uvs_window* w, int flag, uvs_p
     }
     if (flag == 1) return marginalize_second_new_host(s, w, out);      // (reads the old prior only: host work, no device round trip)
     if (flag == 0) { const int rd = marginalize_old_device(s, w, out); if (rd != kMargFallback) return rd; }      // (needs nothing of the resident blob: the factors of frame 0 travel as a window of their own)
-    HIPCHK(s, hipSetDevice(s->device));
+    UVS_HIP(s->err, hipSetDevice(s->device));
     // state sections of the resident blob: frames[184] = pose | speedbias | ex_pose | td, inverse depths, line parameters
     // staged in the pinned upload buffer (copies from the caller's pageable arrays would each be a synchronous staging round trip)
     const size_t nst = 184 + (size_t)h.n_points + 4 * (size_t)h.n_lines;
-    HIPCHK(s, hipStreamSynchronize(s->stream));      // the staging buffer may still feed an earlier copy
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));      // the staging buffer may still feed an earlier copy
     int rcp;
-    if ((rcp = ensure_pinned(s, &s->h_up, &s->h_up_cap, nst * 8)) != UVS_OK) return rcp;
-    double* fr = (double*)s->h_up;
+    if ((rcp = s->h_up.ensure(nst * 8, s->err, grow_pinned)) != UVS_OK) return rcp;
+    double* fr = (double*)s->h_up.get();
     std::memcpy(fr, w->pose, 77 * 8); std::memcpy(fr + 77, w->speedbias, 99 * 8); std::memcpy(fr + 176, w->ex_pose, 7 * 8); fr[183] = w->td;
     if (h.n_points) std::memcpy(fr + 184, w->inv_depth, (size_t)h.n_points * 8);
     if (h.n_lines) std::memcpy(fr + 184 + h.n_points, w->line_orth, (size_t)h.n_lines * 32);
     char* blob = s->d_blobs + s->blob_off[0];
-    HIPCHK(s, hipMemcpyAsync(blob + (size_t)h.d_frames * 8, fr, 184 * 8, hipMemcpyHostToDevice, s->stream));
-    if (h.n_points) HIPCHK(s, hipMemcpyAsync(blob + (size_t)h.d_invd * 8, fr + 184, (size_t)h.n_points * 8, hipMemcpyHostToDevice, s->stream));
-    if (h.n_lines) HIPCHK(s, hipMemcpyAsync(blob + (size_t)h.d_line * 8, fr + 184 + h.n_points, (size_t)h.n_lines * 32, hipMemcpyHostToDevice, s->stream));
+    UVS_HIP(s->err, hipMemcpyAsync(blob + (size_t)h.d_frames * 8, fr, 184 * 8, hipMemcpyHostToDevice, s->stream));
+    if (h.n_points) UVS_HIP(s->err, hipMemcpyAsync(blob + (size_t)h.d_invd * 8, fr + 184, (size_t)h.n_points * 8, hipMemcpyHostToDevice, s->stream));
+    if (h.n_lines) UVS_HIP(s->err, hipMemcpyAsync(blob + (size_t)h.d_line * 8, fr + 184 + h.n_points, (size_t)h.n_lines * 32, hipMemcpyHostToDevice, s->stream));
     return run_marginalize(s->device, s->stream, s->d_blobs, s->d_ws, s->hdrs[0], w, make_kopts(s->opts, 0), flag, out, s->err, s->eval_scratch);
 }
 
@@ -1650,18 +1589,11 @@ int uvs_marginalize_wait(uvs_solver* s, uvs_prior* out) {
 // (assembled on the packing threads) to the same kernel.  A window the device path does not take (a landmark or frame block the reference's eps cut would touch, a system larger than
 // the kernel's LDS layout, no factors at all) goes through uvs_marginalize() on the calling thread.
 struct MargBatchBuf {
-    char* h_stage = nullptr; size_t h_stage_cap = 0;      // pinned: blobs | tables | descriptors | dense systems
-    char* h_out = nullptr; size_t h_out_cap = 0;          // pinned: finish outputs | linearization scalars
-    char* d_blobs = nullptr; size_t d_blobs_cap = 0; double* d_ws = nullptr; size_t d_ws_cap = 0; double* d_lin = nullptr; size_t d_lin_cap = 0;
-    char* d_tab = nullptr; size_t d_tab_cap = 0; double* d_in = nullptr; size_t d_in_cap = 0; double* d_out = nullptr; size_t d_out_cap = 0;
+    PinnedBuf<char> h_stage;      // pinned: blobs | tables | descriptors | dense systems
+    PinnedBuf<char> h_out;        // pinned: finish outputs | linearization scalars
+    DevBuf<char> d_blobs; DevBuf<double> d_ws, d_lin; DevBuf<char> d_tab; DevBuf<double> d_in, d_out;
     std::vector<MargDevScratch> thread_sub; std::vector<EvalScratch> thread_eval;
 };
-static void free_marg_batch(MargBatchBuf* m) {
-    if (!m) return;
-    if (m->h_stage) (void)hipHostFree(m->h_stage); if (m->h_out) (void)hipHostFree(m->h_out);
-    for (void* p : {(void*)m->d_blobs, (void*)m->d_ws, (void*)m->d_lin, (void*)m->d_tab, (void*)m->d_in, (void*)m->d_out}) if (p) (void)hipFree(p);
-    delete m;
-}
 namespace {
 struct MargBatchItem {
     int path = 3;      // 0: *out is final already; 1: device linearization + device finish (MARGIN_OLD); 2: device finish of a host-assembled system (MARGIN_SECOND_NEW); 3: uvs_marginalize()
@@ -1677,8 +1609,8 @@ extern "C" int uvs_marginalize_batch(uvs_solver* s, int n_win, const uvs_window*
     for (int b = 0; b < n_win; ++b) if (!ws[b] || (flags[b] != 0 && flags[b] != 1)) { s->err = "uvs_marginalize_batch: null window or flag outside {0, 1}"; return UVS_ERR_INVALID_ARG; }
     if (marg_in_flight(s)) { s->err = "uvs_marginalize_batch: a marginalization begun with uvs_marginalize_resident_begin has not been waited for"; return UVS_ERR_INVALID_ARG; }
     if (n_win == 0) return UVS_OK;
-    HIPCHK(s, hipSetDevice(s->device));
-    if (!s->marg_batch) s->marg_batch = new MargBatchBuf();
+    UVS_HIP(s->err, hipSetDevice(s->device));
+    if (!s->marg_batch) s->marg_batch = std::make_unique<MargBatchBuf>();
     MargBatchBuf& B = *s->marg_batch;
     const bool prof = std::getenv("UVS_MARG_PROFILE") != nullptr;
     const auto tb0 = std::chrono::steady_clock::now();
@@ -1744,15 +1676,15 @@ extern "C" int uvs_marginalize_batch(uvs_solver* s, int n_win, const uvs_window*
         for (int q = 0; q < n1; ++q) { const MargBatchItem& it = items[slot_win[q]]; blob_off[q] = (long long)blob_total; blob_total += (it.blob.size() + 255) & ~(size_t)255; ws_off[q] = ws_total; ws_total += it.h.ws_doubles; }
         const size_t tab_bytes = (size_t)n1 * 16 + (size_t)nfin * MF_DESC * 4, dense_bytes = (size_t)(nfin - n1) * MF_IN * 8;
         int rc;
-        if ((rc = ensure_pinned(s, &B.h_stage, &B.h_stage_cap, blob_total + tab_bytes + dense_bytes + 64)) != UVS_OK) return rc;
-        if ((rc = ensure_pinned(s, &B.h_out, &B.h_out_cap, (size_t)nfin * MF_OUT * 8 + (size_t)std::max(n1, 1) * 64)) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_blobs, &B.d_blobs_cap, std::max<size_t>(blob_total, 256))) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_ws, &B.d_ws_cap, std::max<size_t>((size_t)ws_total * 8, 256))) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_lin, &B.d_lin_cap, (size_t)std::max(n1, 1) * MARG_OUT * 8)) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_tab, &B.d_tab_cap, tab_bytes + 64)) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_in, &B.d_in_cap, std::max<size_t>(dense_bytes, 256))) != UVS_OK) return rc;
-        if ((rc = ensure(s, (void**)&B.d_out, &B.d_out_cap, (size_t)nfin * MF_OUT * 8)) != UVS_OK) return rc;
-        HIPCHK(s, hipStreamSynchronize(s->stream));      // the staging buffer may still feed an earlier call's copies
+        if ((rc = B.h_stage.ensure(blob_total + tab_bytes + dense_bytes + 64, s->err, grow_pinned)) != UVS_OK) return rc;
+        if ((rc = B.h_out.ensure((size_t)nfin * MF_OUT * 8 + (size_t)std::max(n1, 1) * 64, s->err, grow_pinned)) != UVS_OK) return rc;
+        if ((rc = B.d_blobs.ensure(std::max<size_t>(blob_total, 256), s->err)) != UVS_OK) return rc;
+        if ((rc = B.d_ws.ensure(std::max<size_t>((size_t)ws_total * 8, 256), s->err)) != UVS_OK) return rc;
+        if ((rc = B.d_lin.ensure((size_t)std::max(n1, 1) * MARG_OUT * 8, s->err)) != UVS_OK) return rc;
+        if ((rc = B.d_tab.ensure(tab_bytes + 64, s->err)) != UVS_OK) return rc;
+        if ((rc = B.d_in.ensure(std::max<size_t>(dense_bytes, 256), s->err)) != UVS_OK) return rc;
+        if ((rc = B.d_out.ensure((size_t)nfin * MF_OUT * 8, s->err)) != UVS_OK) return rc;
+        UVS_HIP(s->err, hipStreamSynchronize(s->stream));      // the staging buffer may still feed an earlier call's copies
         char* hb = B.h_stage; char* ht = hb + blob_total; char* hd = ht + ((tab_bytes + 7) & ~(size_t)7);
         for (int q = 0; q < n1; ++q) { const MargBatchItem& it = items[slot_win[q]]; std::memcpy(hb + blob_off[q], it.blob.data(), it.blob.size()); }
         long long* t_off = (long long*)ht; int* t_desc = (int*)(ht + (size_t)n1 * 16);
@@ -1764,35 +1696,35 @@ extern "C" int uvs_marginalize_batch(uvs_solver* s, int n_win, const uvs_window*
             if (q < n1) for (int i = 0; i < it.md + it.n; ++i) d[4 + i] = it.map[i];
             else std::memcpy(hd + (size_t)(q - n1) * MF_IN * 8, it.dense.data(), it.dense.size() * 8);
         }
-        if (n1 > 0) HIPCHK(s, hipMemcpyAsync(B.d_blobs, hb, blob_total, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(s, hipMemcpyAsync(B.d_tab, ht, tab_bytes, hipMemcpyHostToDevice, s->stream));
+        if (n1 > 0) UVS_HIP(s->err, hipMemcpyAsync(B.d_blobs, hb, blob_total, hipMemcpyHostToDevice, s->stream));
+        UVS_HIP(s->err, hipMemcpyAsync(B.d_tab, ht, tab_bytes, hipMemcpyHostToDevice, s->stream));
         if (nfin > n1) {      // (likewise only the used head N^2 + N of every dense input slot)
             int N_max = 1; for (int q = n1; q < nfin; ++q) N_max = std::max(N_max, items[slot_win[q]].md + items[slot_win[q]].n);
-            HIPCHK(s, hipMemcpy2DAsync(B.d_in, (size_t)MF_IN * 8, hd, (size_t)MF_IN * 8, (size_t)(N_max * N_max + N_max) * 8, (size_t)(nfin - n1), hipMemcpyHostToDevice, s->stream));
+            UVS_HIP(s->err, hipMemcpy2DAsync(B.d_in, (size_t)MF_IN * 8, hd, (size_t)MF_IN * 8, (size_t)(N_max * N_max + N_max) * 8, (size_t)(nfin - n1), hipMemcpyHostToDevice, s->stream));
         }
         const KOpts ko = make_kopts(o_sub, 0);
         if (n1 > 0) {
-            hipLaunchKernelGGL(k_marg_linearize_batch, dim3(n1), dim3(NT), LDS_BYTES, s->stream, B.d_blobs, (const long long*)B.d_tab, B.d_ws, (const long long*)B.d_tab + n1, ko, B.d_lin);
-            HIPCHK(s, hipGetLastError());
+            hipLaunchKernelGGL(k_marg_linearize_batch, dim3(n1), dim3(NT), LDS_BYTES, s->stream, B.d_blobs, (const long long*)B.d_tab.get(), B.d_ws, (const long long*)B.d_tab.get() + n1, ko, B.d_lin);
+            UVS_HIP(s->err, hipGetLastError());
         }
         // (path-2 slots read their dense system at slot - n1: the pointer is shifted so that the kernel's `in_all + MF_IN * blockIdx.x` lands there)
         hipLaunchKernelGGL(k_marg_finish, dim3(nfin), dim3(MF_NT), MF_LDS_BYTES, s->stream, (const int*)(B.d_tab + (size_t)n1 * 16), (const double*)B.d_in - (size_t)n1 * MF_IN, (const double*)B.d_lin, (int)MARG_OUT,
                            (int)UVS_RD, B.d_out, 1e-8);
-        HIPCHK(s, hipGetLastError());
+        UVS_HIP(s->err, hipGetLastError());
         int n_max = 1; for (int q = 0; q < nfin; ++q) n_max = std::max(n_max, items[slot_win[q]].n);
         // (only the used head of every output slot travels: status | r0 | J0 [n][n])
-        HIPCHK(s, hipMemcpy2DAsync(B.h_out, (size_t)MF_OUT * 8, B.d_out, (size_t)MF_OUT * 8, (size_t)(MF_OUT_J + n_max * n_max) * 8, (size_t)nfin, hipMemcpyDeviceToHost, s->stream));
+        UVS_HIP(s->err, hipMemcpy2DAsync(B.h_out, (size_t)MF_OUT * 8, B.d_out, (size_t)MF_OUT * 8, (size_t)(MF_OUT_J + n_max * n_max) * 8, (size_t)nfin, hipMemcpyDeviceToHost, s->stream));
         double* h_scal = (double*)(B.h_out + (size_t)nfin * MF_OUT * 8);
-        if (n1 > 0) HIPCHK(s, hipMemcpy2DAsync(h_scal, 64, B.d_lin + (MARG_OUT - 8), (size_t)MARG_OUT * 8, 64, (size_t)n1, hipMemcpyDeviceToHost, s->stream));
+        if (n1 > 0) UVS_HIP(s->err, hipMemcpy2DAsync(h_scal, 64, B.d_lin + (MARG_OUT - 8), (size_t)MARG_OUT * 8, 64, (size_t)n1, hipMemcpyDeviceToHost, s->stream));
         tb2 = std::chrono::steady_clock::now();
-        HIPCHK(s, hipStreamSynchronize(s->stream));
+        UVS_HIP(s->err, hipStreamSynchronize(s->stream));
         tb3 = std::chrono::steady_clock::now();
-        if (prof) { double sw = 0, swmax = 0, rot = 0, cut = 0, cy[3] = {0, 0, 0}; for (int q = 0; q < nfin; ++q) { const double* fo = (const double*)B.h_out + (size_t)q * MF_OUT; sw += fo[MF_OUT_S + 1]; swmax = std::max(swmax, fo[MF_OUT_S + 1]); rot += fo[MF_OUT_S + 2]; cut += fo[MF_OUT_S + 3]; for (int k = 0; k < 3; ++k) cy[k] += fo[MF_OUT_S + 4 + k]; }
+        if (prof) { double sw = 0, swmax = 0, rot = 0, cut = 0, cy[3] = {0, 0, 0}; for (int q = 0; q < nfin; ++q) { const double* fo = (const double*)B.h_out.get() + (size_t)q * MF_OUT; sw += fo[MF_OUT_S + 1]; swmax = std::max(swmax, fo[MF_OUT_S + 1]); rot += fo[MF_OUT_S + 2]; cut += fo[MF_OUT_S + 3]; for (int k = 0; k < 3; ++k) cy[k] += fo[MF_OUT_S + 4 + k]; }
                     std::fprintf(stderr, "[uvs_marginalize_batch] k_marg_finish: %.1f Jacobi sweeps (most: %.0f), %.0f rotations, %.1f eigenvalues cut per window (mean over %d); shader-clock cycles per window: first rotation parameters of the sweeps %.0f k, A passes %.0f k, V passes (beside the next step's parameters) %.0f k\n",
                                  sw / nfin, swmax, rot / nfin, cut / nfin, nfin, cy[0] / nfin * 1e-3, cy[1] / nfin * 1e-3, cy[2] / nfin * 1e-3); }
         for (int q = 0; q < nfin; ++q) {
             const int b = slot_win[q]; MargBatchItem& it = items[b];
-            const double* fo = (const double*)B.h_out + (size_t)q * MF_OUT;
+            const double* fo = (const double*)B.h_out.get() + (size_t)q * MF_OUT;
             const int st = (int)fo[MF_OUT_S];
             if (q < n1 && (h_scal[8 * q + 1] != 0.0 || !std::isfinite(h_scal[8 * q]))) { it.path = 3; continue; }      // a landmark block the reference's eps cut would touch: the host path applies that cut
             if (st == MF_NONFINITE) { it.rc = UVS_ERR_NUMERIC; it.err = "marginalization: the linearized system is not finite"; it.path = 0; continue; }
@@ -1823,7 +1755,44 @@ extern "C" int uvs_marginalize_batch(uvs_solver* s, int n_win, const uvs_window*
     return first_bad;
 }
 
+uvs_solver::~uvs_solver() {
+    if (!pool_borrowed) delete pool;
+    for (hipEvent_t e : {ev_done, ev0, ev1}) if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+// Defined here, where the types a handle owns are complete.  Only the steps whose order matters; every buffer frees itself.
+extern "C" void uvs_destroy(uvs_solver* s) {
+    if (!s) return;
+    s->marg_worker.reset();      // (waits for a marginalization begun and never waited for: it still uses the handle)
+    s->twin.reset(); s->twin2.reset(); s->twin3.reset();      // before the PackPool they borrow (~uvs_solver)
+    uvs_large_comm_destroy(s);
+    (void)hipSetDevice(s->device);      // teardown: nothing useful to do with an error
+    delete s;
+}
+
 // ------------------------------------------------------------------ large single window (configs[3]), optionally multi-GPU
+// What uvs_large_begin and uvs_large_solve_fused do once the window is uploaded: a fresh run state, the buffers of the loop, ||x||^2.
+static int large_prologue(uvs_solver* s, const uvs_window* w) {
+    auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0];
+    L = {};      // (the buffers and the communicator in LB stay)
+    L.n_chunks = h.n_chunks; L.radius = s->opts.initial_trust_region_radius;
+    L.grid = std::min(h.n_chunks, s->chunk_wgs());
+    const std::pair<DevBuf<double>*, size_t> bufs[] = {{&LB.d_state, LG_STATE}, {&LB.d_reduced, LG_XCH_ALL}, {&LB.d_out, 64}, {&LB.d_sc5, 8}, {&LB.d_fimg, LG_FIMG},
+                                                       {&LB.d_partials, (size_t)std::max(L.grid, 1) * LG_ROW}, {&LB.d_bsums, (size_t)std::max(L.n_chunks, 1) * 8}};      // doubles
+    for (const auto& b : bufs) if (const int rc = b.first->ensure(b.second * 8, s->err)) return rc;
+    double x2 = 0.0, l2 = 0.0;      // ||x||^2: frames (identical on every rank) and this rank's landmarks (summed over the ranks by the first all-reduce)
+    for (int f = 0; f < UVS_NUM_FRAMES; ++f) { for (int k = 0; k < 7; ++k) x2 += w->pose[f][k] * w->pose[f][k]; for (int k = 0; k < 9; ++k) x2 += w->speedbias[f][k] * w->speedbias[f][k]; }
+    if (s->opts.estimate_td) x2 += w->td * w->td;
+    if (s->opts.estimate_extrinsic) for (int k = 0; k < 7; ++k) x2 += w->ex_pose[k] * w->ex_pose[k];
+    if (w->n_relo_obs > 0) for (int k = 0; k < 7; ++k) x2 += w->relo_pose[k] * w->relo_pose[k];      // relo_Pose is a free block of the problem (estimator.cpp:947)
+    for (int k = 0; k < w->n_points; ++k) l2 += w->inv_depth[k] * w->inv_depth[k];
+    for (int k = 0; k < 4 * w->n_lines; ++k) l2 += w->line_orth[k] * w->line_orth[k];
+    L.local_x2 = l2; L.x_norm = std::sqrt(x2 + l2); L.frame_x2 = x2;
+    std::memcpy(L.relo_pose_in, w->relo_pose, sizeof(L.relo_pose_in));
+    return UVS_OK;
+}
+
 // Step-wise so that the caller can all-reduce the two device vectors between steps (RCCL through torch.distributed in
 // bench.py / api.py; nothing to reduce on one GPU):
 //   uvs_large_begin -> loop { uvs_large_linearize -> [all-reduce SUM of uvs_large_reduced()] -> uvs_large_step
@@ -1835,34 +1804,17 @@ int uvs_large_begin(uvs_solver* s, const uvs_window* w) {
     const uvs_window* arr[1] = {w};
     int rc = upload_windows(s, 1, arr, true, s->chunk_wgs());
     if (rc != UVS_OK) return rc;
-    auto& L = s->L; const DevWin& h = s->hdrs[0];
-    double* keep_ctl = L.d_ctl; uvs_report* keep_rep = L.d_rep; void* keep_comm = L.comm; const int keep_rank = L.rank, keep_nranks = L.nranks; double* keep_fimg = L.d_fimg;
-    L = uvs_solver::Large{L.active, 0, 0, 0, 0, 0, 0, 0, 0, true, true, false, 0, 2, 0, 0, 0, 0, L.d_state, L.d_partials, L.d_reduced, L.d_bsums, L.d_out, L.d_sc5, L.cap_partials, L.cap_bsums, {}};
-    L.active = true; L.n_chunks = h.n_chunks; L.radius = s->opts.initial_trust_region_radius;
-    L.grid = std::min(h.n_chunks, s->chunk_wgs());
-    L.d_ctl = keep_ctl; L.d_rep = keep_rep; L.comm = keep_comm; L.rank = keep_rank; L.nranks = keep_nranks; L.d_fimg = keep_fimg;
-    if (!L.d_state) { HIPCHK(s, hipMalloc((void**)&L.d_state, LG_STATE * 8)); HIPCHK(s, hipMalloc((void**)&L.d_reduced, LG_XCH_ALL * 8)); HIPCHK(s, hipMemset(L.d_reduced, 0, LG_XCH_ALL * 8)); HIPCHK(s, hipMalloc((void**)&L.d_out, 64 * 8)); HIPCHK(s, hipMalloc((void**)&L.d_sc5, 8 * 8)); }
-    if (!L.d_fimg) HIPCHK(s, hipMalloc((void**)&L.d_fimg, LG_FIMG * 8));
-    int r2;
-    if ((r2 = ensure(s, (void**)&L.d_partials, &L.cap_partials, (size_t)std::max(L.grid, 1) * LG_ROW * 8)) != UVS_OK) return r2;
-    if ((r2 = ensure(s, (void**)&L.d_bsums, &L.cap_bsums, (size_t)std::max(L.n_chunks, 1) * 8 * 8)) != UVS_OK) return r2;
-    HIPCHK(s, hipMemsetAsync(L.d_state, 0, LG_STATE * 8, s->stream));
+    const bool fresh = !s->LB.d_reduced;      // (zeroed once, when it is first allocated)
+    if ((rc = large_prologue(s, w)) != UVS_OK) return rc;
+    auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0];
+    L.active = true;
+    if (fresh) UVS_HIP(s->err, hipMemset(LB.d_reduced, 0, LG_XCH_ALL * 8));
+    UVS_HIP(s->err, hipMemsetAsync(LB.d_state, 0, LG_STATE * 8, s->stream));
     // frames -> state.X ; landmark parameters -> workspace buffer 0 (device-to-device from the blob)
-    HIPCHK(s, hipMemcpyAsync(L.d_state + LS_X, s->d_blobs + (size_t)h.d_frames * 8, UVS_XDIM * 8, hipMemcpyDeviceToDevice, s->stream));
-    if (h.n_points) HIPCHK(s, hipMemcpyAsync(s->d_ws + h.w_invd0, s->d_blobs + (size_t)h.d_invd * 8, (size_t)h.n_points * 8, hipMemcpyDeviceToDevice, s->stream));
-    if (h.n_lines) HIPCHK(s, hipMemcpyAsync(s->d_ws + h.w_line0, s->d_blobs + (size_t)h.d_line * 8, (size_t)h.n_lines * 32, hipMemcpyDeviceToDevice, s->stream));
-    double x2 = 0.0;
-    for (int f = 0; f < UVS_NUM_FRAMES; ++f) { for (int k = 0; k < 7; ++k) x2 += w->pose[f][k] * w->pose[f][k]; for (int k = 0; k < 9; ++k) x2 += w->speedbias[f][k] * w->speedbias[f][k]; }
-    if (s->opts.estimate_td) x2 += w->td * w->td;
-    if (s->opts.estimate_extrinsic) for (int k = 0; k < 7; ++k) x2 += w->ex_pose[k] * w->ex_pose[k];
-    if (w->n_relo_obs > 0) for (int k = 0; k < 7; ++k) x2 += w->relo_pose[k] * w->relo_pose[k];      // relo_Pose is a free block of the problem (estimator.cpp:947)
-    double l2 = 0.0;
-    for (int k = 0; k < w->n_points; ++k) l2 += w->inv_depth[k] * w->inv_depth[k];
-    for (int k = 0; k < 4 * w->n_lines; ++k) l2 += w->line_orth[k] * w->line_orth[k];
-    L.local_x2 = l2; L.x_norm = std::sqrt(x2 + l2); L.frame_x2 = x2;
-    std::memset(&L.rep, 0, sizeof(L.rep));
-    std::memcpy(L.relo_pose_in, w->relo_pose, sizeof(L.relo_pose_in));
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+    UVS_HIP(s->err, hipMemcpyAsync(LB.d_state + LS_X, s->d_blobs + (size_t)h.d_frames * 8, UVS_XDIM * 8, hipMemcpyDeviceToDevice, s->stream));
+    if (h.n_points) UVS_HIP(s->err, hipMemcpyAsync(s->d_ws + h.w_invd0, s->d_blobs + (size_t)h.d_invd * 8, (size_t)h.n_points * 8, hipMemcpyDeviceToDevice, s->stream));
+    if (h.n_lines) UVS_HIP(s->err, hipMemcpyAsync(s->d_ws + h.w_line0, s->d_blobs + (size_t)h.d_line * 8, (size_t)h.n_lines * 32, hipMemcpyDeviceToDevice, s->stream));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     L.t_begin = std::chrono::steady_clock::now();
     return UVS_OK;
 }
@@ -1873,47 +1825,47 @@ void uvs_large_set_landmark_x2(uvs_solver* s, double all_ranks_x2) { if (s) { au
 
 int uvs_large_need_linearize(const uvs_solver* s) { return s && s->L.active && !s->L.done && s->L.need_lin; }
 int uvs_large_done(const uvs_solver* s) { return !s || !s->L.active || s->L.done; }
-double* uvs_large_reduced(uvs_solver* s, int* n) { if (n) *n = LG_RED; return s ? s->L.d_reduced : nullptr; }     // DEVICE pointer; [LG_ACC+1] is a MAX entry
-double* uvs_large_scalars(uvs_solver* s, int* n) { if (n) *n = 6; return s ? s->L.d_sc5 : nullptr; }             // DEVICE pointer; [5] = this rank's "time is up" vote (SUM over ranks > 0 ends the solve on every rank)
+double* uvs_large_reduced(uvs_solver* s, int* n) { if (n) *n = LG_RED; return s ? s->LB.d_reduced.get() : nullptr; }     // DEVICE pointer; [LG_ACC+1] is a MAX entry
+double* uvs_large_scalars(uvs_solver* s, int* n) { if (n) *n = 6; return s ? s->LB.d_sc5.get() : nullptr; }             // DEVICE pointer; [5] = this rank's "time is up" vote (SUM over ranks > 0 ends the solve on every rank)
 
 // host-staged access to the two exchange vectors (which = 0: reduced[LG_RED], 1: scalars[5]); set != 0 writes host -> device
 int uvs_large_exchange_host(uvs_solver* s, int which, double* buf, int set) {
     if (!s || !s->L.active || !buf) return UVS_ERR_INVALID_ARG;
-    double* d = which == 0 ? s->L.d_reduced : s->L.d_sc5; const size_t n = which == 0 ? LG_RED : 6;
-    HIPCHK(s, hipSetDevice(s->device));
-    if (set) HIPCHK(s, hipMemcpy(d, buf, n * 8, hipMemcpyHostToDevice)); else HIPCHK(s, hipMemcpy(buf, d, n * 8, hipMemcpyDeviceToHost));
+    double* d = which == 0 ? s->LB.d_reduced.get() : s->LB.d_sc5.get(); const size_t n = which == 0 ? LG_RED : 6;
+    UVS_HIP(s->err, hipSetDevice(s->device));
+    if (set) UVS_HIP(s->err, hipMemcpy(d, buf, n * 8, hipMemcpyHostToDevice)); else UVS_HIP(s->err, hipMemcpy(buf, d, n * 8, hipMemcpyDeviceToHost));
     return UVS_OK;
 }
 
 int uvs_large_linearize(uvs_solver* s) {
     if (!s || !s->L.active) return UVS_ERR_INVALID_ARG;
-    auto& L = s->L;
-    HIPCHK(s, hipSetDevice(s->device));
+    auto& L = s->L; auto& LB = s->LB;
+    UVS_HIP(s->err, hipSetDevice(s->device));
     KOpts ko = make_kopts(s->opts, 0);
-    if (s->large_chunks_nt == 512) { if (uvs_k_large_chunks512_launch(L.grid + 1, s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), L.d_state, L.sel, L.first ? 1 : 0, L.radius, L.d_partials, nullptr, 0, 0, L.grid, L.d_fimg) != UVS_OK) { s->err = "k_large_chunks (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
-    else hipLaunchKernelGGL(k_large_chunks, dim3(L.grid + 1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, L.sel, L.first ? 1 : 0, L.radius, L.d_partials, LargeCtl{nullptr, 0, 0}, L.grid, L.d_fimg);
-    { const int n_ent = s->hdrs[0].relo2 ? LG_ROW : LG_RED; hipLaunchKernelGGL(k_large_reduce, dim3((n_ent + 15) / 16), dim3(256), 0, s->stream, L.d_partials, L.grid, L.d_reduced, LargeCtl{nullptr, 0, 0}, n_ent); }
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (s->large_chunks_nt == 512) { if (uvs_k_large_chunks512_launch(L.grid + 1, s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), LB.d_state, L.sel, L.first ? 1 : 0, L.radius, LB.d_partials, nullptr, 0, 0, L.grid, LB.d_fimg) != UVS_OK) { s->err = "k_large_chunks (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
+    else hipLaunchKernelGGL(k_large_chunks, dim3(L.grid + 1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, L.sel, L.first ? 1 : 0, L.radius, LB.d_partials, LargeCtl{nullptr, 0, 0}, L.grid, LB.d_fimg);
+    { const int n_ent = s->hdrs[0].relo2 ? LG_ROW : LG_RED; hipLaunchKernelGGL(k_large_reduce, dim3((n_ent + 15) / 16), dim3(256), 0, s->stream, LB.d_partials, L.grid, LB.d_reduced, LargeCtl{nullptr, 0, 0}, n_ent); }
+    UVS_HIP(s->err, hipGetLastError());
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     return UVS_OK;
 }
 
 int uvs_large_step(uvs_solver* s) {
     if (!s || !s->L.active) return UVS_ERR_INVALID_ARG;
-    auto& L = s->L;
-    HIPCHK(s, hipSetDevice(s->device));
+    auto& L = s->L; auto& LB = s->LB;
+    UVS_HIP(s->err, hipSetDevice(s->device));
     KOpts ko = make_kopts(s->opts, 0);
-    if (s->large_solve_nt == 512) { if (uvs_k_large_solve512_launch(s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), L.d_state, L.d_reduced, L.first ? 1 : 0, L.radius, L.d_out, nullptr, 0, 0, L.d_fimg) != UVS_OK) { s->err = "k_large_solve (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
-    else hipLaunchKernelGGL(k_large_solve, dim3(1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, L.d_reduced, L.first ? 1 : 0, L.radius, L.d_out, LargeCtl{nullptr, 0, 0}, L.d_fimg);
+    if (s->large_solve_nt == 512) { if (uvs_k_large_solve512_launch(s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), LB.d_state, LB.d_reduced, L.first ? 1 : 0, L.radius, LB.d_out, nullptr, 0, 0, LB.d_fimg) != UVS_OK) { s->err = "k_large_solve (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
+    else hipLaunchKernelGGL(k_large_solve, dim3(1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, LB.d_reduced, L.first ? 1 : 0, L.radius, LB.d_out, LargeCtl{nullptr, 0, 0}, LB.d_fimg);
     { const int bg = std::min(L.n_chunks, UVS_LARGE_OCC * s->chunk_wgs());      // (UVS_LARGE_OCC workgroups per compute unit: the kernel asks for little LDS and half the registers)
-      hipLaunchKernelGGL(k_large_backsub, dim3(bg + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, L.sel, L.d_bsums, LargeCtl{nullptr, 0, 0}, bg, L.d_out); }
-    hipLaunchKernelGGL(k_large_sum_bsums, dim3(1), dim3(256), 0, s->stream, L.d_bsums, L.n_chunks, L.d_sc5, LargeCtl{nullptr, 0, 0}, 0LL);
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipStreamSynchronize(s->stream));
+      hipLaunchKernelGGL(k_large_backsub, dim3(bg + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, L.sel, LB.d_bsums, LargeCtl{nullptr, 0, 0}, bg, LB.d_out); }
+    hipLaunchKernelGGL(k_large_sum_bsums, dim3(1), dim3(256), 0, s->stream, LB.d_bsums, L.n_chunks, LB.d_sc5, LargeCtl{nullptr, 0, 0}, 0LL);
+    UVS_HIP(s->err, hipGetLastError());
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
     // options.max_solver_time_in_seconds on the host-driven loop: this process's vote travels as scalar [5], so that ranks which all-reduce the scalars decide together
     const uvs_options& o = s->opts;
     const double vote = (o.max_solver_time_in_seconds > 0.0 && L.it > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - L.t_begin).count() >= o.max_solver_time_in_seconds) ? 1.0 : 0.0;
-    if (o.max_solver_time_in_seconds > 0.0) HIPCHK(s, hipMemcpy(L.d_sc5 + 5, &vote, 8, hipMemcpyHostToDevice));
+    if (o.max_solver_time_in_seconds > 0.0) UVS_HIP(s->err, hipMemcpy(LB.d_sc5 + 5, &vote, 8, hipMemcpyHostToDevice));
     return UVS_OK;
 }
 
@@ -1921,10 +1873,10 @@ int uvs_large_step(uvs_solver* s) {
 // caller all-reduced uvs_large_scalars()).  Note: on this path a (re)linearization is implied by need_lin BEFORE the next step.
 int uvs_large_decide(uvs_solver* s) {
     if (!s || !s->L.active) return UVS_ERR_INVALID_ARG;
-    auto& L = s->L; const uvs_options& o = s->opts;
+    auto& L = s->L; auto& LB = s->LB; const uvs_options& o = s->opts;
     double out[LO_N + 8], sc[6];
-    HIPCHK(s, hipMemcpy(out, L.d_out, sizeof(double) * (LO_N + 4), hipMemcpyDeviceToHost));
-    HIPCHK(s, hipMemcpy(sc, L.d_sc5, sizeof(sc), hipMemcpyDeviceToHost));
+    UVS_HIP(s->err, hipMemcpy(out, LB.d_out, sizeof(double) * (LO_N + 4), hipMemcpyDeviceToHost));
+    UVS_HIP(s->err, hipMemcpy(sc, LB.d_sc5, sizeof(sc), hipMemcpyDeviceToHost));
     uvs_report& rep = L.rep;
     const double lc = out[LO_COST]; const double gm = out[LO_GMAX];
     if (L.first) {
@@ -1962,7 +1914,7 @@ int uvs_large_decide(uvs_solver* s) {
     else if (std::fabs(L.cost - cand) <= o.function_tolerance * L.cost) { L.term = UVS_TERM_FUNCTION_TOL; stop = true; }
     if (stop && !(o.function_tol_keeps_candidate && successful)) { L.done = true; return UVS_OK; }
     if (successful) {
-        HIPCHK(s, hipMemcpyAsync(L.d_state + LS_X, L.d_state + LS_XC, UVS_XDIM * 8, hipMemcpyDeviceToDevice, s->stream));   // stream-ordered with the next launch (a plain D2D hipMemcpy
+        UVS_HIP(s->err, hipMemcpyAsync(LB.d_state + LS_X, LB.d_state + LS_XC, UVS_XDIM * 8, hipMemcpyDeviceToDevice, s->stream));   // stream-ordered with the next launch (a plain D2D hipMemcpy
         // runs on the null stream, which this non-blocking stream does not wait for)
         L.sel ^= 1; ++L.nsucc; L.x_norm = std::sqrt(xc2);
         L.radius = L.radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3.0));
@@ -1980,15 +1932,15 @@ int uvs_large_decide(uvs_solver* s) {
 
 int uvs_large_finish(uvs_solver* s, uvs_state* out, uvs_report* rep) {
     if (!s || !s->L.active || !out || !rep) return UVS_ERR_INVALID_ARG;
-    auto& L = s->L; const DevWin& h = s->hdrs[0];
+    auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0];
     L.rep.status = L.status; L.rep.termination = L.term; L.rep.num_iterations = L.it; L.rep.num_successful = L.nsucc; L.rep.final_cost = L.cost;
     *rep = L.rep;
     double fr[UVS_XDIM];
-    HIPCHK(s, hipMemcpy(fr, L.d_state + LS_X, sizeof(fr), hipMemcpyDeviceToHost));
+    UVS_HIP(s->err, hipMemcpy(fr, LB.d_state + LS_X, sizeof(fr), hipMemcpyDeviceToHost));
     std::memcpy(out->pose, fr, 77 * 8); std::memcpy(out->speedbias, fr + 77, 99 * 8); std::memcpy(out->ex_pose, fr + 176, 7 * 8); out->td = fr[183];
     std::memcpy(out->relo_pose, fr + 184, sizeof(out->relo_pose));      // optimized when the window carries relocalization blocks, the input value otherwise
-    if (out->inv_depth && h.n_points) HIPCHK(s, hipMemcpy(out->inv_depth, s->d_ws + (L.sel ? h.w_invd1 : h.w_invd0), (size_t)h.n_points * 8, hipMemcpyDeviceToHost));
-    if (out->line_orth && h.n_lines) HIPCHK(s, hipMemcpy(out->line_orth, s->d_ws + (L.sel ? h.w_line1 : h.w_line0), (size_t)h.n_lines * 32, hipMemcpyDeviceToHost));
+    if (out->inv_depth && h.n_points) UVS_HIP(s->err, hipMemcpy(out->inv_depth, s->d_ws + (L.sel ? h.w_invd1 : h.w_invd0), (size_t)h.n_points * 8, hipMemcpyDeviceToHost));
+    if (out->line_orth && h.n_lines) UVS_HIP(s->err, hipMemcpy(out->line_orth, s->d_ws + (L.sel ? h.w_line1 : h.w_line0), (size_t)h.n_lines * 32, hipMemcpyDeviceToHost));
     L.active = false;
     return L.status;
 }
@@ -2050,23 +2002,23 @@ int uvs_large_comm_unique_id(uvs_rccl_id* id) {
 
 int uvs_large_comm_init(uvs_solver* s, int nranks, int rank, const uvs_rccl_id* id) {
     if (!s || nranks < 1 || nranks > LG_MAXRANKS || rank < 0 || rank >= nranks || (nranks > 1 && !id)) return UVS_ERR_INVALID_ARG;
-    auto& L = s->L;
+    auto& LB = s->LB;
     uvs_large_comm_destroy(s);
-    L.rank = rank; L.nranks = nranks;
+    LB.rank = rank; LB.nranks = nranks;
     if (nranks == 1 && !id) return UVS_OK;                        // nothing to exchange (with an id a one-rank communicator is built all the same: exercises the RCCL path on one GPU)
     RcclApi& r = rccl();
     if (!r.lib) { s->err = r.err; return UVS_ERR_UNSUPPORTED; }
-    HIPCHK(s, hipSetDevice(s->device));
-    const int rc = r.CommInitRank(&L.comm, nranks, *id, rank);
-    if (rc != 0) { s->err = std::string("ncclCommInitRank: ") + (r.GetErrorString ? r.GetErrorString(rc) : "error"); L.comm = nullptr; L.nranks = 1; L.rank = 0; return UVS_ERR_HIP; }
+    UVS_HIP(s->err, hipSetDevice(s->device));
+    const int rc = r.CommInitRank(&LB.comm, nranks, *id, rank);
+    if (rc != 0) { s->err = std::string("ncclCommInitRank: ") + (r.GetErrorString ? r.GetErrorString(rc) : "error"); LB.comm = nullptr; LB.nranks = 1; LB.rank = 0; return UVS_ERR_HIP; }
     return UVS_OK;
 }
 
 void uvs_large_comm_destroy(uvs_solver* s) {
     if (!s) return;
-    auto& L = s->L;
-    if (L.comm) { (void)hipSetDevice(s->device); rccl().CommDestroy(L.comm); L.comm = nullptr; }
-    L.rank = 0; L.nranks = 1;
+    auto& LB = s->LB;
+    if (LB.comm) { (void)hipSetDevice(s->device); rccl().CommDestroy(LB.comm); LB.comm = nullptr; }
+    LB.rank = 0; LB.nranks = 1;
 }
 
 // Error inside the enqueue loop of the fused solve: drain what is already on the stream and leave the handle idle.  With several ranks the
@@ -2090,71 +2042,51 @@ int uvs_large_solve_fused(uvs_solver* s, const uvs_window* w, uvs_state* out, uv
     const uvs_window* arr[1] = {w};
     int rc = upload_windows(s, 1, arr, false, s->chunk_wgs());
     if (rc != UVS_OK) return rc;
-    auto& L = s->L; const DevWin& h = s->hdrs[0]; const uvs_options& o = s->opts;
+    auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0]; const uvs_options& o = s->opts;
     // relocalization blocks are per-landmark, so a landmark shard may hold none of them while the all-reduced system carries the other ranks' relo_Pose rows: a rank
     // cannot tell from its own shard whether relo_Pose is a free block.  Not taken by a multi-rank solve (NO rank may pass n_relo_obs > 0; one rank takes them).
-    if (L.nranks > 1 && w->n_relo_obs > 0) { s->err = "relocalization blocks are not taken by a landmark-sharded solve over several ranks"; return UVS_ERR_UNSUPPORTED; }
-    {
-        double* keep_ctl = L.d_ctl; uvs_report* keep_rep = L.d_rep; void* keep_comm = L.comm; const int keep_rank = L.rank, keep_nranks = L.nranks; double* keep_fimg = L.d_fimg;
-        L = uvs_solver::Large{L.active, 0, 0, 0, 0, 0, 0, 0, 0, true, true, false, 0, 2, 0, 0, 0, 0, L.d_state, L.d_partials, L.d_reduced, L.d_bsums, L.d_out, L.d_sc5, L.cap_partials, L.cap_bsums, {}};
-        L.active = false; L.n_chunks = h.n_chunks; L.radius = o.initial_trust_region_radius;      // active only while work is enqueued (set below): an allocation failure leaves the handle idle
-        L.grid = std::min(h.n_chunks, s->chunk_wgs());
-        L.d_ctl = keep_ctl; L.d_rep = keep_rep; L.comm = keep_comm; L.rank = keep_rank; L.nranks = keep_nranks; L.d_fimg = keep_fimg;
-    }
-    if (!L.d_state) { HIPCHK(s, hipMalloc((void**)&L.d_state, LG_STATE * 8)); HIPCHK(s, hipMalloc((void**)&L.d_reduced, LG_XCH_ALL * 8)); HIPCHK(s, hipMalloc((void**)&L.d_out, 64 * 8)); HIPCHK(s, hipMalloc((void**)&L.d_sc5, 8 * 8)); }
-    if (!L.d_fimg) HIPCHK(s, hipMalloc((void**)&L.d_fimg, LG_FIMG * 8));
-    if (!L.d_ctl) { HIPCHK(s, hipMalloc((void**)&L.d_ctl, 64 * 8)); HIPCHK(s, hipMalloc((void**)&L.d_rep, sizeof(uvs_report))); }
-    if ((rc = ensure(s, (void**)&L.d_partials, &L.cap_partials, (size_t)std::max(L.grid, 1) * LG_ROW * 8)) != UVS_OK) return rc;
-    if ((rc = ensure(s, (void**)&L.d_bsums, &L.cap_bsums, (size_t)std::max(L.n_chunks, 1) * 8 * 8)) != UVS_OK) return rc;
+    if (LB.nranks > 1 && w->n_relo_obs > 0) { s->err = "relocalization blocks are not taken by a landmark-sharded solve over several ranks"; return UVS_ERR_UNSUPPORTED; }
+    if ((rc = large_prologue(s, w)) != UVS_OK) return rc;      // (inactive until work is enqueued, below: an allocation failure leaves the handle idle)
     constexpr int RD = (int)(sizeof(uvs_report) / 8);
     const size_t out_doubles = 64 + RD + UVS_XDIM + (size_t)h.n_points + 4 * (size_t)h.n_lines;
-    if ((rc = ensure(s, (void**)&s->d_outpack, &s->d_outpack_cap, out_doubles * 8)) != UVS_OK) return rc;
-    if ((rc = ensure_pinned(s, &s->h_out, &s->h_out_cap, out_doubles * 8)) != UVS_OK) return rc;
-    double x2 = 0.0, l2 = 0.0;      // ||x||^2: frames (identical on every rank) and this rank's landmarks (summed over the ranks by the first all-reduce)
-    for (int f = 0; f < UVS_NUM_FRAMES; ++f) { for (int k = 0; k < 7; ++k) x2 += w->pose[f][k] * w->pose[f][k]; for (int k = 0; k < 9; ++k) x2 += w->speedbias[f][k] * w->speedbias[f][k]; }
-    if (o.estimate_td) x2 += w->td * w->td;
-    if (o.estimate_extrinsic) for (int k = 0; k < 7; ++k) x2 += w->ex_pose[k] * w->ex_pose[k];
-    if (w->n_relo_obs > 0) for (int k = 0; k < 7; ++k) x2 += w->relo_pose[k] * w->relo_pose[k];
-    for (int k = 0; k < w->n_points; ++k) l2 += w->inv_depth[k] * w->inv_depth[k];
-    for (int k = 0; k < 4 * w->n_lines; ++k) l2 += w->line_orth[k] * w->line_orth[k];
-    L.local_x2 = l2; L.x_norm = std::sqrt(x2 + l2); L.frame_x2 = x2;
-    std::memcpy(L.relo_pose_in, w->relo_pose, sizeof(L.relo_pose_in));
+    if ((rc = LB.d_ctl.ensure(64 * 8, s->err)) != UVS_OK || (rc = LB.d_rep.ensure(sizeof(uvs_report), s->err)) != UVS_OK ||
+        (rc = s->d_outpack.ensure(out_doubles * 8, s->err)) != UVS_OK || (rc = s->h_out.ensure(out_doubles * 8, s->err, grow_pinned)) != UVS_OK) return rc;
     L.active = true;
-    hipLaunchKernelGGL(k_large_init, dim3(16), dim3(256), 0, s->stream, s->d_blobs, s->d_ws, L.d_state, L.d_ctl, L.d_rep, L.d_reduced, o.initial_trust_region_radius, L.frame_x2, L.local_x2);
+    hipLaunchKernelGGL(k_large_init, dim3(16), dim3(256), 0, s->stream, s->d_blobs, s->d_ws, LB.d_state, LB.d_ctl, LB.d_rep, LB.d_reduced, o.initial_trust_region_radius, L.frame_x2, L.local_x2);
     const char* lprof = std::getenv("UVS_LARGE_PROF");      // debug: per-workgroup timeline of the LAST k_large_chunks launch, written to this file
     const KOpts ko = make_kopts(o, lprof ? 7 : 0);
-    const LargeCtl lc{L.d_ctl, L.rank, L.nranks};
+    const LargeCtl lc{LB.d_ctl, LB.rank, LB.nranks};
     RcclApi& r = rccl();
     const int passes = std::max(1, o.max_num_iterations);
     const int rows = L.grid;
     const int bgrid = std::min(L.n_chunks, UVS_LARGE_OCC * s->chunk_wgs());      // k_large_backsub runs UVS_LARGE_OCC workgroups per compute unit
-    HIPCHK(s, hipEventRecord(s->ev0, s->stream));
+    UVS_HIP(s->err, hipEventRecord(s->ev0, s->stream));
     for (int p = 0; p < passes; ++p) {
-        if (s->large_chunks_nt == 512) { if (uvs_k_large_chunks512_launch(L.grid + 1, s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), L.d_state, 0, 0, 0.0, L.d_partials, lc.ctl, lc.rank, lc.nranks, L.grid, L.d_fimg) != UVS_OK) return fused_abort(s, "k_large_chunks (512 threads): argument layout mismatch"); }
-        else hipLaunchKernelGGL(k_large_chunks, dim3(L.grid + 1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, 0, 0, 0.0, L.d_partials, lc, L.grid, L.d_fimg);
+        if (s->large_chunks_nt == 512) { if (uvs_k_large_chunks512_launch(L.grid + 1, s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), LB.d_state, 0, 0, 0.0, LB.d_partials, lc.ctl, lc.rank, lc.nranks, L.grid, LB.d_fimg) != UVS_OK) return fused_abort(s, "k_large_chunks (512 threads): argument layout mismatch"); }
+        else hipLaunchKernelGGL(k_large_chunks, dim3(L.grid + 1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, 0, 0, 0.0, LB.d_partials, lc, L.grid, LB.d_fimg);
         // (summing the partial rows inside k_large_solve instead of by a launch of its own was measured: one workgroup needs 15-24 us for what 314 do in 5)
-        { const int n_ent = s->hdrs[0].relo2 ? LG_ROW : LG_RED; hipLaunchKernelGGL(k_large_reduce, dim3((n_ent + 15) / 16), dim3(256), 0, s->stream, L.d_partials, rows, L.d_reduced, lc, n_ent); }
-        if (L.comm) { const int e = r.AllReduce(L.d_reduced, L.d_reduced, LG_XCH, kNcclDouble, kNcclSum, L.comm, s->stream); if (e != 0) return fused_abort(s, "ncclAllReduce(reduced) failed"); }
-        if (s->large_solve_nt == 512) { if (uvs_k_large_solve512_launch(s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), L.d_state, L.d_reduced, 0, 0.0, L.d_out, lc.ctl, lc.rank, lc.nranks, L.d_fimg) != UVS_OK) return fused_abort(s, "k_large_solve (512 threads): argument layout mismatch"); }
-        else hipLaunchKernelGGL(k_large_solve, dim3(1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, L.d_reduced, 0, 0.0, L.d_out, lc, L.d_fimg);
-        hipLaunchKernelGGL(k_large_backsub, dim3(bgrid + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, L.d_state, 0, L.d_bsums, lc, bgrid, L.d_out);
-        if (L.comm) {
-            hipLaunchKernelGGL(k_large_sum_bsums, dim3(1), dim3(256), 0, s->stream, L.d_bsums, L.n_chunks, L.d_sc5, lc, ko.max_ticks);
-            const int e = r.AllReduce(L.d_sc5, L.d_sc5, 8, kNcclDouble, kNcclSum, L.comm, s->stream); if (e != 0) return fused_abort(s, "ncclAllReduce(step scalars) failed");
-            hipLaunchKernelGGL(k_large_decide, dim3(1), dim3(256), 0, s->stream, L.d_ctl, L.d_state, L.d_out, L.d_sc5, L.d_reduced, ko, L.d_rep, (const double*)nullptr, 0);
-        } else hipLaunchKernelGGL(k_large_decide, dim3(1), dim3(256), 0, s->stream, L.d_ctl, L.d_state, L.d_out, L.d_sc5, L.d_reduced, ko, L.d_rep, (const double*)L.d_bsums, L.n_chunks);
+        { const int n_ent = s->hdrs[0].relo2 ? LG_ROW : LG_RED; hipLaunchKernelGGL(k_large_reduce, dim3((n_ent + 15) / 16), dim3(256), 0, s->stream, LB.d_partials, rows, LB.d_reduced, lc, n_ent); }
+        if (LB.comm) { const int e = r.AllReduce(LB.d_reduced, LB.d_reduced, LG_XCH, kNcclDouble, kNcclSum, LB.comm, s->stream); if (e != 0) return fused_abort(s, "ncclAllReduce(reduced) failed"); }
+        if (s->large_solve_nt == 512) { if (uvs_k_large_solve512_launch(s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), LB.d_state, LB.d_reduced, 0, 0.0, LB.d_out, lc.ctl, lc.rank, lc.nranks, LB.d_fimg) != UVS_OK) return fused_abort(s, "k_large_solve (512 threads): argument layout mismatch"); }
+        else hipLaunchKernelGGL(k_large_solve, dim3(1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, LB.d_reduced, 0, 0.0, LB.d_out, lc, LB.d_fimg);
+        hipLaunchKernelGGL(k_large_backsub, dim3(bgrid + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, 0, LB.d_bsums, lc, bgrid, LB.d_out);
+        if (LB.comm) {
+            hipLaunchKernelGGL(k_large_sum_bsums, dim3(1), dim3(256), 0, s->stream, LB.d_bsums, L.n_chunks, LB.d_sc5, lc, ko.max_ticks);
+            const int e = r.AllReduce(LB.d_sc5, LB.d_sc5, 8, kNcclDouble, kNcclSum, LB.comm, s->stream); if (e != 0) return fused_abort(s, "ncclAllReduce(step scalars) failed");
+            hipLaunchKernelGGL(k_large_decide, dim3(1), dim3(256), 0, s->stream, LB.d_ctl, LB.d_state, LB.d_out, LB.d_sc5, LB.d_reduced, ko, LB.d_rep, (const double*)nullptr, 0);
+        } else hipLaunchKernelGGL(k_large_decide, dim3(1), dim3(256), 0, s->stream, LB.d_ctl, LB.d_state, LB.d_out, LB.d_sc5, LB.d_reduced, ko, LB.d_rep, (const double*)LB.d_bsums, L.n_chunks);
     }
-    HIPCHK(s, hipEventRecord(s->ev1, s->stream));
-    hipLaunchKernelGGL(k_large_pack, dim3(16), dim3(256), 0, s->stream, s->d_blobs, s->d_ws, L.d_state, L.d_ctl, L.d_rep, s->d_outpack);
-    HIPCHK(s, hipGetLastError());
-    HIPCHK(s, hipMemcpyAsync(s->h_out, s->d_outpack, out_doubles * 8, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    if (loop_ms) HIPCHK(s, hipEventElapsedTime(loop_ms, s->ev0, s->ev1));
+    UVS_HIP(s->err, hipEventRecord(s->ev1, s->stream));
+    hipLaunchKernelGGL(k_large_pack, dim3(16), dim3(256), 0, s->stream, s->d_blobs, s->d_ws, LB.d_state, LB.d_ctl, LB.d_rep, s->d_outpack);
+    UVS_HIP(s->err, hipGetLastError());
+    UVS_HIP(s->err, hipMemcpyAsync(s->h_out, s->d_outpack, out_doubles * 8, hipMemcpyDeviceToHost, s->stream));
+    UVS_HIP(s->err, hipStreamSynchronize(s->stream));
+    if (loop_ms) UVS_HIP(s->err, hipEventElapsedTime(loop_ms, s->ev0, s->ev1));
     if (lprof) {
         std::vector<long long> tp(1024 * 8);
         if ((s->large_chunks_nt == 512 ? uvs_k_large_chunks512_prof(tp.data(), tp.size()) == UVS_OK : hipMemcpyFromSymbol(tp.data(), HIP_SYMBOL(g_large_prof), tp.size() * 8) == hipSuccess)) { if (FILE* f = std::fopen(lprof, "wb")) { const int hdr[2] = {L.grid + 1, L.n_chunks}; std::fwrite(hdr, 4, 2, f); std::fwrite(tp.data(), 8, tp.size(), f); std::fclose(f); } }
     }
-    const double* ho = (const double*)s->h_out;
+    const double* ho = (const double*)s->h_out.get();
     const double* ctl = ho;
     L.active = false;
     const bool unterminated = ctl[LC_DONE] == 0.0;      // cannot happen since k_large_decide tests the iteration cap on every branch; if it ever does, the caller still gets the last accepted state
