@@ -310,6 +310,17 @@ int uvs_evaluate(uvs_solver *s, const uvs_window *w, int robust, uvs_eval *out);
 int uvs_debug_first_iteration(uvs_solver *s, const uvs_window *w, double *S_lower, double *g, double *hd, double *dd,
                               double *step, double *scal);
 
+/* Diagnostic (step tests only): the damped LM step of the FIRST linearization of `w`, solved at radii[0] with the first iteration's Jacobi scaling
+ * and clamped Marquardt diagonal, then at radii[1], radii[2], ... each the way the selected kernels handle a rejected step.  form 0 = the persistent
+ * k_solve of the handle's instantiation (UVS_KSOLVE_NT), which re-damps its stored linearization; no other form is taken yet.  Per radius k:
+ * step[k * n_step ...] = the FULL unscaled tangent step as the kernels hold it (not recovered from the candidate state):
+ *   11 x 15 frame entries (dp, dtheta, dv, dba, dbg), 6 extrinsic entries if estimate_extrinsic, 1 td entry if estimate_td, 6 relo_Pose entries
+ *   if n_relo_obs > 0, n_points inverse depths, 4 n_lines line parameters -- n_step must be exactly that length;
+ * scal[k * UVS_DEBUG_SCAL_LEN ...] = {cost, gmax, chol_ok, model_cost_change, step_norm^2, 0...} as for uvs_debug_first_iteration.
+ * UVS_ERR_INVALID_ARG: null pointer, n_radii < 1, an unknown form, a radius that is not finite or <= 0, or n_step not matching the layout.
+ * Ordinary solves do not run this code: it is a separate instantiation of the kernel. */
+int uvs_debug_step(uvs_solver *s, const uvs_window *w, int form, int n_radii, const double *radii, int n_step, double *step, double *scal);
+
 /* Diagnostic, host only (no device is touched): packs `w` the way uvs_batch_upload() does and reports the layout:
  * info[12] = {blob bytes, workspace doubles, landmark chunks, packed point observations (incl. relocalization blocks), relocalization
  * blocks, doubles per point record, extra Schur slots per point landmark, LDS doubles of the fullest chunk, LDS staging capacity,
@@ -350,7 +361,12 @@ int uvs_marginalize_batch(uvs_solver *s, int n, const uvs_window *const *ws, con
  * every rank ends the solve at the same iteration).  Both are DEVICE pointers so that RCCL can reduce them in place.  On one GPU skip the all-reduces
  * or call uvs_large_solve().  Loop: begin; while (!done) { if (need_linearize) { linearize; allreduce(reduced) } step; allreduce(scalars); decide } finish.
  * Relocalization blocks (n_relo_obs > 0) are taken on ONE rank only: a landmark shard cannot tell from its own observations whether relo_Pose is a
- * free block of the window, so in a solve over several ranks no rank may pass them (uvs_large_solve_fused answers UVS_ERR_UNSUPPORTED). */
+ * free block of the window, so in a solve over several ranks no rank may pass them (uvs_large_solve_fused answers UVS_ERR_UNSUPPORTED).
+ * uvs_large_set_nranks(s, n) tells the step-wise form over how many ranks the caller all-reduces (default 1; UVS_ERR_INVALID_ARG for n < 1); with n > 1,
+ * uvs_large_begin answers UVS_ERR_UNSUPPORTED for a shard with n_relo_obs > 0, as the fused form does.  A rank whose shard holds none of them is not
+ * refused by its own call: the caller must spread the refusal to every rank before the first collective (api.py: Solver.large_solve).
+ * uvs_large_solve (one process) ignores the count and leaves it set. */
+int uvs_large_set_nranks(uvs_solver *s, int nranks);
 int uvs_large_begin(uvs_solver *s, const uvs_window *w);
 int uvs_large_need_linearize(const uvs_solver *s);
 int uvs_large_linearize(uvs_solver *s);

@@ -83,6 +83,28 @@ def test_shard_landmarks_partition():
     assert np.array_equal(s0.pt_pj[obs], w.pt_pj[gobs])
 
 
+def test_shard_landmarks_carries_relocalization_blocks():
+    """Every relocalization block goes to the rank that owns its landmark, remapped into the shard; the union is the window's."""
+    w = synth.add_relocalization(synth.make_window(54, n_points=80, n_lines=12, n_tagged=8), relo_frame=5, fraction=0.8, seed=4)
+    w = synth.add_time_offset(w, seed=4)
+    assert len(w.relo_lm) >= 8
+    world = 3
+    got = []
+    for r in range(world):
+        s, pk, lk = synth.shard_landmarks(w, r, world)
+        assert np.array_equal(s.relo_pose, w.relo_pose) and s.relo_frame == w.relo_frame
+        assert len(s.relo_lm) == len(s.relo_pi) == len(s.relo_pj)
+        assert np.all(np.diff(s.relo_lm) > 0) and np.all((s.relo_lm >= 0) & (s.relo_lm < len(s.inv_depth)))
+        assert np.all(np.isin(s.relo_lm, s.pt_lm))                                  # each keeps an ordinary observation in its shard (its anchor frame)
+        assert len(s.pt_vel_i) == len(s.pt_vel_j) == len(s.pt_td_i) == len(s.pt_td_j) == len(s.pt_lm)
+        for k in range(len(s.relo_lm)):
+            got.append((int(pk[s.relo_lm[k]]), tuple(s.relo_pi[k]), tuple(s.relo_pj[k])))
+        obs = np.nonzero(np.isin(w.pt_lm, pk))[0]
+        assert np.array_equal(s.pt_vel_j, w.pt_vel_j[obs]) and np.array_equal(s.pt_td_i, w.pt_td_i[obs])
+    want = [(int(w.relo_lm[k]), tuple(w.relo_pi[k]), tuple(w.relo_pj[k])) for k in range(len(w.relo_lm))]
+    assert sorted(got) == sorted(want)
+
+
 def _gpu_worker(rank, world, port, q):
     sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
     import importlib
@@ -236,3 +258,47 @@ def test_fused_loop_with_two_ranks_on_one_gpu(gpu_api, oracle, seed, shape):
     assert np.abs(inv_depth - st.inv_depth).max() < 1e-7 and np.abs(line_orth - st.line_orth.reshape(-1, 4)).max() < 1e-6
     dp, da = pose_deltas(res[0][1], so.pose)
     assert dp < 1e-6 and da < 1e-6 and abs(res[0][7] - ro.final_cost) <= 1e-7 * ro.final_cost
+
+
+def _gpu_relo_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import importlib
+    u = importlib.import_module("uv-slam_amd")
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.cuda.set_device(0)
+    out = []
+    for ex in (0, 1):
+        w = u.synth.add_relocalization(u.synth.make_window(55, n_points=120, n_lines=30, n_tagged=20), relo_frame=4, fraction=0.6, seed=5)
+        # every relocalization block on rank 0: rank 1's shard holds none, so its own uvs_large_begin accepts it
+        m = w.relo_lm % world == 0
+        w.relo_lm = w.relo_lm[m]; w.relo_pi = w.relo_pi[m]; w.relo_pj = w.relo_pj[m]
+        shard, pk, lk = u.synth.shard_landmarks(w, rank, world)
+        opts = u.abi.default_options(); opts.estimate_extrinsic = ex
+        s = u.api.Solver(opts=opts, device=0, max_batch=2)
+        try:
+            s.large_solve(shard, dist=dist, device="cuda:0")
+            out.append((ex, len(shard.relo_lm), "solved"))
+        except RuntimeError as e:
+            out.append((ex, len(shard.relo_lm), str(e)))
+        s.close()
+    q.put((rank, out))
+    dist.barrier(); dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+def test_two_ranks_refuse_relocalization_blocks(gpu_api):
+    """A landmark-sharded relocalization window over two ranks is refused on EVERY rank (the step-wise form, fixed and free extrinsic):
+    a shard cannot tell whether relo_Pose is free in the all-reduced system, and with a free extrinsic the relo2 tail is not exchanged."""
+    world = 2
+    ctx = mp.get_context("spawn"); q = ctx.Queue(); port = _free_port()
+    procs = [ctx.Process(target=_gpu_relo_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs: p.start()
+    res = sorted([q.get(timeout=300) for _ in range(world)], key=lambda r: r[0])
+    for p in procs: p.join(120)
+    assert all(p.exitcode == 0 for p in procs)
+    for rank, out in res:
+        assert [o[0] for o in out] == [0, 1]
+        for ex, n_relo, msg in out:
+            assert (n_relo > 0) == (rank == 0), (rank, ex, n_relo)
+            assert msg != "solved" and "uvs error 2" in msg, (rank, ex, msg)

@@ -58,8 +58,11 @@ def lib():
         L.uvs_marginalize_wait.argtypes = [C.c_void_p, C.POINTER(abi.Prior)]; L.uvs_marginalize_wait.restype = C.c_int
         L.uvs_debug_first_iteration.argtypes = [C.c_void_p, C.POINTER(abi.WindowC)] + [abi.c_double_p] * 6
         L.uvs_debug_first_iteration.restype = C.c_int
+        L.uvs_debug_step.argtypes = [C.c_void_p, C.POINTER(abi.WindowC), C.c_int, C.c_int, abi.c_double_p, C.c_int, abi.c_double_p, abi.c_double_p]
+        L.uvs_debug_step.restype = C.c_int
         L.uvs_reduced_dim.argtypes = [C.POINTER(abi.Options)]; L.uvs_reduced_dim.restype = C.c_int
         L.uvs_large_begin.argtypes = [C.c_void_p, C.POINTER(abi.WindowC)]; L.uvs_large_begin.restype = C.c_int
+        L.uvs_large_set_nranks.argtypes = [C.c_void_p, C.c_int]; L.uvs_large_set_nranks.restype = C.c_int
         for name in ("uvs_large_need_linearize", "uvs_large_linearize", "uvs_large_step", "uvs_large_decide", "uvs_large_done"):
             getattr(L, name).argtypes = [C.c_void_p]; getattr(L, name).restype = C.c_int
         L.uvs_large_reduced.argtypes = [C.c_void_p, C.POINTER(C.c_int)]; L.uvs_large_reduced.restype = C.c_void_p
@@ -198,11 +201,20 @@ class Solver:
         rep = abi.Report()
         L = lib()
         if dist is None:
+            self._check(L.uvs_large_set_nranks(self._h, 1))
             self._check(L.uvs_large_solve(self._h, C.byref(wc), C.byref(sc), C.byref(rep)), allow=(abi.UVS_OK, abi.UVS_ERR_NUMERIC))
             return st.from_c(sc), rep
         import torch
-        self._check(L.uvs_large_begin(self._h, C.byref(wc)))
         gpu_aware = dist.get_backend() == "nccl"          # RCCL reduces the solver's device buffers in place; otherwise stage through the host
+        self._check(L.uvs_large_set_nranks(self._h, dist.get_world_size()))
+        rc = L.uvs_large_begin(self._h, C.byref(wc))
+        # a rank whose shard holds no relocalization block is accepted by uvs_large_begin while another rank's is refused: every rank learns the worst
+        # code, so that all of them raise together instead of waiting in a collective for a peer that has left (on the backend's device: RCCL has no CPU tensors)
+        worst = torch.tensor([rc], dtype=torch.int64, device=device if gpu_aware else "cpu")
+        dist.all_reduce(worst, op=dist.ReduceOp.MAX)
+        self._check(rc)
+        if int(worst.item()) != abi.UVS_OK:
+            raise RuntimeError(f"uvs error {int(worst.item())}: {lib().uvs_status_string(int(worst.item())).decode()} / refused on another rank of the sharded solve")
         x2 = torch.tensor([L.uvs_large_local_x2(self._h)], dtype=torch.float64, device=device if gpu_aware else "cpu")
         dist.all_reduce(x2)
         L.uvs_large_set_landmark_x2(self._h, float(x2.item()))
@@ -315,6 +327,17 @@ class Solver:
         self._marg_keep = None
         self._check(rc)
         return p
+
+    def debug_step(self, w: abi.Window, radii, form=0):
+        """uvs_debug_step: the damped step of the first linearization of `w` at radii[0], then at each later radius the way `form` handles a
+        rejected step.  -> (step [n_radii, n_step] in the layout of include/uvs_solver.h, scal [n_radii, UVS_DEBUG_SCAL_LEN])."""
+        wc, keep = w.to_c()
+        o = self.opts
+        n_step = 165 + 6 * bool(o.estimate_extrinsic) + bool(o.estimate_td) + 6 * (len(w.relo_lm) > 0) + len(w.inv_depth) + 4 * len(w.line_orth)
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        step = np.zeros((len(r), n_step)); scal = np.zeros((len(r), 40))
+        self._check(lib().uvs_debug_step(self._h, C.byref(wc), int(form), len(r), abi._dp(r), n_step, abi._dp(step), abi._dp(scal)))
+        return step, scal
 
     def debug_first_iteration(self, w: abi.Window):
         wc, keep = w.to_c()

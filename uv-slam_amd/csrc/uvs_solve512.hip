@@ -27,6 +27,7 @@ int uvs_k_solve512_init(const unsigned char* fa, const unsigned char* fb, int n)
     if (n != UVS_NBLK) return UVS_ERR_INVALID_ARG;
     if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, n) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, n) != hipSuccess) return UVS_ERR_HIP;
     if (hipFuncSetAttribute((const void*)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
+    if (hipFuncSetAttribute((const void*)k_solve_dstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
     if (hipFuncSetAttribute((const void*)k_large_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
     if (hipFuncSetAttribute((const void*)k_large_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
     return UVS_OK;
@@ -49,7 +50,16 @@ int uvs_k_solve512_launch(int n_windows, hipStream_t stream, char* blobs, const 
     hipLaunchKernelGGL(k_solve, dim3(n_windows), dim3(NT), LDS_BYTES, stream, blobs, blob_off, ws_all, ws_off, ko, reports, d);
     return UVS_OK;
 }
-size_t uvs_k_solve512_arg_bytes(int which) { return which == 0 ? sizeof(KOpts) : sizeof(DebugOut); }
+size_t uvs_k_solve512_arg_bytes(int which) { return which == 0 ? sizeof(KOpts) : which == 1 ? sizeof(DebugOut) : sizeof(DebugStep); }
+// uvs_debug_step: the debug-step instantiation of the same kernel, window 0 of the uploaded batch
+int uvs_k_solve512_dstep_launch(hipStream_t stream, char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                                const void* kopts, size_t kopts_bytes, uvs_report* reports, const void* ds, size_t ds_bytes) {
+    KOpts ko; DebugStep d;
+    if (kopts_bytes != sizeof(ko) || ds_bytes != sizeof(d)) return UVS_ERR_INVALID_ARG;
+    __builtin_memcpy(&ko, kopts, sizeof(ko)); __builtin_memcpy(&d, ds, sizeof(d));
+    hipLaunchKernelGGL(k_solve_dstep, dim3(1), dim3(NT), LDS_BYTES, stream, blobs, blob_off, ws_all, ws_off, ko, reports, d);
+    return UVS_OK;
+}
 // k_large_solve with 512 threads (one workgroup): the frame image arrives with twice the loads in flight, the factorization has six workers and the pivot chain its SIMD alone
 int uvs_k_large_solve512_launch(hipStream_t stream, char* blob, double* ws, const void* kopts, size_t kopts_bytes, double* state, const double* reduced, int first, double radius, double* out,
                                 const double* ctl, int rank, int nranks, const double* fimg) {

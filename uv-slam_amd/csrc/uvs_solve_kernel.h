@@ -2536,8 +2536,9 @@ UVS_DEV void relinearize_damping(const Ctx& c, const double* x, double radius, G
 #define UVS_BS_FRAME_LANE0 192
 #endif
 template <int LNBT = BS_LNB, int PSB = 4, bool STREAM = false>
+// lstep (uvs_debug_step only; nullptr, i.e. no code, everywhere else): the landmark steps themselves, [points | 4 x lines]
 UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* line, double* invd_c, double* line_c,
-                                  int pk0, int pk1, int lk0, int lk1, bool with_frames, double* sums_out) {
+                                  int pk0, int pk1, int lk0, int lk1, bool with_frames, double* sums_out, double* lstep = nullptr) {
     const DevWin& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
@@ -2630,6 +2631,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
         const double dl = -px0 - t;
         const double v = iv0 + dl;
         invd_c[k] = v;
+        if (lstep) lstep[k] = dl;
         // L_G holds the Schur-REDUCED frame gradient g_f - E^T h^-1 g_l; (E delta_f) h^-1 g_l = t * g_l restores the full g_f . delta_f
         gd += px1 * (dl + t); dd2 += px2 * dl * dl; step2 += dl * dl; xc2 += v * v;
     }
@@ -2667,6 +2669,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
             const double dl = -(STREAM ? lxq : lx[q]) - t;
             const double v = (STREAM ? ln0 : line[4 * k + q]) + dl;
             line_c[4 * k + q] = v;
+            if (lstep) lstep[h.n_points + 4 * k + q] = dl;
             gd += (STREAM ? lx4 : lx[4 + q]) * (dl + t); dd2 += (STREAM ? lx8 : lx[8 + q]) * dl * dl; step2 += dl * dl; xc2 += v * v;
             if (ltrig_c) sincos(v, ltrig_c + 8 * k + 2 * q, ltrig_c + 8 * k + 2 * q + 1);
         }
@@ -2701,6 +2704,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
             const double dl = -lx[q] - t[q];
             const double v = line[4 * k + q] + dl;
             line_c[4 * k + q] = v; vn[q] = v;
+            if (lstep) lstep[h.n_points + 4 * k + q] = dl;
             gd += lx[4 + q] * (dl + t[q]); dd2 += lx[8 + q] * dl * dl; step2 += dl * dl; xc2 += v * v;
         }
         if (ltrig_c) line_trig(vn, ltrig_c + 8 * k);      // sin/cos of the candidate parameters, once per line instead of once per observation
@@ -2888,9 +2892,21 @@ struct DebugOut {   // optional dump of the first linearization (uvs_debug_linea
     double* scal;   // [UVS_DEBUG_SCAL_LEN]: cost, gmax, chol_ok, mcc, step2, -, -, -, phase cycles [8..23], sub-timers [24..31]
 };
 
-__global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
-                                              KOpts o, uvs_report* reports, DebugOut dbg) {
-    extern __shared__ __attribute__((aligned(16))) double sh[];
+// uvs_debug_step: the step of every LM iteration of window 0 is stored and then handled as a REJECTED one at the caller's next radius (k_solve re-damps
+// its stored linearization), so that one launch solves the damped system of the first linearization at radii[0], radii[1], ...  Only the k_solve_dstep
+// instantiation of the body below carries this code.
+#define UVS_DSTEP_FR (UVS_RD + 24)      // frame part of a stored step: the whole L_DLT (padded frame dofs, td / extrinsic slots, relo_Pose at [192..197])
+struct DebugStep {
+    const double* radii;       // [n]; radii[0] is KOpts::r0
+    int n;
+    long long stride;          // doubles per radius in steps: UVS_DSTEP_FR + n_points + 4 n_lines
+    double* steps;             // [n][stride]: L_DLT | point steps | line steps (the back-substitution's own values, unscaled tangent)
+    double* scal;              // [n][UVS_DEBUG_SCAL_LEN]: cost, gmax, chol_ok, model_cost_change, step_norm^2
+};
+
+template <bool DSTEP>
+UVS_DEV void k_solve_body(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                          KOpts o, uvs_report* reports, DebugOut dbg, DebugStep ds, double* sh) {
     const int tid = lane_tid(), wdx = blockIdx.x;
     char* blob = blobs + blob_off[wdx];
     Ctx c;
@@ -2975,10 +2991,19 @@ __global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob
         UVS_PROF(c, P_TRSV);
         UVS_TLOG(c, 32);
         bool ok = sh[L_CTRL + C_CHOLOK] != 0.0;
-        backsub_candidate(c, invd[cur], line[cur], invd[cur ^ 1], line[cur ^ 1], 0, h.n_points, 0, h.n_lines, true, nullptr);
+        backsub_candidate(c, invd[cur], line[cur], invd[cur ^ 1], line[cur ^ 1], 0, h.n_points, 0, h.n_lines, true, nullptr,
+                          DSTEP ? ds.steps + (size_t)(it - 1) * ds.stride + UVS_DSTEP_FR : nullptr);
         UVS_PROF(c, P_BACKSUB);
         UVS_TLOG(c, 33);
         const double mcc = sh[L_CTRL + C_MCC], step2 = sh[L_CTRL + C_STEP2], xc2 = sh[L_CTRL + C_XC2];
+        if (DSTEP) {
+            if (tid < UVS_DSTEP_FR) ds.steps[(size_t)(it - 1) * ds.stride + tid] = sh[L_DLT + tid];
+            if (tid == 0) { double* sc = ds.scal + (size_t)(it - 1) * UVS_DEBUG_SCAL_LEN; sc[0] = cost; sc[1] = gmax; sc[2] = ok ? 1.0 : 0.0; sc[3] = mcc; sc[4] = step2; }
+            if (it >= ds.n) break;
+            radius = ds.radii[it]; need_lin = true; prep_mode = 2;      // HandleUnsuccessfulStep with the caller's radius
+            __syncthreads();
+            continue;
+        }
         if (o.debug && it == 1 && dbg.S) {
             if (tid < UVS_RD) dbg.step[tid] = sh[L_DLT + tid];
             if (tid == 0) { dbg.scal[0] = cost; dbg.scal[1] = gmax; dbg.scal[2] = ok ? 1.0 : 0.0; dbg.scal[3] = mcc; dbg.scal[4] = step2; }
@@ -3056,6 +3081,23 @@ __global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob
         ((DevWin*)blob)->cur_sel = cur;
     }
 }
+#ifndef UVS_DSTEP_ONLY
+__global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                                              KOpts o, uvs_report* reports, DebugOut dbg) {
+    extern __shared__ __attribute__((aligned(16))) double sh[];
+    k_solve_body<false>(blobs, blob_off, ws_all, ws_off, o, reports, dbg, DebugStep{}, sh);
+}
+#endif
+// (not beside the 256-thread k_solve of uvs_solver.hip: the two kernels share the noinline factorization calls, and a second caller moves the product kernel's
+// register figures; uvs_solve_dstep256.hip instantiates it alone)
+#ifndef UVS_NO_DSTEP
+__global__ __launch_bounds__(NT) void k_solve_dstep(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                                                    KOpts o, uvs_report* reports, DebugStep ds) {
+    extern __shared__ __attribute__((aligned(16))) double sh[];
+    DebugOut dbg; dbg.S = nullptr; dbg.g = nullptr; dbg.hd = nullptr; dbg.dd = nullptr; dbg.step = nullptr; dbg.scal = nullptr;
+    k_solve_body<true>(blobs, blob_off, ws_all, ws_off, o, reports, dbg, ds, sh);
+}
+#endif
 
 #ifndef UVS_SOLVE_KERNEL_ONLY      // (uvs_solve512.hip instantiates k_solve alone)
 // ------------------------------------------------------------------ marginalization on the device (MARGIN_OLD)

@@ -30,6 +30,7 @@
 #include "uvs_hip_buf.h"
 #include "uvs_layout.h"
 #include "uvs_factors.h"
+#define UVS_NO_DSTEP 1      // (the 256-thread k_solve_dstep is its own translation unit: uvs_solve_dstep256.hip)
 #include "uvs_solve_kernel.h"
 #include "uvs_eval_kernel.h"
 #include "uvs_large_kernel.h"
@@ -44,6 +45,11 @@ int uvs_k_solve512_init(const unsigned char* fa, const unsigned char* fb, int n)
 int uvs_k_solve512_launch(int n_windows, hipStream_t stream, char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
                            const void* kopts, size_t kopts_bytes, uvs_report* reports, const void* dbg, size_t dbg_bytes);
 size_t uvs_k_solve512_arg_bytes(int which);
+int uvs_k_solve512_dstep_launch(hipStream_t stream, char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                                const void* kopts, size_t kopts_bytes, uvs_report* reports, const void* ds, size_t ds_bytes);
+int uvs_k_solve256d_init(const unsigned char* fa, const unsigned char* fb, int n);
+int uvs_k_solve256d_launch(hipStream_t stream, char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
+                           const void* kopts, size_t kopts_bytes, uvs_report* reports, const void* ds, size_t ds_bytes);
 int uvs_k_solve512_timeline(long long* out, size_t n);
 int uvs_k_large_chunks512_prof(long long* out, size_t n);
 int uvs_k_large_solve512_launch(hipStream_t stream, char* blob, double* ws, const void* kopts, size_t kopts_bytes, double* state, const double* reduced, int first, double radius, double* out,
@@ -169,6 +175,7 @@ struct uvs_solver {
         DevBuf<double> d_ctl; DevBuf<uvs_report> d_rep;         // fused loop: trust-region state and report on the device
         DevBuf<double> d_fimg;                                  // frame image of the reduced system (k_large_chunks' extra workgroup -> k_large_solve)
         void* comm = nullptr; int rank = 0, nranks = 1;         // RCCL communicator owned by the handle (uvs_large_comm_init)
+        int step_nranks = 1;                                    // ranks the caller all-reduces the step-wise form over (uvs_large_set_nranks)
     } LB;
     ~uvs_solver();
 };
@@ -259,7 +266,8 @@ int uvs_create(const uvs_options* opts, int device, int max_batch, int max_point
     unsigned char fa[UVS_NBLK], fb[UVS_NBLK];
     for (int i = 0, b = 0; i < UVS_NF; ++i) for (int j = 0; j <= i; ++j, ++b) { fa[b] = (unsigned char)i; fb[b] = (unsigned char)j; }
     if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, sizeof(fa)) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, sizeof(fb)) != hipSuccess) { uvs_destroy(s); return UVS_ERR_HIP; }
-    if (uvs_k_solve512_arg_bytes(0) != sizeof(KOpts) || uvs_k_solve512_arg_bytes(1) != sizeof(DebugOut) || uvs_k_solve512_init(fa, fb, UVS_NBLK) != UVS_OK) { uvs_destroy(s); return UVS_ERR_HIP; }
+    if (uvs_k_solve512_arg_bytes(0) != sizeof(KOpts) || uvs_k_solve512_arg_bytes(1) != sizeof(DebugOut) || uvs_k_solve512_arg_bytes(2) != sizeof(DebugStep) || uvs_k_solve512_init(fa, fb, UVS_NBLK) != UVS_OK ||
+        uvs_k_solve256d_init(fa, fb, UVS_NBLK) != UVS_OK) { uvs_destroy(s); return UVS_ERR_HIP; }
     { const char* e = std::getenv("UVS_KSOLVE_NT"); s->ksolve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
     { const char* e = std::getenv("UVS_LARGE_CHUNKS_NT"); s->large_chunks_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
     { const char* e = std::getenv("UVS_LARGE_SOLVE_NT"); s->large_solve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }      // A/B switch: 256 = the one-wave-per-SIMD instantiation of the persistent kernel
@@ -1453,6 +1461,52 @@ int uvs_debug_first_iteration(uvs_solver* s, const uvs_window* w, double* S_lowe
     return UVS_OK;
 }
 
+// Diagnostic entry (step tests): the damped step of the first linearization of `w` at radii[0], then at radii[1], ... each the way `form` handles a
+// rejected step (form 0, k_solve: re-damping of the stored linearization).  step[k * n_step ...] = unscaled tangent step in the layout of include/uvs_solver.h, scal[k * UVS_DEBUG_SCAL_LEN ...] its scalars.
+int uvs_debug_step(uvs_solver* s, const uvs_window* w, int form, int n_radii, const double* radii, int n_step, double* step, double* scal) {
+    if (!s || !w || !radii || !step || !scal || n_radii < 1 || form != 0) { if (s) s->err = "uvs_debug_step: bad argument"; return UVS_ERR_INVALID_ARG; }
+    for (int k = 0; k < n_radii; ++k) if (!std::isfinite(radii[k]) || !(radii[k] > 0.0)) { s->err = "uvs_debug_step: a radius that is not finite or <= 0"; return UVS_ERR_INVALID_ARG; }
+    if (w->n_points < 0 || w->n_lines < 0) { s->err = "uvs_debug_step: negative landmark count"; return UVS_ERR_INVALID_ARG; }
+    const uvs_options& o = s->opts;
+    const int ex = o.estimate_extrinsic ? 1 : 0, td = o.estimate_td ? 1 : 0, relo = w->n_relo_obs > 0 ? 1 : 0;
+    const long long n_fr = 165 + 6 * ex + td + 6 * relo;
+    if ((long long)n_step != n_fr + w->n_points + 4LL * w->n_lines) { s->err = "uvs_debug_step: step length does not match the layout"; return UVS_ERR_INVALID_ARG; }
+    const long long stride = UVS_DSTEP_FR + (long long)w->n_points + 4LL * w->n_lines;
+    std::vector<double> raw((size_t)(stride * n_radii)), rsc((size_t)UVS_DEBUG_SCAL_LEN * n_radii, 0.0);
+    int rc = UVS_OK;
+    {
+        const uvs_window* arr[1] = {w};
+        if ((rc = uvs_batch_upload(s, 1, arr)) != UVS_OK) return rc;
+        UVS_HIP(s->err, hipSetDevice(s->device));
+        const size_t need = sizeof(double) * ((size_t)n_radii + (size_t)(stride * n_radii) + (size_t)UVS_DEBUG_SCAL_LEN * n_radii);
+        if ((rc = s->d_dbg.ensure(need, s->err)) != UVS_OK) return rc;
+        double* d_radii = s->d_dbg; double* d_steps = d_radii + n_radii; double* d_scal = d_steps + stride * n_radii;
+        UVS_HIP(s->err, hipMemcpy(d_radii, radii, sizeof(double) * n_radii, hipMemcpyHostToDevice));
+        UVS_HIP(s->err, hipMemset(d_steps, 0, sizeof(double) * (size_t)(stride * n_radii + (long long)UVS_DEBUG_SCAL_LEN * n_radii)));
+        KOpts ko = make_kopts(o, 0);
+        ko.r0 = radii[0]; ko.max_it = n_radii; ko.gtol = -1.0; ko.rmin = 0.0; ko.max_ticks = 0; ko.max_invalid = n_radii + 1;      // nothing ends the loop before the last radius
+        DebugStep ds; ds.radii = d_radii; ds.n = n_radii; ds.stride = stride; ds.steps = d_steps; ds.scal = d_scal;
+        if (s->ksolve_nt == 512) { if (uvs_k_solve512_dstep_launch(s->stream, s->d_blobs, s->d_blob_off, s->d_ws, s->d_ws_off, &ko, sizeof(ko), s->d_reports, &ds, sizeof(ds)) != UVS_OK) { s->err = "k_solve_dstep (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
+        else if (uvs_k_solve256d_launch(s->stream, s->d_blobs, s->d_blob_off, s->d_ws, s->d_ws_off, &ko, sizeof(ko), s->d_reports, &ds, sizeof(ds)) != UVS_OK) { s->err = "k_solve_dstep (256 threads): argument layout mismatch"; return UVS_ERR_HIP; }
+        UVS_HIP(s->err, hipGetLastError());
+        UVS_HIP(s->err, hipStreamSynchronize(s->stream));
+        UVS_HIP(s->err, hipMemcpy(raw.data(), d_steps, sizeof(double) * raw.size(), hipMemcpyDeviceToHost));
+        UVS_HIP(s->err, hipMemcpy(rsc.data(), d_scal, sizeof(double) * rsc.size(), hipMemcpyDeviceToHost));
+    }
+    // padded device layout -> the ABI's: frames (16 f + dof, dof < 15), extrinsic, td, relo_Pose, landmarks
+    for (int k = 0; k < n_radii; ++k) {
+        const double* r = raw.data() + (size_t)k * stride; double* d = step + (size_t)k * n_step;
+        long long j = 0;
+        for (int f = 0; f < UVS_NF; ++f) for (int a = 0; a < 15; ++a) d[j++] = r[16 * f + a];
+        if (ex) for (int a = 0; a < 6; ++a) d[j++] = r[UVS_EX_INDEX(a)];
+        if (td) d[j++] = r[UVS_TD_INDEX];
+        if (relo) for (int a = 0; a < 6; ++a) d[j++] = r[16 * UVS_RELO_FRAME + a];
+        std::memcpy(d + j, r + UVS_DSTEP_FR, sizeof(double) * (size_t)(stride - UVS_DSTEP_FR));
+        std::memcpy(scal + (size_t)k * UVS_DEBUG_SCAL_LEN, rsc.data() + (size_t)k * UVS_DEBUG_SCAL_LEN, sizeof(double) * UVS_DEBUG_SCAL_LEN);
+    }
+    return UVS_OK;
+}
+
 int uvs_evaluate(uvs_solver* s, const uvs_window* w, int robust, uvs_eval* out) {
     if (!s || !w || !out) return UVS_ERR_INVALID_ARG;
     const uvs_window* arr[1] = {w};
@@ -1799,8 +1853,17 @@ static int large_prologue(uvs_solver* s, const uvs_window* w) {
 //                             -> [all-reduce SUM of uvs_large_scalars()] -> uvs_large_decide } -> uvs_large_finish
 extern "C" {
 
+int uvs_large_set_nranks(uvs_solver* s, int nranks) {
+    if (!s || nranks < 1) return UVS_ERR_INVALID_ARG;
+    s->LB.step_nranks = nranks;
+    return UVS_OK;
+}
+
 int uvs_large_begin(uvs_solver* s, const uvs_window* w) {
     if (!s || !w) return UVS_ERR_INVALID_ARG;
+    // the fused form's rule (uvs_large_solve_fused): a shard cannot tell whether relo_Pose is a free block of the all-reduced system, and the relo2 tail of the
+    // reduced vector is not exchanged
+    if (s->LB.step_nranks > 1 && w->n_relo_obs > 0) { s->L.active = false; s->err = "relocalization blocks are not taken by a landmark-sharded solve over several ranks"; return UVS_ERR_UNSUPPORTED; }
     const uvs_window* arr[1] = {w};
     int rc = upload_windows(s, 1, arr, true, s->chunk_wgs());
     if (rc != UVS_OK) return rc;
@@ -1947,7 +2010,11 @@ int uvs_large_finish(uvs_solver* s, uvs_state* out, uvs_report* rep) {
 
 // single-GPU convenience: the loop above with nothing to all-reduce; elapsed_ms (may be NULL) = wall time of the loop
 int uvs_large_solve(uvs_solver* s, const uvs_window* w, uvs_state* out, uvs_report* rep) {
+    if (!s) return UVS_ERR_INVALID_ARG;
+    // one process, nothing exchanged: the rank count of the step-wise form (uvs_large_set_nranks) does not apply, and stays set for the next step-wise solve
+    const int nr = s->LB.step_nranks; s->LB.step_nranks = 1;
     int rc = uvs_large_begin(s, w);
+    s->LB.step_nranks = nr;
     if (rc != UVS_OK) return rc;
     while (!uvs_large_done(s)) {
         if (uvs_large_need_linearize(s)) { if ((rc = uvs_large_linearize(s)) != UVS_OK) return rc; }

@@ -391,7 +391,9 @@ def algorithmic_bytes(w: abi.Window):
 
 
 def shard_landmarks(w: abi.Window, rank: int, world: int):
-    """Sub-window holding the landmarks k with k % world == rank (frames / IMU / prior replicated) -- SURVEY.md section 8e."""
+    """Sub-window holding the landmarks k with k % world == rank (frames / IMU / prior replicated) -- SURVEY.md section 8e.
+    Per-observation arrays (the ProjectionTdFactor inputs among them) follow their observations; a relocalization block goes to the
+    rank that owns its landmark, with the landmark index remapped into the shard (relo_pose / relo_frame are replicated)."""
     o = w.copy()
     pk = np.arange(len(w.inv_depth)) % world == rank
     lk = np.arange(len(w.line_orth)) % world == rank
@@ -400,8 +402,13 @@ def shard_landmarks(w: abi.Window, rank: int, world: int):
     lo = lk[w.ln_lm] if len(w.ln_lm) else np.zeros(0, bool)
     o.inv_depth = w.inv_depth[pk]; o.line_orth = w.line_orth[lk]
     o.pt_lm = pmap[w.pt_lm[po]].astype(np.int32); o.pt_fi = w.pt_fi[po]; o.pt_fj = w.pt_fj[po]; o.pt_pi = w.pt_pi[po]; o.pt_pj = w.pt_pj[po]
+    for name in ("pt_vel_i", "pt_vel_j", "pt_td_i", "pt_td_j"):
+        if getattr(w, name) is not None:
+            setattr(o, name, getattr(w, name)[po])
     o.ln_lm = lmap[w.ln_lm[lo]].astype(np.int32); o.ln_fj = w.ln_fj[lo]; o.ln_sp = w.ln_sp[lo]; o.ln_ep = w.ln_ep[lo]
     o.ln_has_vp = w.ln_has_vp[lo]; o.ln_vp = w.ln_vp[lo]
+    ro = pk[w.relo_lm] if len(w.relo_lm) else np.zeros(0, bool)
+    o.relo_lm = pmap[w.relo_lm[ro]].astype(np.int32); o.relo_pi = w.relo_pi[ro]; o.relo_pj = w.relo_pj[ro]
     return o, np.nonzero(pk)[0], np.nonzero(lk)[0]
 
 
