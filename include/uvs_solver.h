@@ -312,13 +312,17 @@ int uvs_debug_first_iteration(uvs_solver *s, const uvs_window *w, double *S_lowe
 
 /* Diagnostic (step tests only): the damped LM step of the FIRST linearization of `w`, solved at radii[0] with the first iteration's Jacobi scaling
  * and clamped Marquardt diagonal, then at radii[1], radii[2], ... each the way the selected kernels handle a rejected step.  form 0 = the persistent
- * k_solve of the handle's instantiation (UVS_KSOLVE_NT), which re-damps its stored linearization; no other form is taken yet.  Per radius k:
+ * k_solve of the handle's instantiation (UVS_KSOLVE_NT), which re-damps its stored linearization.  form 1 = the landmark-sharded kernels
+ * (k_large_chunks -> k_large_reduce -> k_large_solve -> k_large_backsub of the handle's instantiations, UVS_LARGE_CHUNKS_NT / UVS_LARGE_SOLVE_NT) through the
+ * step-wise calls below, which re-linearize at the same state with the new radius (uvs_large_decide keeps no linearization to re-damp); the landmark part
+ * and the frame part (relo_Pose included) are what k_large_backsub itself holds, the scalars are formed by the code uvs_large_decide uses.  Per radius k:
  * step[k * n_step ...] = the FULL unscaled tangent step as the kernels hold it (not recovered from the candidate state):
  *   11 x 15 frame entries (dp, dtheta, dv, dba, dbg), 6 extrinsic entries if estimate_extrinsic, 1 td entry if estimate_td, 6 relo_Pose entries
  *   if n_relo_obs > 0, n_points inverse depths, 4 n_lines line parameters -- n_step must be exactly that length;
  * scal[k * UVS_DEBUG_SCAL_LEN ...] = {cost, gmax, chol_ok, model_cost_change, step_norm^2, 0...} as for uvs_debug_first_iteration.
  * UVS_ERR_INVALID_ARG: null pointer, n_radii < 1, an unknown form, a radius that is not finite or <= 0, or n_step not matching the layout.
- * Ordinary solves do not run this code: it is a separate instantiation of the kernel. */
+ * UVS_ERR_UNSUPPORTED (form 1): relocalization blocks while uvs_large_set_nranks announced more than one rank, as uvs_large_begin.
+ * Ordinary solves do not run this code: it is a separate instantiation of the kernel (k_solve_dstep, k_large_backsub_dstep). */
 int uvs_debug_step(uvs_solver *s, const uvs_window *w, int form, int n_radii, const double *radii, int n_step, double *step, double *scal);
 
 /* Diagnostic, host only (no device is touched): packs `w` the way uvs_batch_upload() does and reports the layout:
@@ -380,6 +384,24 @@ double uvs_large_local_x2(const uvs_solver *s);
 void uvs_large_set_landmark_x2(uvs_solver *s, double all_ranks_x2);
 int uvs_large_finish(uvs_solver *s, uvs_state *out, uvs_report *rep);
 int uvs_large_solve(uvs_solver *s, const uvs_window *w, uvs_state *out, uvs_report *rep);
+
+/* Diagnostic (step tests only): the step of a SHARD of the step-wise form, so that a test can drive several handles in one process and sum their
+ * exchange vectors on the host.  uvs_large_set_debug_step(s, 1) makes every later uvs_large_step of the handle (uvs_debug_step form 1 does the same for
+ * its own duration) run the storing instantiation of k_large_backsub; ordinary calls (flag 0, the default) run the product kernel and pay nothing.
+ * uvs_large_debug_step(), called after uvs_large_step and after the caller has summed uvs_large_scalars() over the ranks, returns step[n_step] = the
+ * unscaled tangent step of THIS shard's window in the layout of uvs_debug_step (frames, extrinsic, td, relo_Pose, the shard's own inverse depths and
+ * lines in the shard's numbering) and scal[UVS_DEBUG_SCAL_LEN] = {cost, gmax, chol_ok, model_cost_change, step_norm^2, landmark chunks, chunk
+ * workgroups of k_large_chunks (= partial rows of k_large_reduce), chunk workgroups of k_large_backsub, 0...} from the exchanged scalars and the
+ * launches of this step (uvs_debug_step form 1 returns the same three figures).  next_radius > 0 then handles the step as a REJECTED one at that radius (re-linearization at the same state: need_linearize becomes 1) in
+ * place of uvs_large_decide; next_radius == 0 leaves the run state alone.  UVS_ERR_INVALID_ARG: no step-wise solve in progress, the flag not set
+ * before the last uvs_large_step (a step stored by an earlier solve is never handed out), n_step not matching the layout, a next radius that is
+ * negative or not finite.
+ * UVS_DEBUG_LARGE_GRID=<n> in the environment of uvs_create (step tests only; unset in production) caps the chunk workgroups of the handle's
+ * large-window kernels at n (never above compute units - 1), so that a window of a thousand landmarks walks the persistent loops that only a
+ * configs[3] window reaches on the full grid: the packing asks for a multiple of n chunks, k_large_chunks runs n workgroups, k_large_backsub 2 n.
+ * It is the device-side twin of UVS_DEBUG_CHUNK_GRID, which sets the same grid for the host-only uvs_debug_pack_layout. */
+int uvs_large_set_debug_step(uvs_solver *s, int on);
+int uvs_large_debug_step(uvs_solver *s, double next_radius, int n_step, double *step, double *scal);
 
 /* ---- fused multi-GPU loop: the library owns the RCCL communicator (SURVEY.md 8b "library owns ... RCCL comm") and keeps the
  * trust-region control on the device, so that one solve is one stream of launches with two in-place all-reduces per iteration and no

@@ -6,13 +6,109 @@ from helpers import abi, synth
 
 NAMES = ["prior_free", "prior", "prior_extrinsic", "full_rows", "points_only", "lines_only", "small", "tracks2", "tracks10", "ragged",
          "skipped_imu", "td", "extrinsic", "no_jacobi"]
-PRIOR_CASES = ("prior", "prior_extrinsic", "full_rows")
+PRIOR_CASES = ("prior", "prior_extrinsic", "full_rows", "relo_prior")
+# relocalization blocks (estimator.cpp:944-978): name -> (relo_frame, fraction of the eligible landmarks re-observed).  Fixed extrinsic: relo_Pose sits in
+# the spare rows of the reduced system; free extrinsic: second-level elimination (relo2_eliminate; block row 13 travels as the tail of the partial rows)
+RELO = {"relo": (4, 0.6), "relo_first": (0, 1.0), "relo_prior": (9, 0.2), "relo_extrinsic": (9, 1.0), "relo_extrinsic_td": (5, 0.2)}
+RELO_NAMES = list(RELO)
+# 1 000 points with ten-frame tracks + 300 lines, every point matched in the relocalization frame, free extrinsic (the window of
+# test_relo.py::test_relo_blocks_with_a_free_extrinsic_on_a_large_window): 203 chunks on the 255-workgroup grid of an MI355X, one per workgroup, the relo2 tail
+# summed over all of them.  many_chunks_grid20 is the same window on TWENTY chunk workgroups (UVS_DEBUG_LARGE_GRID): 60 chunks, three per persistent
+# workgroup of k_large_chunks, twenty partial rows through both levels of k_large_reduce, two chunks per workgroup in half of k_large_backsub's grid.
+# many_chunks_plain: the window without its relocalization blocks (the two-shard runs).
+BIG_NAMES = ["many_chunks_mid", "many_chunks_grid20"]
+EXTRA_NAMES = ["prior_td", "weak"]      # a prior with a TD block (n = 76); landmarks that the damping alone holds up
+
+
+def oracle_marginalize(oracle, name):
+    """The oracle's marginalization as `marginalize_fn` of build(): prior_td marginalizes under the case's own options (the td block is a kept block of the prior)."""
+    return (lambda w, flag: oracle.marginalize(w, flag, opts=options(name))) if name == "prior_td" else oracle.marginalize
+
+
+WEAK_POINTS, WEAK_FAR, WEAK_LINES = 12, 6, 6
+
+
+def _weak(w):
+    """Landmarks that the damping alone holds up.  Points 0..11: ONE observation, in the frame after the anchor, of a point that lies (up to a relative offset
+    eps = 1e-2 .. 1e-5) on the line through the two camera centres -- the epipole, no parallax, J_lambda ~ eps.  Points 12..17: their whole track, of a
+    point 1 .. 100 km away (inverse depth 1e-3 .. 1e-5).  Lines 0..5: two observations from consecutive frames.  Everything exact at the window's truth."""
+    o = w.copy(); t = o.truth
+    first = np.nonzero(np.r_[True, o.pt_lm[1:] != o.pt_lm[:-1]])[0]
+    keep = np.ones(len(o.pt_lm), bool)
+    o.pt_pi = o.pt_pi.copy(); o.pt_pj = o.pt_pj.copy(); o.pt_fj = o.pt_fj.copy(); o.inv_depth = o.inv_depth.copy()
+    t = dict(t); t["inv_depth"] = t["inv_depth"].copy(); o.truth = t
+    done = 0
+    for lm in range(len(o.inv_depth)):
+        if done == WEAK_POINTS: break
+        k = first[lm]; fi = int(o.pt_fi[k])
+        if fi + 1 >= abi.NUM_FRAMES: continue
+        Ri, ti = synth._cam(t["pose"][fi, :3], t["pose"][fi, 3:], o.ex_pose); Rj, tj = synth._cam(t["pose"][fi + 1, :3], t["pose"][fi + 1, 3:], o.ex_pose)
+        d = (tj - ti) / np.linalg.norm(tj - ti)
+        perp = np.cross(d, [0.3, -0.5, 0.8]); perp /= np.linalg.norm(perp)
+        eps = 10.0 ** -(2 + 3 * done / (WEAK_POINTS - 1))
+        for sign in (1.0, -1.0):
+            X = ti + sign * 6.0 * (d + eps * perp)
+            ci, cj = Ri.T @ (X - ti), Rj.T @ (X - tj)
+            if ci[2] > 0.5 and cj[2] > 0.5: break
+        else: continue
+        keep[o.pt_lm == lm] = False; keep[k] = True
+        o.pt_fj[k] = fi + 1; o.pt_pi[k] = ci / ci[2]; o.pt_pj[k] = cj / cj[2]
+        t["inv_depth"][lm] = 1.0 / ci[2]; o.inv_depth[lm] = (1.0 + 1e-3) / ci[2]
+        done += 1
+    assert done == WEAK_POINTS
+    far = [lm for lm in range(len(o.inv_depth)) if lm not in set(o.pt_lm[~keep].tolist())][:WEAK_FAR]
+    for n, lm in enumerate(far):
+        rows = np.nonzero(o.pt_lm == lm)[0]; fi = int(o.pt_fi[rows[0]])
+        Ri, ti = synth._cam(t["pose"][fi, :3], t["pose"][fi, 3:], o.ex_pose)
+        lam = 10.0 ** -(3 + 2 * n / (WEAK_FAR - 1))
+        X = Ri @ (o.pt_pi[rows[0]] / lam) + ti
+        for k in rows:
+            fj = int(o.pt_fj[k]); Rj, tj = synth._cam(t["pose"][fj, :3], t["pose"][fj, 3:], o.ex_pose)
+            c = Rj.T @ (X - tj); o.pt_pj[k] = c / c[2]
+        t["inv_depth"][lm] = lam; o.inv_depth[lm] = lam * (1.0 + 1e-3)
+    for nm in ("pt_lm", "pt_fi", "pt_fj", "pt_pi", "pt_pj"): setattr(o, nm, getattr(o, nm)[keep])
+    keep = np.ones(len(o.ln_lm), bool)
+    for lm in range(WEAK_LINES):
+        ix = np.nonzero(o.ln_lm == lm)[0]
+        keep[ix[2:]] = False
+    for nm in ("ln_lm", "ln_fj", "ln_sp", "ln_ep", "ln_has_vp", "ln_vp"): setattr(o, nm, getattr(o, nm)[keep])
+    return o
+
+
+def weak_landmarks(w):
+    """-> (points with one observation, points with inverse depth <= 1.1e-3, lines with two observations)."""
+    tp, tl = _track_lengths(w.pt_lm, len(w.inv_depth)), _track_lengths(w.ln_lm, len(w.line_orth))
+    return np.nonzero(tp == 1)[0], np.nonzero(np.abs(w.inv_depth) <= 1.1e-3)[0], np.nonzero(tl == 2)[0]
+
+
+def check_weak(sysm):
+    """The property of `weak` in numbers, on the undamped normal matrix H of the case (lm_step_ref.System): the smallest landmark pivot lies at least seven
+    orders under the largest for the points and four for the lines (smallest eigenvalue of a 4 x 4 line block against the largest of any), the weak
+    landmarks are the ones built for it, and at the default radius 1e4 the damped Jacobi-scaled system still has cond(M) < 1e13."""
+    w, L = sysm.w, sysm.L
+    one, far, two = weak_landmarks(w)
+    assert len(one) == WEAK_POINTS and len(far) == WEAK_FAR and len(two) == WEAK_LINES
+    hp = np.asarray(np.diag(sysm.H)[L["pt"]:L["ln"]], np.float64)
+    assert hp.min() <= 1e-7 * hp.max(), (hp.min(), hp.max())      # measured 1.0e-8 (the perturbed start state keeps the points 1e-3 off the epipole)
+    assert set(np.argsort(hp)[:4].tolist()) <= set(one.tolist()), np.argsort(hp)[:6]      # the points nearest the epipole
+    ev = [np.linalg.eigvalsh(np.asarray(sysm.H[L["ln"] + 4 * k:L["ln"] + 4 * k + 4, L["ln"] + 4 * k:L["ln"] + 4 * k + 4], np.float64)) for k in range(len(w.line_orth))]
+    lo = np.array([e[0] for e in ev]); hi = max(e[-1] for e in ev)
+    assert lo.min() <= 1e-4 * hi, (lo.min(), hi)
+    cond = np.linalg.cond(np.asarray(sysm.M(1e4), np.float64))
+    assert cond < 1e13, cond
+    return float(hp.min() / hp.max()), float(lo.min() / hi), float(cond)
+
+
+def capacity(name):
+    """Solver capacities the case needs beyond the defaults."""
+    return dict(max_points=1100, max_point_obs=12000, max_lines=320, max_line_obs=3400) if name.startswith("many_chunks") else {}
 
 
 def options(name):
     o = abi.default_options()
-    if name == "td": o.estimate_td = 1
-    if name in ("extrinsic", "prior_extrinsic"): o.estimate_extrinsic = 1
+    if name in BIG_NAMES: o.estimate_extrinsic = 1
+    if name in ("td", "relo_extrinsic_td", "prior_td"): o.estimate_td = 1
+    if name in ("extrinsic", "prior_extrinsic", "relo_extrinsic", "relo_extrinsic_td"): o.estimate_extrinsic = 1
     if name == "no_jacobi": o.jacobi_scaling = 0
     return o
 
@@ -20,6 +116,11 @@ def options(name):
 def environment(name):
     """Environment of the solve: full_rows runs the full-row Cholesky (DevWin::chol_half_ok = 0) on an ordinary window."""
     return {"UVS_CHOL_FULL_ROWS": "1"} if name == "full_rows" else {}
+
+
+def create_environment(name):
+    """Environment of uvs_create (read once per handle)."""
+    return {"UVS_DEBUG_LARGE_GRID": "20"} if name == "many_chunks_grid20" else {}
 
 
 def _ragged(w, seed):
@@ -41,7 +142,20 @@ def _ragged(w, seed):
 
 def build(name, marginalize_fn=None):
     """-> (window, options).  The prior cases need `marginalize_fn(window, flag) -> abi.Prior` (the product's on the GPU, the oracle's on the CPU)."""
-    if name == "prior_free":      # the canonical window without a prior: the gauge directions are held by the damping alone
+    if name.startswith("many_chunks"):
+        w = synth.make_window(78, n_points=1000, n_lines=300, n_tagged=200, pt_track=10, ln_track=10)
+        if name != "many_chunks_plain": w = synth.add_relocalization(w, relo_frame=9, fraction=1.0, pixel_sigma=0.5, seed=2)
+    elif name == "weak":
+        w = _weak(synth.make_window(130))
+    elif name == "prior_td":      # a prior with a TD block: the marginalization of another td window under the same options (tests/test_td.py, test_marginalization.py do the same): n = 76
+        w = synth.add_time_offset(synth.make_window(120), seed=120)
+        w.prior = marginalize_fn(synth.add_time_offset(synth.make_window(220, pt_track=11, ln_track=11), seed=220), 0)      # (eleven-frame tracks: the marginalized frame is linked to every other pose)
+    elif name in RELO:
+        seed = 110 + RELO_NAMES.index(name)
+        w = synth.make_window(seed, with_prior=True, marginalize_fn=marginalize_fn) if name == "relo_prior" else synth.make_window(seed)
+        if name == "relo_extrinsic_td": w = synth.add_time_offset(w, seed=seed)
+        w = synth.add_relocalization(w, relo_frame=RELO[name][0], fraction=RELO[name][1], seed=seed)
+    elif name == "prior_free":      # the canonical window without a prior: the gauge directions are held by the damping alone
         w = synth.make_window(4)
     elif name in PRIOR_CASES:     # the canonical window with the n = 75 prior of marginalizing the previous window's oldest frame
         w = synth.make_window(11 if name != "prior_extrinsic" else 12, with_prior=True, marginalize_fn=marginalize_fn)
@@ -77,10 +191,50 @@ def _track_lengths(lm, n):
     return np.bincount(lm, minlength=n)
 
 
+def chunk_count(w, o, grid):
+    """Landmark chunks of `w` when packed for `grid` chunk workgroups (host only: uvs_debug_pack_layout)."""
+    import ctypes as C
+    import importlib
+    import os
+    lib = importlib.import_module("uv-slam_amd").api.lib()
+    lib.uvs_debug_pack_layout.argtypes = [C.POINTER(abi.Options), C.POINTER(abi.WindowC), C.POINTER(C.c_int32)]
+    wc, keep = w.to_c(); info = (C.c_int32 * 12)()
+    old = os.environ.get("UVS_DEBUG_CHUNK_GRID"); os.environ["UVS_DEBUG_CHUNK_GRID"] = str(grid)
+    try:
+        assert lib.uvs_debug_pack_layout(C.byref(o), C.byref(wc), info) == abi.UVS_OK
+    finally:
+        if old is None: del os.environ["UVS_DEBUG_CHUNK_GRID"]
+        else: os.environ["UVS_DEBUG_CHUNK_GRID"] = old
+    return int(info[2])
+
+
 def check_structure(name, w, o):
     np_, nl = len(w.inv_depth), len(w.line_orth)
-    assert len(w.relo_lm) == 0
-    if name in PRIOR_CASES:
+    if name.startswith("many_chunks"):
+        assert (np_, nl) == (1000, 300) and bool(o.estimate_extrinsic) == (name != "many_chunks_plain") and not o.estimate_td
+        assert (len(w.relo_lm) >= 900) if name != "many_chunks_plain" else len(w.relo_lm) == 0
+        assert np.all(_track_lengths(w.pt_lm, np_) + 1 == 10) and np.all(_track_lengths(w.ln_lm, nl) == 10)
+        n255, n20 = chunk_count(w, o, 255), chunk_count(w, o, 20)
+        assert 128 <= n255 <= 255, n255                          # one chunk per workgroup on an MI355X, far more rows than the 16 slices of k_large_reduce
+        assert n20 == 60, n20                                    # three per workgroup of k_large_chunks; k_large_backsub runs min(60, 2 x 20) = 40 workgroups, 20 of them with two chunks
+        return
+    if name in RELO:
+        fr, frac = RELO[name]
+        first = {}
+        for k in range(len(w.pt_lm)): first.setdefault(int(w.pt_lm[k]), int(w.pt_fi[k]))
+        eligible = sum(1 for f in first.values() if f <= fr)
+        assert w.relo_frame == fr and len(w.relo_lm) >= 3 and len(set(w.relo_lm.tolist())) == len(w.relo_lm)
+        assert all(first[int(lm)] <= fr for lm in w.relo_lm)
+        assert (len(w.relo_lm) == eligible) if frac == 1.0 else (0.5 * frac * eligible <= len(w.relo_lm) <= min(2 * frac, 0.9) * eligible), (len(w.relo_lm), eligible)
+        assert np.array_equal(w.relo_pose, w.pose[fr])
+    else:
+        assert len(w.relo_lm) == 0
+    if name == "prior_td":
+        p = w.prior
+        kinds = list(p.block_kind[:p.n_blocks])
+        assert p.n == 76 and kinds.count(abi.BLOCK_TD) == 1 and kinds.count(abi.BLOCK_POSE) == 10 and kinds.count(abi.BLOCK_SPEEDBIAS) == 1 and kinds.count(abi.BLOCK_EX_POSE) == 1
+        assert p.block_size[kinds.index(abi.BLOCK_TD)] == 1
+    elif name in PRIOR_CASES:
         p = w.prior
         assert p is not None and p.n == 75
         kinds = list(p.block_kind[:p.n_blocks])
@@ -89,7 +243,7 @@ def check_structure(name, w, o):
         assert environment(name).get("UVS_CHOL_FULL_ROWS") == ("1" if name == "full_rows" else None)            # ... unless switched off
     else:
         assert w.prior is None or w.prior.n == 0
-    assert bool(o.estimate_td) == (name == "td") and bool(o.estimate_extrinsic) == (name in ("extrinsic", "prior_extrinsic"))
+    assert bool(o.estimate_td) == (name in ("td", "relo_extrinsic_td", "prior_td")) and bool(o.estimate_extrinsic) == (name in ("extrinsic", "prior_extrinsic", "relo_extrinsic", "relo_extrinsic_td"))
     assert bool(o.jacobi_scaling) == (name != "no_jacobi")
     if name == "points_only": assert np_ > 0 and nl == 0 and len(w.ln_lm) == 0
     elif name == "lines_only": assert np_ == 0 and nl > 0 and len(w.pt_lm) == 0
@@ -100,7 +254,7 @@ def check_structure(name, w, o):
     if name == "tracks2": assert np.all(tp == 2) and np.all(tl == 2)
     if name == "tracks10": assert np.all(tp == 10) and np.all(tl == 10)
     if name == "ragged": assert tp.min() == 2 and tp.max() == 9 and len(np.unique(tp)) == 8 and tl.min() == 3 and len(np.unique(tl)) >= 5
-    if name == "td":
+    if name in ("td", "relo_extrinsic_td", "prior_td"):
         assert w.pt_vel_i is not None and len(w.pt_vel_i) == len(w.pt_lm) and np.abs(w.pt_vel_j).max() > 0
     if np_: assert set(np.unique(w.pt_lm)) == set(range(np_))
     if nl: assert set(np.unique(w.ln_lm)) == set(range(nl))

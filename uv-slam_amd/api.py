@@ -70,6 +70,8 @@ def lib():
         L.uvs_large_exchange_host.argtypes = [C.c_void_p, C.c_int, abi.c_double_p, C.c_int]; L.uvs_large_exchange_host.restype = C.c_int
         L.uvs_large_local_x2.argtypes = [C.c_void_p]; L.uvs_large_local_x2.restype = C.c_double
         L.uvs_large_set_landmark_x2.argtypes = [C.c_void_p, C.c_double]
+        L.uvs_large_set_debug_step.argtypes = [C.c_void_p, C.c_int]; L.uvs_large_set_debug_step.restype = C.c_int
+        L.uvs_large_debug_step.argtypes = [C.c_void_p, C.c_double, C.c_int, abi.c_double_p, abi.c_double_p]; L.uvs_large_debug_step.restype = C.c_int
         L.uvs_large_finish.argtypes = [C.c_void_p, C.POINTER(abi.StateC), C.POINTER(abi.Report)]; L.uvs_large_finish.restype = C.c_int
         L.uvs_large_solve.argtypes = [C.c_void_p, C.POINTER(abi.WindowC), C.POINTER(abi.StateC), C.POINTER(abi.Report)]; L.uvs_large_solve.restype = C.c_int
         L.uvs_large_comm_unique_id.argtypes = [C.c_char_p]; L.uvs_large_comm_unique_id.restype = C.c_int
@@ -338,6 +340,52 @@ class Solver:
         step = np.zeros((len(r), n_step)); scal = np.zeros((len(r), 40))
         self._check(lib().uvs_debug_step(self._h, C.byref(wc), int(form), len(r), abi._dp(r), n_step, abi._dp(step), abi._dp(scal)))
         return step, scal
+
+    @staticmethod
+    def debug_step_sharded(solvers, shards, radii):
+        """Diagnostic: the step of uvs_debug_step form 1 for a window sharded over `solvers` (one handle per shard of synth.shard_landmarks, all in this
+        process), through the step-wise calls with the two exchange vectors summed on the host as large_solve(dist=...) sums them (entry n - 7 of the
+        reduced vector is a MAX).  -> per shard (step [n_radii, n_step of the shard], scal [n_radii, UVS_DEBUG_SCAL_LEN])."""
+        L = lib()
+        G = len(solvers)
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        keep = [w.to_c() for w in shards]
+        out = []
+        for s, w in zip(solvers, shards):
+            o = s.opts
+            n_step = 165 + 6 * bool(o.estimate_extrinsic) + bool(o.estimate_td) + 6 * (len(w.relo_lm) > 0) + len(w.inv_depth) + 4 * len(w.line_orth)
+            out.append((np.zeros((len(r), n_step)), np.zeros((len(r), 40))))
+        rcs = []
+        for s, (wc, _) in zip(solvers, keep):
+            s._check(L.uvs_large_set_nranks(s._h, G)); s._check(L.uvs_large_set_debug_step(s._h, 1))
+            rcs.append(L.uvs_large_begin(s._h, C.byref(wc)))
+        try:
+            for s, rc in zip(solvers, rcs): s._check(rc)      # (a refusal on one rank is every rank's: nothing has been exchanged yet)
+
+            def exchange(which, n):
+                bufs = [np.zeros(n) for _ in solvers]
+                for s, b in zip(solvers, bufs): s._check(L.uvs_large_exchange_host(s._h, which, abi._dp(b), 0))
+                tot = bufs[0].copy()
+                for b in bufs[1:]: tot = tot + b
+                if which == 0: tot[n - 7] = max(b[n - 7] for b in bufs)
+                for s in solvers: s._check(L.uvs_large_exchange_host(s._h, which, abi._dp(tot), 1))
+
+            n = C.c_int(0)
+            L.uvs_large_reduced(solvers[0]._h, C.byref(n)); n_red = n.value
+            L.uvs_large_scalars(solvers[0]._h, C.byref(n)); n_sc = n.value
+            for k in range(len(r)):
+                for s in solvers:
+                    assert L.uvs_large_need_linearize(s._h)
+                    s._check(L.uvs_large_linearize(s._h))
+                exchange(0, n_red)
+                for s in solvers: s._check(L.uvs_large_step(s._h))
+                exchange(1, n_sc)
+                for s, (step, scal) in zip(solvers, out):
+                    s._check(L.uvs_large_debug_step(s._h, float(r[k + 1]) if k + 1 < len(r) else 0.0, step.shape[1], abi._dp(step[k]), abi._dp(scal[k])))
+        finally:
+            for s in solvers:
+                L.uvs_large_set_debug_step(s._h, 0); L.uvs_large_set_nranks(s._h, 1)
+        return out
 
     def debug_first_iteration(self, w: abi.Window):
         wc, keep = w.to_c()

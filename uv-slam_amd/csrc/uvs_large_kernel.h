@@ -269,7 +269,10 @@ __global__ __launch_bounds__(NT) void k_large_solve(char* blob, double* ws, KOpt
 #define UVS_LARGE_OCC 2
 #endif
 static constexpr size_t LDS_BYTES_BACKSUB = (size_t)(L_S + 2048) * 8;      // prior_quad's partials [0, 512), the IMU residual scratch of cost_pass at 1024
-__global__ __launch_bounds__(NT, UVS_LARGE_OCC) void k_large_backsub(char* blob, double* ws, KOpts o, const double* state, int sel, double* bsums, LargeCtl lc, int n_chunk_wgs, double* out) {
+// DSTEP (k_large_backsub_dstep, behind uvs_debug_step form 1 and uvs_large_set_debug_step): the landmark steps of backsub_candidate are stored to lstep[points | 4 x lines]
+// as well; the product kernel passes nullptr, i.e. carries no such code
+template <bool DSTEP>
+__device__ __forceinline__ void large_backsub_body(char* blob, double* ws, KOpts o, const double* state, int sel, double* bsums, LargeCtl lc, int n_chunk_wgs, double* out, double* lstep) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int tid = threadIdx.x;
     if (lc.ctl) { if (lc.ctl[LC_DONE] != 0.0) return; sel = (int)lc.ctl[LC_SEL]; }
@@ -311,7 +314,9 @@ __global__ __launch_bounds__(NT, UVS_LARGE_OCC) void k_large_backsub(char* blob,
             }
         }
 #endif
-        backsub_candidate<2, UVS_LARGE_PSB, true>(c, invd, line, invd_c, line_c, type == 0 ? k0 : 0, type == 0 ? k1 : 0, type == 1 ? k0 : 0, type == 1 ? k1 : 0, false, bo);
+        backsub_candidate<2, UVS_LARGE_PSB, true>(c, invd, line, invd_c, line_c, type == 0 ? k0 : 0, type == 0 ? k1 : 0, type == 1 ? k0 : 0, type == 1 ? k1 : 0, false, bo, DSTEP ? lstep + UVS_DSTEP_FR : nullptr);
+        // the frame part as THIS kernel holds it (relo_Pose at [16 * UVS_RELO_FRAME ..): copied from the spare rows or rebuilt by relo2_backsub inside the call above)
+        if (DSTEP && ch == 0 && tid < UVS_DSTEP_FR) lstep[tid] = sh[L_DLT + tid];
 #ifndef UVS_X_NO_LARGE_TOUCH
         asm volatile("" :: "v"(tacc), "v"(tiacc));
 #endif
@@ -324,6 +329,12 @@ __global__ __launch_bounds__(NT, UVS_LARGE_OCC) void k_large_backsub(char* blob,
         block_reduce(sh, s4, &mx);
         if (tid == 0) bo[4] = s4[0];
     }
+}
+__global__ __launch_bounds__(NT, UVS_LARGE_OCC) void k_large_backsub(char* blob, double* ws, KOpts o, const double* state, int sel, double* bsums, LargeCtl lc, int n_chunk_wgs, double* out) {
+    large_backsub_body<false>(blob, ws, o, state, sel, bsums, lc, n_chunk_wgs, out, nullptr);
+}
+__global__ __launch_bounds__(NT, UVS_LARGE_OCC) void k_large_backsub_dstep(char* blob, double* ws, KOpts o, const double* state, int sel, double* bsums, LargeCtl lc, int n_chunk_wgs, double* out, double* lstep) {
+    large_backsub_body<true>(blob, ws, o, state, sel, bsums, lc, n_chunk_wgs, out, lstep);
 }
 // out5[5] (fused loop with a communicator): THIS rank's vote "options.max_solver_time_in_seconds is used up" -- the SUM all-reduce of the 8 doubles turns the votes
 // into one number that is the same on every rank, and k_large_decide ends the solve when it is non-zero: a rank that tested its own clock could stop an

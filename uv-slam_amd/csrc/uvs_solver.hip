@@ -128,7 +128,8 @@ struct uvs_solver {
     int large_solve_nt = 512;                // ... and for k_large_solve (UVS_LARGE_SOLVE_NT=256)
     int large_chunks_nt = 512;               // likewise for k_large_chunks (UVS_LARGE_CHUNKS_NT=256 selects the 256-thread kernel of this file)
     int ksolve_nt = 512;                     // which instantiation of the persistent kernel launch_solve uses (uvs_solve512.hip / this file's 256-thread one)
-    int chunk_wgs() const { return std::max(1, n_cus - 1); }      // chunk workgroups of the persistent large-window kernels: one compute unit stays free for the frame-terms workgroup of the same launch
+    int large_grid = 0;                      // UVS_DEBUG_LARGE_GRID (step tests, read at uvs_create): fewer chunk workgroups than the device offers, so that a small window walks the persistent loops
+    int chunk_wgs() const { return std::max(1, large_grid > 0 ? std::min(large_grid, n_cus - 1) : n_cus - 1); }      // chunk workgroups of the persistent large-window kernels: one compute unit stays free for the frame-terms workgroup of the same launch
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
@@ -162,6 +163,7 @@ struct uvs_solver {
     struct Large {
         bool active = false; int n_chunks = 0, sel = 0, it = 0, invalid = 0, nsucc = 0, pending = 0, term = 0, status = 0;
         bool need_lin = true, first = true, done = false;
+        bool stored = false; int backsub_wgs = 0;              // the last uvs_large_step ran the storing back-substitution (uvs_large_debug_step), on so many chunk workgroups
         double radius = 0, decr = 2, cost = 0, gmax = 0, x_norm = 0, local_x2 = 0;
         uvs_report rep;
         double frame_x2 = 0;                                    // frame part of ||x||^2 (the landmark part is per rank: local_x2)
@@ -176,6 +178,7 @@ struct uvs_solver {
         DevBuf<double> d_fimg;                                  // frame image of the reduced system (k_large_chunks' extra workgroup -> k_large_solve)
         void* comm = nullptr; int rank = 0, nranks = 1;         // RCCL communicator owned by the handle (uvs_large_comm_init)
         int step_nranks = 1;                                    // ranks the caller all-reduces the step-wise form over (uvs_large_set_nranks)
+        bool debug_step = false; DevBuf<double> d_lstep;        // uvs_large_set_debug_step: uvs_large_step runs k_large_backsub_dstep, which stores the step [UVS_DSTEP_FR | points | 4 x lines]
     } LB;
     ~uvs_solver();
 };
@@ -196,7 +199,7 @@ static KOpts make_kopts(const uvs_options& o, int debug) {
 }
 
 struct DevWin;
-static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vector<char>& out, DevWin& hdr, std::string& err, int chunk_grid = 0, PackCache* cache = nullptr, PackDst* dst = nullptr);
+static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vector<char>& out, DevWin& hdr, std::string& err, int chunk_grid = 0, PackCache* cache = nullptr, PackDst* dst = nullptr, bool all_blocks = false);
 
 extern "C" {
 
@@ -269,6 +272,7 @@ int uvs_create(const uvs_options* opts, int device, int max_batch, int max_point
     if (uvs_k_solve512_arg_bytes(0) != sizeof(KOpts) || uvs_k_solve512_arg_bytes(1) != sizeof(DebugOut) || uvs_k_solve512_arg_bytes(2) != sizeof(DebugStep) || uvs_k_solve512_init(fa, fb, UVS_NBLK) != UVS_OK ||
         uvs_k_solve256d_init(fa, fb, UVS_NBLK) != UVS_OK) { uvs_destroy(s); return UVS_ERR_HIP; }
     { const char* e = std::getenv("UVS_KSOLVE_NT"); s->ksolve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
+    { const char* e = std::getenv("UVS_DEBUG_LARGE_GRID"); s->large_grid = e ? std::max(0, std::atoi(e)) : 0; }
     { const char* e = std::getenv("UVS_LARGE_CHUNKS_NT"); s->large_chunks_nt = (e && std::atoi(e) == 256) ? 256 : 512; }
     { const char* e = std::getenv("UVS_LARGE_SOLVE_NT"); s->large_solve_nt = (e && std::atoi(e) == 256) ? 256 : 512; }      // A/B switch: 256 = the one-wave-per-SIMD instantiation of the persistent kernel
     // the LDS opt-in is a per-device function attribute: every handle sets it for its own device (the current one since hipSetDevice above)
@@ -360,14 +364,14 @@ static int pack_inner_threads(int n_obs) {
 // (memcmp of the arrays), no hashing.  Small windows do not use it: their structure changes with every frame of a live sequence.
 struct PackCache {
     bool valid = false, device_holds_tables = false;
-    int chunk_grid = 0, td_on = 0, ex_on = 0;
+    int chunk_grid = 0, td_on = 0, ex_on = 0; bool all_blocks = false;
     int n_points = 0, n_pt_obs = 0, n_lines = 0, n_ln_obs = 0, n_imu = 0;
     std::vector<int32_t> pt_lm, pt_fi, pt_fj, ln_lm, ln_fj, ln_has_vp;
     int imu_fs[UVS_WINDOW_SIZE][2];
     bool have_prior = false; int prior_n = 0, prior_nb = 0; int prior_tab[5][UVS_MAX_PRIOR_BLOCKS];
     DevWin hdr;
-    bool matches(const uvs_window* w, const uvs_options& o, int grid) const {
-        if (!valid || !w || grid != chunk_grid || (o.estimate_td != 0) != (td_on != 0) || (o.estimate_extrinsic != 0) != (ex_on != 0) || w->n_relo_obs > 0) return false;
+    bool matches(const uvs_window* w, const uvs_options& o, int grid, bool all) const {
+        if (!valid || !w || grid != chunk_grid || all != all_blocks || (o.estimate_td != 0) != (td_on != 0) || (o.estimate_extrinsic != 0) != (ex_on != 0) || w->n_relo_obs > 0) return false;
         if (w->n_points != n_points || w->n_point_obs != n_pt_obs || w->n_lines != n_lines || w->n_line_obs != n_ln_obs || w->n_imu != n_imu) return false;
         const bool hp = w->prior && w->prior->n > 0;
         if (hp != have_prior) return false;
@@ -384,8 +388,8 @@ struct PackCache {
         return (!np_ || (!std::memcmp(w->pt_lm, pt_lm.data(), np_) && !std::memcmp(w->pt_fi, pt_fi.data(), np_) && !std::memcmp(w->pt_fj, pt_fj.data(), np_))) &&
                (!nl_ || (!std::memcmp(w->ln_lm, ln_lm.data(), nl_) && !std::memcmp(w->ln_fj, ln_fj.data(), nl_) && !std::memcmp(w->ln_has_vp, ln_has_vp.data(), nl_)));
     }
-    void store(const uvs_window* w, const uvs_options& o, int grid, const DevWin& h) {
-        valid = true; device_holds_tables = false; chunk_grid = grid; td_on = o.estimate_td != 0; ex_on = o.estimate_extrinsic != 0;
+    void store(const uvs_window* w, const uvs_options& o, int grid, bool all, const DevWin& h) {
+        valid = true; device_holds_tables = false; chunk_grid = grid; all_blocks = all; td_on = o.estimate_td != 0; ex_on = o.estimate_extrinsic != 0;
         n_points = w->n_points; n_pt_obs = w->n_point_obs; n_lines = w->n_lines; n_ln_obs = w->n_line_obs; n_imu = w->n_imu;
         pt_lm.assign(w->pt_lm, w->pt_lm + n_pt_obs); pt_fi.assign(w->pt_fi, w->pt_fi + n_pt_obs); pt_fj.assign(w->pt_fj, w->pt_fj + n_pt_obs);
         ln_lm.assign(w->ln_lm, w->ln_lm + n_ln_obs); ln_fj.assign(w->ln_fj, w->ln_fj + n_ln_obs); ln_has_vp.assign(w->ln_has_vp, w->ln_has_vp + n_ln_obs);
@@ -446,8 +450,8 @@ static void fill_values(char* B, const DevWin& h, const uvs_window* w, bool td_o
     }
 }
 
-static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vector<char>& out, DevWin& hdr, std::string& err, int chunk_grid, PackCache* cache, PackDst* dst) {
-    if (cache && cache->matches(w_in, opts, chunk_grid) && out.size() == (size_t)cache->hdr.blob_bytes) {      // same structure as the blob still sitting in `out`: values only
+static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vector<char>& out, DevWin& hdr, std::string& err, int chunk_grid, PackCache* cache, PackDst* dst, bool all_blocks) {
+    if (cache && cache->matches(w_in, opts, chunk_grid, all_blocks) && out.size() == (size_t)cache->hdr.blob_bytes) {      // same structure as the blob still sitting in `out`: values only
         fill_values(out.data(), cache->hdr, w_in, opts.estimate_td != 0, pack_inner_threads(w_in->n_point_obs + w_in->n_line_obs));
         hdr = cache->hdr;
         return UVS_OK;
@@ -695,9 +699,11 @@ static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vec
         for (int b = 0; b < UVS_NBLKX2; ++b) {      // the pseudo-frame blocks only exist with their option
             const bool tdb = b >= UVS_NBLK && b < UVS_NBLK + UVS_NF + 1, exb = b >= UVS_NBLK + UVS_NF + 1 && b < UVS_NBLKX;
             // a block nothing contributes to (frames further apart than the longest track, pseudo-frame blocks of an option that is off) gets
-            // no group at all: S is zeroed anyway, and its group goes to a heavy block instead (15 of 128 groups for the canonical window)
+            // no group at all: S is zeroed anyway, and its group goes to a heavy block instead (15 of 128 groups for the canonical window).
+            // all_blocks (a landmark SHARD of a solve over several ranks): every block of an option that is on keeps a group, because k_large_solve loads the all-reduced
+            // vector through the part-0 groups -- a block that only the OTHER ranks' landmarks contribute to would otherwise never reach this rank's reduced system
             const bool r2b = b >= UVS_NBLKX;      // block row 13 (relo_Pose beside a free extrinsic)
-            np[b] = ((b < UVS_NBLK || (tdb && td_on) || (!r2b && exb && (ex_on || relo_on) && (td_on || b != UVS_NBLK + UVS_NF + 1 + UVS_NF)) || (r2b && relo2 && (td_on || b != UVS_NBLKX + UVS_NF))) && blk_work[b] > 0) ? 1 : 0;
+            np[b] = ((b < UVS_NBLK || (tdb && td_on) || (!r2b && exb && (ex_on || relo_on) && (td_on || b != UVS_NBLK + UVS_NF + 1 + UVS_NF)) || (r2b && relo2 && (td_on || b != UVS_NBLKX + UVS_NF))) && (all_blocks || blk_work[b] > 0)) ? 1 : 0;
             used += np[b];
         }
         // The waves run in lock step inside a chunk and the chunks of the two landmark families are separated by barriers, so what counts
@@ -964,7 +970,7 @@ static int pack_window(const uvs_window* w_in, const uvs_options& opts, std::vec
     for (int q = 0; q < NG; ++q) I[h.i_wblk + q] = wblk[q];
     lap_("blob");
     hdr = h;
-    if (cache && !relo_on && h.n_pt_obs + h.n_ln_obs >= kPackCacheMinObs) cache->store(w_in, opts, chunk_grid, h);
+    if (cache && !relo_on && h.n_pt_obs + h.n_ln_obs >= kPackCacheMinObs) cache->store(w_in, opts, chunk_grid, all_blocks, h);
     return UVS_OK;
 }
 
@@ -980,7 +986,7 @@ __global__ void k_pack_outputs(const double* ws, const long long* tab, double* o
 }
 
 // out_direct: (uvs_batch_stream) every staged header gets the address of its window's slot in the pinned result buffer (DevWin::out_host): k_solve then writes the final state there itself
-static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, bool wait, int chunk_grid = 0, bool out_direct = false) {
+static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, bool wait, int chunk_grid = 0, bool out_direct = false, bool all_blocks = false) {
     if (!s || n < 1 || !ws) return UVS_ERR_INVALID_ARG;
     if (n > s->max_batch) { s->err = "batch larger than max_batch"; return UVS_ERR_CAPACITY; }
     UVS_HIP(s->err, hipSetDevice(s->device));
@@ -1009,7 +1015,7 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
         if (!s->pack_cache) s->pack_cache = std::make_unique<PackCache>();
         const bool was_valid = s->pack_cache->valid, dev = s->pack_cache->device_holds_tables;
         s->blob_off[0] = 0;
-        int rc = pack_window(ws[0], s->opts, s->host_blobs, s->hdrs[0], s->err, chunk_grid, s->pack_cache.get());
+        int rc = pack_window(ws[0], s->opts, s->host_blobs, s->hdrs[0], s->err, chunk_grid, s->pack_cache.get(), nullptr, all_blocks);
         if (rc != UVS_OK) { s->n_loaded = 0; return rc; }
         values_only = !out_direct && was_valid && dev && s->pack_cache->valid && s->pack_cache->device_holds_tables;      // (a miss resets both flags; the stream patches every staged header -- DevWin::out_host -- so the whole blob travels)
     } else if (nthreads == 1) {
@@ -1017,7 +1023,7 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
         if (s->pack_cache) { s->pack_cache->valid = false; s->pack_cache->device_holds_tables = false; }
         for (int b = 0; b < n; ++b) {
             s->blob_off[b] = (long long)s->host_blobs.size();
-            int rc = pack_window(ws[b], s->opts, s->host_blobs, s->hdrs[b], s->err, chunk_grid, nullptr);
+            int rc = pack_window(ws[b], s->opts, s->host_blobs, s->hdrs[b], s->err, chunk_grid, nullptr, nullptr, all_blocks);
             if (rc != UVS_OK) { s->n_loaded = 0; return rc; }
         }
     } else {
@@ -1036,7 +1042,7 @@ static int upload_windows(uvs_solver* s, int n, const uvs_window* const* ws, boo
             for (int b = t; b < n; b += nthreads) {
                 PackDst d{&bump, direct_cap ? s->h_up.get() : nullptr, direct_cap, -1};
                 s->slot_blobs[b].clear();
-                rcs[b] = pack_window(ws[b], s->opts, s->slot_blobs[b], s->hdrs[b], errs[b], chunk_grid, nullptr, &d);
+                rcs[b] = pack_window(ws[b], s->opts, s->slot_blobs[b], s->hdrs[b], errs[b], chunk_grid, nullptr, &d, all_blocks);
                 placed[b] = d.off;
             }
         };
@@ -1461,16 +1467,18 @@ int uvs_debug_first_iteration(uvs_solver* s, const uvs_window* w, double* S_lowe
     return UVS_OK;
 }
 
+static int debug_step_large(uvs_solver* s, const uvs_window* w, int n_radii, const double* radii, int n_step, double* step, double* scal);      // form 1, behind the step-wise large-window calls below
 // Diagnostic entry (step tests): the damped step of the first linearization of `w` at radii[0], then at radii[1], ... each the way `form` handles a
-// rejected step (form 0, k_solve: re-damping of the stored linearization).  step[k * n_step ...] = unscaled tangent step in the layout of include/uvs_solver.h, scal[k * UVS_DEBUG_SCAL_LEN ...] its scalars.
+// rejected step (form 0, k_solve: re-damping of the stored linearization; form 1, k_large_*: re-linearization at the same state).  step[k * n_step ...] = unscaled tangent step in the layout of include/uvs_solver.h, scal[k * UVS_DEBUG_SCAL_LEN ...] its scalars.
 int uvs_debug_step(uvs_solver* s, const uvs_window* w, int form, int n_radii, const double* radii, int n_step, double* step, double* scal) {
-    if (!s || !w || !radii || !step || !scal || n_radii < 1 || form != 0) { if (s) s->err = "uvs_debug_step: bad argument"; return UVS_ERR_INVALID_ARG; }
+    if (!s || !w || !radii || !step || !scal || n_radii < 1 || (form != 0 && form != 1)) { if (s) s->err = "uvs_debug_step: bad argument"; return UVS_ERR_INVALID_ARG; }
     for (int k = 0; k < n_radii; ++k) if (!std::isfinite(radii[k]) || !(radii[k] > 0.0)) { s->err = "uvs_debug_step: a radius that is not finite or <= 0"; return UVS_ERR_INVALID_ARG; }
     if (w->n_points < 0 || w->n_lines < 0) { s->err = "uvs_debug_step: negative landmark count"; return UVS_ERR_INVALID_ARG; }
     const uvs_options& o = s->opts;
     const int ex = o.estimate_extrinsic ? 1 : 0, td = o.estimate_td ? 1 : 0, relo = w->n_relo_obs > 0 ? 1 : 0;
     const long long n_fr = 165 + 6 * ex + td + 6 * relo;
     if ((long long)n_step != n_fr + w->n_points + 4LL * w->n_lines) { s->err = "uvs_debug_step: step length does not match the layout"; return UVS_ERR_INVALID_ARG; }
+    if (form == 1) return debug_step_large(s, w, n_radii, radii, n_step, step, scal);
     const long long stride = UVS_DSTEP_FR + (long long)w->n_points + 4LL * w->n_lines;
     std::vector<double> raw((size_t)(stride * n_radii)), rsc((size_t)UVS_DEBUG_SCAL_LEN * n_radii, 0.0);
     int rc = UVS_OK;
@@ -1865,7 +1873,7 @@ int uvs_large_begin(uvs_solver* s, const uvs_window* w) {
     // reduced vector is not exchanged
     if (s->LB.step_nranks > 1 && w->n_relo_obs > 0) { s->L.active = false; s->err = "relocalization blocks are not taken by a landmark-sharded solve over several ranks"; return UVS_ERR_UNSUPPORTED; }
     const uvs_window* arr[1] = {w};
-    int rc = upload_windows(s, 1, arr, true, s->chunk_wgs());
+    int rc = upload_windows(s, 1, arr, true, s->chunk_wgs(), false, s->LB.step_nranks > 1);
     if (rc != UVS_OK) return rc;
     const bool fresh = !s->LB.d_reduced;      // (zeroed once, when it is first allocated)
     if ((rc = large_prologue(s, w)) != UVS_OK) return rc;
@@ -1920,7 +1928,16 @@ int uvs_large_step(uvs_solver* s) {
     KOpts ko = make_kopts(s->opts, 0);
     if (s->large_solve_nt == 512) { if (uvs_k_large_solve512_launch(s->stream, s->d_blobs, s->d_ws, &ko, sizeof(ko), LB.d_state, LB.d_reduced, L.first ? 1 : 0, L.radius, LB.d_out, nullptr, 0, 0, LB.d_fimg) != UVS_OK) { s->err = "k_large_solve (512 threads): argument layout mismatch"; return UVS_ERR_HIP; } }
     else hipLaunchKernelGGL(k_large_solve, dim3(1), dim3(NT), LDS_BYTES, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, LB.d_reduced, L.first ? 1 : 0, L.radius, LB.d_out, LargeCtl{nullptr, 0, 0}, LB.d_fimg);
-    { const int bg = std::min(L.n_chunks, UVS_LARGE_OCC * s->chunk_wgs());      // (UVS_LARGE_OCC workgroups per compute unit: the kernel asks for little LDS and half the registers)
+    L.stored = LB.debug_step;
+    { const int bg = std::min(L.n_chunks, UVS_LARGE_OCC * s->chunk_wgs()); L.backsub_wgs = bg;      // (UVS_LARGE_OCC workgroups per compute unit: the kernel asks for little LDS and half the registers)
+      if (LB.debug_step) {      // diagnostic (uvs_large_set_debug_step): the storing instantiation of the same body
+          const DevWin& h = s->hdrs[0];
+          const size_t n = (size_t)UVS_DSTEP_FR + (size_t)h.n_points + 4 * (size_t)h.n_lines;
+          if (const int rc = LB.d_lstep.ensure(n * 8, s->err)) return rc;
+          UVS_HIP(s->err, hipMemsetAsync(LB.d_lstep, 0, n * 8, s->stream));
+          if (L.n_chunks == 0) UVS_HIP(s->err, hipMemcpyAsync(LB.d_lstep, LB.d_state + LS_DLT, UVS_RD * 8, hipMemcpyDeviceToDevice, s->stream));      // no landmark chunk, no back-substitution: the frame step as k_large_solve left it
+          hipLaunchKernelGGL(k_large_backsub_dstep, dim3(bg + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, L.sel, LB.d_bsums, LargeCtl{nullptr, 0, 0}, bg, LB.d_out, LB.d_lstep.get());
+      } else
       hipLaunchKernelGGL(k_large_backsub, dim3(bg + 1), dim3(NT), LDS_BYTES_BACKSUB, s->stream, s->d_blobs, s->d_ws, ko, LB.d_state, L.sel, LB.d_bsums, LargeCtl{nullptr, 0, 0}, bg, LB.d_out); }
     hipLaunchKernelGGL(k_large_sum_bsums, dim3(1), dim3(256), 0, s->stream, LB.d_bsums, L.n_chunks, LB.d_sc5, LargeCtl{nullptr, 0, 0}, 0LL);
     UVS_HIP(s->err, hipGetLastError());
@@ -1930,6 +1947,16 @@ int uvs_large_step(uvs_solver* s) {
     const double vote = (o.max_solver_time_in_seconds > 0.0 && L.it > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - L.t_begin).count() >= o.max_solver_time_in_seconds) ? 1.0 : 0.0;
     if (o.max_solver_time_in_seconds > 0.0) UVS_HIP(s->err, hipMemcpy(LB.d_sc5 + 5, &vote, 8, hipMemcpyHostToDevice));
     return UVS_OK;
+}
+
+// The scalars of one step: the frame part (k_large_solve, identical on every rank) plus the landmark sums of the ranks.  uvs_large_decide and uvs_large_debug_step read them here.
+struct LargeStepScal { double gd, dd2, step2, xc2, mcc, cand; };
+static LargeStepScal large_step_scalars(const double* out, const double* sc) {
+    LargeStepScal v;
+    v.gd = out[LO_GD] + sc[0]; v.dd2 = out[LO_DD2] + sc[1]; v.step2 = out[LO_STEP2] + sc[2]; v.xc2 = out[LO_XC2] + sc[3];
+    v.mcc = 0.5 * (v.dd2 - v.gd);
+    v.cand = out[LO_FRAMECOST] + sc[4];
+    return v;
 }
 
 // Host side of the trust-region loop (same order of tests as k_solve / SURVEY.md Appendix B).  Call after uvs_large_step (and after the
@@ -1956,9 +1983,9 @@ int uvs_large_decide(uvs_solver* s) {
     if (L.radius <= o.min_trust_region_radius) { L.term = UVS_TERM_MIN_RADIUS; L.done = true; return UVS_OK; }
     ++L.it;
     const int ti = L.it < UVS_MAX_ITER ? L.it : UVS_MAX_ITER;
-    const double gd = out[LO_GD] + sc[0], dd2 = out[LO_DD2] + sc[1], step2 = out[LO_STEP2] + sc[2], xc2 = out[LO_XC2] + sc[3];
-    const double mcc = 0.5 * (dd2 - gd);
-    double cand = out[LO_FRAMECOST] + sc[4];
+    const LargeStepScal ss = large_step_scalars(out, sc);
+    const double step2 = ss.step2, xc2 = ss.xc2, mcc = ss.mcc;
+    double cand = ss.cand;
     bool ok = out[LO_CHOLOK] != 0.0 && std::isfinite(mcc) && std::isfinite(step2);
     rep.model_cost_change[ti] = mcc;
     if (!ok || !(mcc > 0.0)) {
@@ -1992,6 +2019,67 @@ int uvs_large_decide(uvs_solver* s) {
     }
     return UVS_OK;
 }
+
+int uvs_large_set_debug_step(uvs_solver* s, int on) {
+    if (!s) return UVS_ERR_INVALID_ARG;
+    s->LB.debug_step = on != 0;
+    return UVS_OK;
+}
+
+// padded device layout of a stored step -> the ABI's: frames (16 f + dof, dof < 15), extrinsic, td, relo_Pose, landmarks
+static void dstep_to_abi(const double* r, long long n_lm, bool ex, bool td, bool relo, double* d) {
+    long long j = 0;
+    for (int f = 0; f < UVS_NF; ++f) for (int a = 0; a < 15; ++a) d[j++] = r[16 * f + a];
+    if (ex) for (int a = 0; a < 6; ++a) d[j++] = r[UVS_EX_INDEX(a)];
+    if (td) d[j++] = r[UVS_TD_INDEX];
+    if (relo) for (int a = 0; a < 6; ++a) d[j++] = r[16 * UVS_RELO_FRAME + a];
+    std::memcpy(d + j, r + UVS_DSTEP_FR, sizeof(double) * (size_t)n_lm);
+}
+static long long dstep_len(const uvs_options& o, int n_points, int n_lines, bool relo) {
+    return 165 + (o.estimate_extrinsic ? 6 : 0) + (o.estimate_td ? 1 : 0) + (relo ? 6 : 0) + (long long)n_points + 4LL * n_lines;
+}
+
+int uvs_large_debug_step(uvs_solver* s, double next_radius, int n_step, double* step, double* scal) {
+    if (!s || !s->L.active || !step || !scal) { if (s) s->err = "uvs_large_debug_step: null pointer or no step-wise solve in progress"; return UVS_ERR_INVALID_ARG; }
+    auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0];
+    if (!LB.debug_step || !L.stored || !LB.d_lstep) { s->err = "uvs_large_debug_step: uvs_large_set_debug_step(1) and one uvs_large_step come first"; return UVS_ERR_INVALID_ARG; }
+    if (std::isnan(next_radius) || std::isinf(next_radius) || next_radius < 0.0) { s->err = "uvs_large_debug_step: the next radius must be finite and >= 0"; return UVS_ERR_INVALID_ARG; }
+    const bool relo = h.relo_on != 0;
+    if ((long long)n_step != dstep_len(s->opts, h.n_points, h.n_lines, relo)) { s->err = "uvs_large_debug_step: step length does not match the layout"; return UVS_ERR_INVALID_ARG; }
+    const size_t n_lm = (size_t)h.n_points + 4 * (size_t)h.n_lines;
+    std::vector<double> raw(UVS_DSTEP_FR + n_lm);
+    double out[LO_N + 8], sc[6];
+    UVS_HIP(s->err, hipSetDevice(s->device));
+    UVS_HIP(s->err, hipMemcpy(raw.data(), LB.d_lstep, raw.size() * 8, hipMemcpyDeviceToHost));
+    UVS_HIP(s->err, hipMemcpy(out, LB.d_out, sizeof(double) * (LO_N + 4), hipMemcpyDeviceToHost));
+    UVS_HIP(s->err, hipMemcpy(sc, LB.d_sc5, sizeof(sc), hipMemcpyDeviceToHost));
+    dstep_to_abi(raw.data(), (long long)n_lm, s->opts.estimate_extrinsic != 0, s->opts.estimate_td != 0, relo, step);
+    const LargeStepScal ss = large_step_scalars(out, sc);
+    std::memset(scal, 0, sizeof(double) * UVS_DEBUG_SCAL_LEN);
+    scal[0] = out[LO_COST]; scal[1] = out[LO_GMAX]; scal[2] = out[LO_CHOLOK]; scal[3] = ss.mcc; scal[4] = ss.step2;
+    scal[5] = L.n_chunks; scal[6] = L.grid; scal[7] = L.backsub_wgs;      // the launch geometry this step really ran with
+    if (next_radius > 0.0) { L.first = false; L.radius = next_radius; L.need_lin = true; }      // what uvs_large_decide does to a rejected step, at the caller's radius
+    return UVS_OK;
+}
+
+}  // extern "C"
+
+// uvs_debug_step, form 1: the step-wise calls themselves with the storing back-substitution, each radius handled as a rejection of the one before
+static int debug_step_large(uvs_solver* s, const uvs_window* w, int n_radii, const double* radii, int n_step, double* step, double* scal) {
+    const bool was = s->LB.debug_step;
+    s->LB.debug_step = true;
+    int rc = uvs_large_begin(s, w);      // (refuses relocalization blocks when uvs_large_set_nranks announced several ranks)
+    if (rc == UVS_OK) s->L.radius = radii[0];
+    for (int k = 0; k < n_radii && rc == UVS_OK; ++k) {
+        if ((rc = uvs_large_linearize(s)) != UVS_OK) break;
+        if ((rc = uvs_large_step(s)) != UVS_OK) break;
+        rc = uvs_large_debug_step(s, k + 1 < n_radii ? radii[k + 1] : 0.0, n_step, step + (size_t)k * n_step, scal + (size_t)k * UVS_DEBUG_SCAL_LEN);
+    }
+    s->LB.debug_step = was; s->L.active = false;
+    return rc;
+}
+
+extern "C" {
 
 int uvs_large_finish(uvs_solver* s, uvs_state* out, uvs_report* rep) {
     if (!s || !s->L.active || !out || !rep) return UVS_ERR_INVALID_ARG;
@@ -2107,7 +2195,7 @@ int uvs_large_solve_fused(uvs_solver* s, const uvs_window* w, uvs_state* out, uv
     // ONE stream, ONE wait: pinned upload -> k_large_init -> the passes -> k_large_pack -> pinned download.  (The step-wise API keeps
     // uvs_large_begin's host-side copies; here every small copy / memset is a line of k_large_init.)
     const uvs_window* arr[1] = {w};
-    int rc = upload_windows(s, 1, arr, false, s->chunk_wgs());
+    int rc = upload_windows(s, 1, arr, false, s->chunk_wgs(), false, s->LB.nranks > 1);
     if (rc != UVS_OK) return rc;
     auto& L = s->L; auto& LB = s->LB; const DevWin& h = s->hdrs[0]; const uvs_options& o = s->opts;
     // relocalization blocks are per-landmark, so a landmark shard may hold none of them while the all-reduced system carries the other ranks' relo_Pose rows: a rank
