@@ -553,6 +553,69 @@ const char *uvs_lc_last_error(const uvs_loop_verifier *lc);
 int uvs_lc_verify(uvs_loop_verifier *lc, int n_pairs, const uvs_lc_pair *pairs, const double tic[3], const double qic_xyzw[4],
                   int32_t *match_old, uint8_t *inlier, uvs_lc_result *results);
 
+/* ---- vanishing points of the line front end (reference feature_tracker/src/line_feature_tracker.cpp:1977-2299) ----
+ * Estimates, for a batch of frames in one call, the three orthogonal vanishing points of each frame's line segments and tags every line with
+ * the one it runs towards; a frame gives the same bits alone or in a batch, and from run to run.  Per frame: 105 line pairs (a counter-based
+ * generator keyed by `seed`) x 360 rotations give 37 800 orthogonal-triple hypotheses; every line pair whose orientations differ by <= 60 deg
+ * votes sqrt(len_i len_j) (sin(2 dev) + 0.2) into the cell of its intersection on a 90 x 360 one-degree latitude / longitude grid; the grid is
+ * smoothed by its 3 x 3 window; the hypothesis whose three cells sum highest wins (the lowest index of the maximum); a line whose direction is
+ * within th_angle of the direction to a vanishing point gets that point's tag.  The numerics (generator, cell rule, the order-independent sum)
+ * are spelled out in csrc/uvs_vanishing_points.hip and restated in tests/vp_ref.py; DESIGN.md 3.8 lists the one place where they deviate from
+ * the reference.  No CPU path: uvs_vp_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_VP_MAX_FRAMES 1024                /* largest max_frames uvs_vp_create takes */
+#define UVS_VP_MAX_LINES 1024                 /* largest max_lines (segments of one frame) */
+#define UVS_VP_MAX_COORD 1e7                  /* largest |coordinate| of a segment, pixels */
+#define UVS_VP_N_SAMPLES 105                  /* int(log(1 - 0.9999) / log(1 - (1/3) * 0.5^2)), line_feature_tracker.cpp:1981-1985 */
+#define UVS_VP_N_ROTATIONS 360
+#define UVS_VP_N_HYPOTHESES 37800             /* UVS_VP_N_SAMPLES x UVS_VP_N_ROTATIONS */
+#define UVS_VP_GRID_LA 90
+#define UVS_VP_GRID_LO 360
+typedef struct uvs_vp_estimator uvs_vp_estimator;  /* opaque: device buffers, pinned staging, stream */
+
+enum {
+    UVS_VP_OK = 0,
+    UVS_VP_TOO_FEW_LINES = 1,      /* n_lines < 2: the reference skips the frame (line_feature_tracker.cpp:86) */
+    UVS_VP_NO_HYPOTHESIS = 2       /* a sample found no pair of distinct, non-parallel lines in its bounded number of attempts */
+};
+
+typedef struct uvs_vp_frame {
+    int32_t n_lines;                   /* 0 .. max_lines */
+    int32_t reserved;
+    const double *segments;            /* [n_lines][4] x1, y1, x2, y2 in pixels of the undistorted image */
+    uint64_t seed;                     /* keys the sample generator */
+} uvs_vp_frame;
+
+typedef struct uvs_vp_camera {
+    double fx, fy, cx, cy;
+} uvs_vp_camera;
+
+typedef struct uvs_vp_result {
+    int32_t status;                    /* UVS_VP_* */
+    int32_t best_hypothesis;           /* 360 * sample + rotation; -1 when status != UVS_VP_OK */
+    double score;                      /* smoothed-grid sum of its three cells */
+    double vps[3][3];                  /* unit vectors with z >= 0: tmp_vps of the reference (zero when status != UVS_VP_OK) */
+    int32_t n_tagged[3];               /* lines per tag */
+    int32_t reserved;
+} uvs_vp_result;
+
+int uvs_vp_create(int device, int max_frames, int max_lines, uvs_vp_estimator **out);
+void uvs_vp_destroy(uvs_vp_estimator *vp);
+const char *uvs_vp_last_error(const uvs_vp_estimator *vp);
+/* th_angle: the tag threshold in radians (the reference: 1 degree).  tag[] (0..2, or 3 for "none") and line_vp[][3] (vps[tag] / vps[tag].z, or
+ * zero for tag 3) hold one entry per line, concatenated over the frames in order; results[n_frames].  A frame whose status is not UVS_VP_OK
+ * has every tag 3.  UVS_ERR_INVALID_ARG: null pointer, n_frames < 1, a negative count, a null array behind a positive count, a coordinate that
+ * is not finite or beyond UVS_VP_MAX_COORD, a zero-length segment, fx / fy / th_angle not positive; UVS_ERR_CAPACITY: n_frames or n_lines
+ * above the handle's capacity.  The handle stays usable after a rejected call. */
+int uvs_vp_estimate(uvs_vp_estimator *vp, int n_frames, const uvs_vp_frame *frames, const uvs_vp_camera *camera, double th_angle,
+                    int32_t *tag, double *line_vp, uvs_vp_result *results);
+/* HIP-event time of the last successful uvs_vp_estimate: upload, the five kernels, download, on the handle's stream (milliseconds). */
+double uvs_vp_last_device_ms(const uvs_vp_estimator *vp);
+/* Diagnostic (tests only): ONE frame through the same kernels, with the intermediate results: hyp[37800][3][3], cells[37800][3] (latitude * 360
+ * + longitude of each vanishing point), scores[37800], grid_raw / grid_smooth[90 * 360], pair_cell[n (n - 1) / 2] (pairs i < j row by row: the
+ * cell the pair voted into, -1 when it did not vote).  All zero when the frame's status is not UVS_VP_OK. */
+int uvs_vp_debug_frame(uvs_vp_estimator *vp, const uvs_vp_frame *frame, const uvs_vp_camera *camera, double th_angle, double *hyp,
+                       int32_t *cells, double *scores, double *grid_raw, double *grid_smooth, int32_t *pair_cell, uvs_vp_result *result);
+
 #ifdef __cplusplus
 }
 #endif

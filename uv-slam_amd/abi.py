@@ -471,3 +471,50 @@ def lc_pairs(pairs):
             e.vio_q[c] = float(d["vio_q"][c])
         e.seed = int(d["seed"]) & ((1 << 64) - 1)
     return arr, keep
+
+
+# ---- vanishing points of the line front end (uvs_vp_*, include/uvs_solver.h) ------------------------------------------------
+VP_MAX_FRAMES = 1024
+VP_MAX_LINES = 1024
+VP_MAX_COORD = 1e7
+VP_N_SAMPLES = 105
+VP_N_ROTATIONS = 360
+VP_N_HYPOTHESES = VP_N_SAMPLES * VP_N_ROTATIONS
+VP_GRID_LA, VP_GRID_LO = 90, 360
+VP_STATUS = ["OK", "TOO_FEW_LINES", "NO_HYPOTHESIS"]      # uvs_vp_result.status
+
+
+class VpFrame(C.Structure):
+    _fields_ = [("n_lines", C.c_int32), ("reserved", C.c_int32), ("segments", c_double_p), ("seed", C.c_uint64)]
+
+
+class VpCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class VpResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("best_hypothesis", C.c_int32), ("score", C.c_double), ("vps", (C.c_double * 3) * 3),
+                ("n_tagged", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(status=int(self.status), best_hypothesis=int(self.best_hypothesis), score=float(self.score),
+                    vps=np.array([list(r) for r in self.vps]), n_tagged=np.array(self.n_tagged[:], np.int32))
+
+
+def vp_frames(frames):
+    """(VpFrame array, keepalive) from dicts with segs [n, 4] (x1, y1, x2, y2 in pixels) and seed."""
+    arr = (VpFrame * max(len(frames), 1))()
+    keep = []
+    for b, d in enumerate(frames):
+        s = np.ascontiguousarray(d["segs"], dtype=np.float64).reshape(-1, 4)
+        keep.append(s)
+        arr[b].n_lines = len(s)
+        arr[b].segments = _dp(s)
+        arr[b].seed = int(d["seed"]) & ((1 << 64) - 1)
+    return arr, keep
+
+
+def vp_camera(cam):
+    c = VpCamera()
+    c.fx, c.fy, c.cx, c.cy = (float(v) for v in cam)
+    return c

@@ -21,6 +21,7 @@ EXPORTS = [
     "uvs_solve_window", "uvs_batch_upload", "uvs_batch_solve", "uvs_batch_download", "uvs_batch_stream", "uvs_evaluate", "uvs_marginalize", "uvs_marginalize_resident", "uvs_marginalize_batch",
     "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step",
     "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify",
+    "uvs_vp_create", "uvs_vp_destroy", "uvs_vp_last_error", "uvs_vp_estimate", "uvs_vp_last_device_ms", "uvs_vp_debug_frame",
 ]
 
 
@@ -90,6 +91,16 @@ def lib():
         L.uvs_lc_verify.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LcPair), abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_uint8), C.POINTER(abi.LcResult)]
         L.uvs_lc_verify.restype = C.c_int
+        L.uvs_vp_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_vp_create.restype = C.c_int
+        L.uvs_vp_destroy.argtypes = [C.c_void_p]; L.uvs_vp_destroy.restype = None
+        L.uvs_vp_last_error.argtypes = [C.c_void_p]; L.uvs_vp_last_error.restype = C.c_char_p
+        L.uvs_vp_estimate.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.VpFrame), C.POINTER(abi.VpCamera), C.c_double, C.POINTER(C.c_int32),
+                                      abi.c_double_p, C.POINTER(abi.VpResult)]
+        L.uvs_vp_estimate.restype = C.c_int
+        L.uvs_vp_last_device_ms.argtypes = [C.c_void_p]; L.uvs_vp_last_device_ms.restype = C.c_double
+        L.uvs_vp_debug_frame.argtypes = [C.c_void_p, C.POINTER(abi.VpFrame), C.POINTER(abi.VpCamera), C.c_double, abi.c_double_p, C.POINTER(C.c_int32),
+                                         abi.c_double_p, abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32), C.POINTER(abi.VpResult)]
+        L.uvs_vp_debug_frame.restype = C.c_int
         _lib = L
     return _lib
 
@@ -503,3 +514,79 @@ class LoopVerifier:
         if rc != abi.UVS_OK:
             raise RuntimeError(f"uvs_lc_verify: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
         return res, mo, inl
+
+
+class VanishingPointEstimator:
+    """Owns one `uvs_vp_estimator` handle: the vanishing points of the line front end (getVPHypVia2Lines, getSphereGrids, getBestVpsHyp,
+    lines2Vps of the reference's line_feature_tracker.cpp) on one GPU, a batch of frames per call.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    ONE_DEGREE = 1.0 / 180.0 * 3.1415926535897932384626433832795       # thAngle of the reference
+
+    def __init__(self, device=0, max_frames=64, max_lines=1024):
+        self._h = C.c_void_p()
+        rc = lib().uvs_vp_create(device, max_frames, max_lines, C.byref(self._h))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_vp_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
+
+    def close(self):
+        if self._h:
+            lib().uvs_vp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate_raw(self, frames, camera, th_angle=None, n_frames=None, null=()):
+        """-> (return code, [result dict], [tag per frame], [line_vp per frame]) without raising: for the tests of the argument checks.
+        n_frames overrides the count passed; `null` names arguments passed as NULL ("frames", "camera", "tag", "line_vp", "results")."""
+        arr, keep = abi.vp_frames(frames)
+        nl = [int(arr[b].n_lines) for b in range(len(frames))]
+        tl = max(sum(nl), 1)
+        cam = abi.vp_camera(camera)
+        tag = np.zeros(tl, np.int32); lvp = np.zeros((tl, 3))
+        res = (abi.VpResult * max(len(frames), 1))()
+        args = dict(frames=C.cast(arr, C.POINTER(abi.VpFrame)), camera=C.byref(cam), tag=tag.ctypes.data_as(C.POINTER(C.c_int32)), line_vp=abi._dp(lvp),
+                    results=C.cast(res, C.POINTER(abi.VpResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_vp_estimate(self._h, len(frames) if n_frames is None else int(n_frames), args["frames"], args["camera"],
+                                   self.ONE_DEGREE if th_angle is None else float(th_angle), args["tag"], args["line_vp"], args["results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernels, download
+        self.last_device_ms = float(lib().uvs_vp_last_device_ms(self._h))      # HIP events around upload, kernels, download
+        off = np.r_[0, np.cumsum(nl)].astype(int)
+        return (rc, [res[b].as_dict() for b in range(len(frames))], [tag[off[b]:off[b + 1]].copy() for b in range(len(frames))],
+                [lvp[off[b]:off[b + 1]].copy() for b in range(len(frames))])
+
+    def estimate(self, frames, camera, th_angle=None):
+        """frames: list of dicts (segs [n, 4]: x1, y1, x2, y2 in pixels of the undistorted image; seed); camera = (fx, fy, cx, cy); th_angle in
+        radians (default: the reference's 1 degree).  -> (results: list of dicts with the uvs_vp_result fields, tag: list of int32 [n] with
+        0..2 or 3 for "none", line_vp: list of [n, 3] with vps[tag] / vps[tag].z or zero)."""
+        rc, res, tag, lvp = self.estimate_raw(frames, camera, th_angle)
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_vp_estimate: {lib().uvs_status_string(rc).decode()} / {lib().uvs_vp_last_error(self._h).decode()}")
+        return res, tag, lvp
+
+    def debug_frame(self, frame, camera, th_angle=None):
+        """ONE frame with the intermediate results (tests only) -> dict: the uvs_vp_result fields, hyp [37800, 3, 3], cells [37800, 3],
+        scores [37800], raw / smooth [90, 360], pair_cell [n (n - 1) / 2]."""
+        arr, keep = abi.vp_frames([frame])
+        n = int(arr[0].n_lines)
+        cam = abi.vp_camera(camera)
+        hyp = np.zeros((abi.VP_N_HYPOTHESES, 3, 3)); cells = np.zeros((abi.VP_N_HYPOTHESES, 3), np.int32); scores = np.zeros(abi.VP_N_HYPOTHESES)
+        raw = np.zeros((abi.VP_GRID_LA, abi.VP_GRID_LO)); smooth = np.zeros((abi.VP_GRID_LA, abi.VP_GRID_LO))
+        pc = np.zeros(max(n * (n - 1) // 2, 1), np.int32)
+        res = abi.VpResult()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = lib().uvs_vp_debug_frame(self._h, C.cast(arr, C.POINTER(abi.VpFrame)), C.byref(cam), self.ONE_DEGREE if th_angle is None else float(th_angle),
+                                      abi._dp(hyp), ip(cells), abi._dp(scores), abi._dp(raw), abi._dp(smooth), ip(pc), C.byref(res))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_vp_debug_frame: {lib().uvs_status_string(rc).decode()} / {lib().uvs_vp_last_error(self._h).decode()}")
+        out = res.as_dict()
+        out.update(hyp=hyp, cells=cells, scores=scores, raw=raw, smooth=smooth, pair_cell=pc[:n * (n - 1) // 2])
+        return out

@@ -228,6 +228,34 @@ def make_groundtruth_sequence(gt, seed=0, t_start=3.0, t_end=None, frame_stride=
     return seq
 
 
+def retag_vanishing_points(seq, estimate, camera):
+    """A copy of `seq` whose line messages carry ESTIMATED vanishing points instead of the simulator's true ones.
+
+    For every frame the pixel segments of its line messages are rebuilt from the normalized endpoints (x = fx m[0] + cx, y = fy m[1] + cy,
+    x = fx m[2] + cx, y = fy m[3] + cy; rows in the order of the frame's message dict) and `estimate(list of [n, 4] arrays, one per frame)`
+    -> (tags: list of int [n], line_vp: list of [n, 3]) is called ONCE with all frames (api.VanishingPointEstimator.estimate behind a closure
+    that adds the seeds, or a reference implementation); m[12:15] of every message is overwritten with its line_vp row.  `camera` =
+    (fx, fy, cx, cy).  The copy's `vp_tags` holds the tags per frame; `seq` itself is not touched."""
+    import copy
+    fx, fy, cx, cy = (float(v) for v in camera)
+    segs = []
+    for f in range(seq.n_frames):
+        m = np.array(list(seq.lines[f].values()), dtype=np.float64).reshape(-1, 15)
+        segs.append(np.stack([fx * m[:, 0] + cx, fy * m[:, 1] + cy, fx * m[:, 2] + cx, fy * m[:, 3] + cy], axis=1))
+    tags, line_vp = estimate(segs)
+    out = copy.copy(seq)
+    out.lines = []
+    for f in range(seq.n_frames):
+        d = {}
+        for k, (i, m) in enumerate(seq.lines[f].items()):
+            m = m.copy(); m[12:15] = line_vp[f][k]
+            d[i] = m
+        out.lines.append(d)
+    out.vp_tags = [np.asarray(t, dtype=np.int32).copy() for t in tags]
+    out.vp_segments = segs
+    return out
+
+
 def save(seq, path):
     out = [MAGIC, float(seq.n_frames)]
     out += list(seq.pose0.ravel()) + list(seq.sb0.ravel())
