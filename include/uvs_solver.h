@@ -616,6 +616,88 @@ double uvs_vp_last_device_ms(const uvs_vp_estimator *vp);
 int uvs_vp_debug_frame(uvs_vp_estimator *vp, const uvs_vp_frame *frame, const uvs_vp_camera *camera, double th_angle, double *hyp,
                        int32_t *cells, double *scores, double *grid_raw, double *grid_smooth, int32_t *pair_cell, uvs_vp_result *result);
 
+/* ---- keyframe features of loop closure (reference pose_graph/src/keyframe.cpp:14-41, 75-113; ThirdParty/DVision/BRIEF.cpp:39-106) ----
+ * Extracts, for a batch of 8-bit grey images in one call, what a keyframe of the pose graph carries into uvs_lc_verify: FAST 9-16 corners
+ * (threshold 20, non-maximum suppression) of the unblurred image in row-major order with their normalized coordinates (PinholeCamera::
+ * liftProjective, FP64), their 256-bit BRIEF descriptors, and the BRIEF descriptors of the frame's window points (sub-pixel (u, v)); BRIEF
+ * reads a 9 x 9 blur of the image.  A frame gives the same bits alone or in a batch, from run to run and on any machine: everything is integer
+ * arithmetic except the float32 add of BRIEF's coordinates and the FP64 of liftProjective, which is IEEE multiplies and adds in a fixed order.
+ *   blur     separable, taps {7, 17, 32, 46, 52, 46, 32, 17, 7} / 256 (exp(-k^2 / 8) normalized to 256 and rounded: sigma 2), border
+ *            reflect-101, rows then columns without rounding in between, out = (sum + 32768) >> 16
+ *   FAST     ring clockwise from the top: (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2)
+ *            (-1,-3); pixels with 3 <= x < W - 3, 3 <= y < H - 3; d_i = ring_i - centre, A = max over the 16 arcs of 9 contiguous ring pixels
+ *            of min(d_i), B the same of -d_i; a corner iff max(A, B) > 20, score max(A, B) - 1 (OpenCV's cornerScore<16>), 0 otherwise; kept
+ *            iff its score is strictly greater than the scores of its 8 neighbours
+ *   BRIEF    test i: xa = (int)(float(u) + float(x1[i])) (float32 add, truncation toward zero; -0.5 becomes 0), ya, xb, yb alike; bit i is
+ *            set iff the four are inside the image and blur[ya][xa] < blur[yb][xb]; bit i is bit (i & 63) of word (i >> 6), the layout of
+ *            uvs_lc_pair.desc / old_desc
+ *   lift     m = (u / fx - cx / fx, v / fy - cy / fy) through 1 / fx, -cx / fx, 1 / fy, -cy / fy; when a distortion coefficient is not zero,
+ *            the recursive model with 8 evaluations of distortion() (PinholeCamera.cc:450-510, 678-694)
+ * The numerics are restated in tests/kf_ref.py; DESIGN.md 3.9 lists the two deviations from the reference (the integer blur in place of
+ * cv::GaussianBlur, the keypoint cap).  The library embeds no BRIEF pattern: the caller reads it (the reference's brief_pattern.yml) and
+ * gives it to uvs_kf_create.  No CPU path: uvs_kf_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_KF_MAX_FRAMES 64                  /* largest max_frames uvs_kf_create takes */
+#define UVS_KF_MIN_SIZE 9                     /* smallest width and height of an image (one reflection covers the blur's border) */
+#define UVS_KF_MAX_WIDTH 4096                 /* largest max_width */
+#define UVS_KF_MAX_HEIGHT 4096                /* largest max_height */
+#define UVS_KF_PATTERN_BITS 256               /* tests of the BRIEF pattern = bits of a descriptor */
+#define UVS_KF_MAX_PATTERN_OFFSET 1024        /* largest |x1|, |y1|, |x2|, |y2| of the pattern */
+#define UVS_KF_MAX_COORD 1e6                  /* largest |u|, |v| of a window point, pixels */
+typedef struct uvs_kf_extractor uvs_kf_extractor;  /* opaque: device buffers, pinned staging, stream */
+
+enum {
+    UVS_KF_OK = 0,
+    UVS_KF_OVERFLOW = 1            /* more corners survive than max_keypoints: the first max_keypoints in row-major order are returned */
+};
+
+typedef struct uvs_kf_frame {
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width */
+    int32_t width;                     /* UVS_KF_MIN_SIZE .. max_width */
+    int32_t height;                    /* UVS_KF_MIN_SIZE .. max_height */
+    int32_t n_window;                  /* window points, 0 .. max_window */
+    int32_t reserved;
+    const float *window_uv;            /* [n_window][2] point_2d_uv, pixels */
+} uvs_kf_frame;
+
+typedef struct uvs_kf_camera {
+    double fx, fy, cx, cy;             /* pinhole */
+    double k1, k2, p1, p2;             /* radial-tangential distortion; all zero: none */
+} uvs_kf_camera;
+
+typedef struct uvs_kf_result {
+    int32_t status;                    /* UVS_KF_OK / UVS_KF_OVERFLOW */
+    int32_t n_keypoints;               /* corners that survive the suppression (the true count, also on overflow) */
+    int32_t n_returned;                /* min(n_keypoints, max_keypoints) */
+    int32_t n_corners_before_nms;      /* pixels with max(A, B) > 20 */
+} uvs_kf_result;
+
+/* x1, y1, x2, y2: the BRIEF pattern, UVS_KF_PATTERN_BITS offsets each.  max_keypoints <= UVS_LC_MAX_OLD and max_window <= UVS_LC_MAX_QUERY,
+ * so that what uvs_kf_extract returns always fits uvs_lc_verify.  UVS_ERR_INVALID_ARG: null pointer, a capacity < 1, max_width or max_height
+ * below UVS_KF_MIN_SIZE, a pattern offset beyond UVS_KF_MAX_PATTERN_OFFSET; UVS_ERR_CAPACITY: a capacity above its bound. */
+int uvs_kf_create(int device, int max_frames, int max_width, int max_height, int max_keypoints, int max_window,
+                  const int32_t *x1, const int32_t *y1, const int32_t *x2, const int32_t *y2, uvs_kf_extractor **out);
+void uvs_kf_destroy(uvs_kf_extractor *kf);
+const char *uvs_kf_last_error(const uvs_kf_extractor *kf);
+/* Layout of the outputs.  The keypoint arrays are STRIDED: frame f owns entries f * max_keypoints .. f * max_keypoints + n_returned - 1 of
+ * keypoints_xy[][2] (x, y), keypoint_score[], keypoints_norm[][2] and desc[][4]; entries past n_returned are not written.  window_desc[][4] is
+ * PACKED: one entry per window point, concatenated over the frames in order (as match_old of uvs_lc_verify is).  results[n_frames].
+ * The arrays of frame f go unchanged into uvs_lc_pair: window_desc -> desc (as the current keyframe), keypoints_norm -> old_uv_norm and
+ * desc -> old_desc with n_old = n_returned (as an old keyframe).
+ * UVS_ERR_INVALID_ARG: null pointer, n_frames < 1, a negative count, a null array behind a positive count, a width or height below
+ * UVS_KF_MIN_SIZE, a window point that is not finite or beyond UVS_KF_MAX_COORD, a camera that is not finite or whose fx or fy is not positive;
+ * UVS_ERR_CAPACITY: n_frames, a width, a height or n_window above the handle's capacity.  More corners than max_keypoints is not an error
+ * (UVS_KF_OVERFLOW in the frame's result).  The handle stays usable after a rejected call. */
+int uvs_kf_extract(uvs_kf_extractor *kf, int n_frames, const uvs_kf_frame *frames, const uvs_kf_camera *camera, int32_t *keypoints_xy,
+                   uint8_t *keypoint_score, double *keypoints_norm, uint64_t *desc, uint64_t *window_desc, uvs_kf_result *results);
+/* HIP-event time of the last successful uvs_kf_extract: upload, the kernels, download, on the handle's stream (milliseconds). */
+double uvs_kf_last_device_ms(const uvs_kf_extractor *kf);
+/* Diagnostic (tests only): ONE frame through the same kernels, with the whole blurred image blur[height][width] and the whole score map
+ * score[height][width] (0 where the pixel is no corner or is not examined) next to the outputs of uvs_kf_extract for that frame
+ * (keypoint arrays of max_keypoints entries, window_desc of n_window). */
+int uvs_kf_debug_frame(uvs_kf_extractor *kf, const uvs_kf_frame *frame, const uvs_kf_camera *camera, uint8_t *blur, uint8_t *score,
+                       int32_t *keypoints_xy, uint8_t *keypoint_score, double *keypoints_norm, uint64_t *desc, uint64_t *window_desc,
+                       uvs_kf_result *result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -518,3 +518,85 @@ def vp_camera(cam):
     c = VpCamera()
     c.fx, c.fy, c.cx, c.cy = (float(v) for v in cam)
     return c
+
+
+# ---- keyframe features of loop closure (uvs_kf_*, include/uvs_solver.h) ------------------------------------------------
+KF_MAX_FRAMES = 64
+KF_MIN_SIZE = 9
+KF_MAX_WIDTH = 4096
+KF_MAX_HEIGHT = 4096
+KF_PATTERN_BITS = 256
+KF_MAX_PATTERN_OFFSET = 1024
+KF_MAX_COORD = 1e6
+KF_STATUS = ["OK", "OVERFLOW"]      # uvs_kf_result.status
+c_u8_p = C.POINTER(C.c_uint8)
+c_float_p = C.POINTER(C.c_float)
+c_i32_p = C.POINTER(C.c_int32)
+
+
+class KfFrame(C.Structure):
+    _fields_ = [("image", c_u8_p), ("width", C.c_int32), ("height", C.c_int32), ("n_window", C.c_int32), ("reserved", C.c_int32),
+                ("window_uv", c_float_p)]
+
+
+class KfCamera(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+
+
+class KfResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_keypoints", C.c_int32), ("n_returned", C.c_int32), ("n_corners_before_nms", C.c_int32)]
+
+    def as_dict(self):
+        return dict(status=int(self.status), n_keypoints=int(self.n_keypoints), n_returned=int(self.n_returned),
+                    n_corners_before_nms=int(self.n_corners_before_nms))
+
+
+def kf_frames(frames):
+    """(KfFrame array, keepalive) from dicts with image [H, W] uint8 and window_uv [n, 2] float32 pixels (optional)."""
+    arr = (KfFrame * max(len(frames), 1))()
+    keep = []
+    for b, d in enumerate(frames):
+        im = np.ascontiguousarray(d["image"], dtype=np.uint8)
+        uv = np.ascontiguousarray(d.get("window_uv", np.zeros((0, 2))), dtype=np.float32).reshape(-1, 2)
+        keep += [im, uv]
+        arr[b].image = im.ctypes.data_as(c_u8_p)
+        arr[b].height, arr[b].width = im.shape
+        arr[b].n_window = len(uv)
+        arr[b].window_uv = uv.ctypes.data_as(c_float_p) if len(uv) else None
+    return arr, keep
+
+
+def kf_camera(cam):
+    """(fx, fy, cx, cy) or (fx, fy, cx, cy, k1, k2, p1, p2)."""
+    c = KfCamera()
+    v = [float(x) for x in cam] + [0.0] * (8 - len(cam))
+    c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2 = v
+    return c
+
+
+def load_brief_pattern(path):
+    """The reference's brief_pattern.yml -> int32 [4, 256] (x1, y1, x2, y2).  The file is a flat YAML of four integer lists (`key:` then
+    `  - value` lines, or an inline `[a, b, ..]`), so it is parsed here without a YAML library."""
+    lists, key = {}, None
+    with open(path) as f:
+        for line in f:
+            s = line.split("#", 1)[0].strip()
+            if not s or s.startswith("%") or s == "---":
+                continue
+            if s.startswith("-"):
+                if key is None:
+                    raise ValueError(f"{path}: a list item before any key")
+                lists[key] += [int(v) for v in s[1:].replace(",", " ").split()]
+            elif ":" in s:
+                key, rest = (t.strip() for t in s.split(":", 1))
+                lists[key] = [int(v) for v in rest.strip("[]").replace(",", " ").split()]
+            else:                                            # the continuation of an inline list
+                lists[key] += [int(v) for v in s.strip("[]").replace(",", " ").split()]
+    try:
+        pat = np.array([lists[k] for k in ("x1", "y1", "x2", "y2")], dtype=np.int32)
+    except (KeyError, ValueError) as e:
+        raise ValueError(f"{path}: x1, y1, x2, y2 must be four integer lists of equal length") from e
+    if pat.shape != (4, KF_PATTERN_BITS):
+        raise ValueError(f"{path}: {pat.shape[1]} tests per list, {KF_PATTERN_BITS} expected")
+    return pat

@@ -22,6 +22,7 @@ EXPORTS = [
     "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step",
     "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify",
     "uvs_vp_create", "uvs_vp_destroy", "uvs_vp_last_error", "uvs_vp_estimate", "uvs_vp_last_device_ms", "uvs_vp_debug_frame",
+    "uvs_kf_create", "uvs_kf_destroy", "uvs_kf_last_error", "uvs_kf_extract", "uvs_kf_last_device_ms", "uvs_kf_debug_frame",
 ]
 
 
@@ -101,6 +102,16 @@ def lib():
         L.uvs_vp_debug_frame.argtypes = [C.c_void_p, C.POINTER(abi.VpFrame), C.POINTER(abi.VpCamera), C.c_double, abi.c_double_p, C.POINTER(C.c_int32),
                                          abi.c_double_p, abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32), C.POINTER(abi.VpResult)]
         L.uvs_vp_debug_frame.restype = C.c_int
+        L.uvs_kf_create.argtypes = [C.c_int] * 6 + [abi.c_i32_p] * 4 + [C.POINTER(C.c_void_p)]; L.uvs_kf_create.restype = C.c_int
+        L.uvs_kf_destroy.argtypes = [C.c_void_p]; L.uvs_kf_destroy.restype = None
+        L.uvs_kf_last_error.argtypes = [C.c_void_p]; L.uvs_kf_last_error.restype = C.c_char_p
+        L.uvs_kf_extract.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KfFrame), C.POINTER(abi.KfCamera), abi.c_i32_p, abi.c_u8_p, abi.c_double_p,
+                                     abi.c_u64_p, abi.c_u64_p, C.POINTER(abi.KfResult)]
+        L.uvs_kf_extract.restype = C.c_int
+        L.uvs_kf_last_device_ms.argtypes = [C.c_void_p]; L.uvs_kf_last_device_ms.restype = C.c_double
+        L.uvs_kf_debug_frame.argtypes = [C.c_void_p, C.POINTER(abi.KfFrame), C.POINTER(abi.KfCamera), abi.c_u8_p, abi.c_u8_p, abi.c_i32_p, abi.c_u8_p,
+                                         abi.c_double_p, abi.c_u64_p, abi.c_u64_p, C.POINTER(abi.KfResult)]
+        L.uvs_kf_debug_frame.restype = C.c_int
         _lib = L
     return _lib
 
@@ -589,4 +600,98 @@ class VanishingPointEstimator:
             raise RuntimeError(f"uvs_vp_debug_frame: {lib().uvs_status_string(rc).decode()} / {lib().uvs_vp_last_error(self._h).decode()}")
         out = res.as_dict()
         out.update(hyp=hyp, cells=cells, scores=scores, raw=raw, smooth=smooth, pair_cell=pc[:n * (n - 1) // 2])
+        return out
+
+
+class KeyframeExtractor:
+    """Owns one `uvs_kf_extractor` handle: the features of a pose-graph keyframe (computeWindowBRIEFPoint / computeBRIEFPoint of the reference's
+    keyframe.cpp: FAST corners, BRIEF descriptors, normalized keypoints) on one GPU, a batch of images per call.
+
+    `pattern` is the BRIEF pattern as int32 [4, 256] (x1, y1, x2, y2), e.g. abi.load_brief_pattern("brief_pattern.yml").
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    def __init__(self, pattern, device=0, max_frames=16, max_width=752, max_height=480, max_keypoints=4096, max_window=1024):
+        pat = np.ascontiguousarray(pattern, dtype=np.int32)
+        if pat.shape != (4, abi.KF_PATTERN_BITS):
+            raise ValueError(f"pattern must be [4, {abi.KF_PATTERN_BITS}] (x1, y1, x2, y2)")
+        self.max_keypoints = int(max_keypoints)
+        self._h = C.c_void_p()
+        rc = lib().uvs_kf_create(device, max_frames, max_width, max_height, max_keypoints, max_window,
+                                 *[pat[k].ctypes.data_as(abi.c_i32_p) for k in range(4)], C.byref(self._h))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_kf_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
+
+    def close(self):
+        if self._h:
+            lib().uvs_kf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _outputs(self, n_frames, n_window):
+        K = max(n_frames, 1) * self.max_keypoints
+        return dict(xy=np.zeros((K, 2), np.int32), score=np.zeros(K, np.uint8), norm=np.zeros((K, 2)), desc=np.zeros((K, 4), np.uint64),
+                    wdesc=np.zeros((max(n_window, 1), 4), np.uint64))
+
+    def _split(self, o, res, nw):
+        """The strided keypoint arrays and the packed window descriptors as one dict per frame."""
+        off = np.r_[0, np.cumsum(nw)].astype(int)
+        out = []
+        for b, r in enumerate(res):
+            d = r.as_dict()
+            s = slice(b * self.max_keypoints, b * self.max_keypoints + d["n_returned"])
+            d.update(xy=o["xy"][s].copy(), score=o["score"][s].copy(), norm=o["norm"][s].copy(), desc=o["desc"][s].copy(),
+                     window_desc=o["wdesc"][off[b]:off[b + 1]].copy())
+            out.append(d)
+        return out
+
+    def extract_raw(self, frames, camera, n_frames=None, null=()):
+        """-> (return code, [dict per frame]) without raising: for the tests of the argument checks.  n_frames overrides the count passed;
+        `null` names arguments passed as NULL ("frames", "camera", "xy", "score", "norm", "desc", "wdesc", "results")."""
+        arr, keep = abi.kf_frames(frames)
+        nw = [int(arr[b].n_window) for b in range(len(frames))]
+        cam = abi.kf_camera(camera)
+        o = self._outputs(len(frames), sum(nw))
+        res = (abi.KfResult * max(len(frames), 1))()
+        args = dict(frames=C.cast(arr, C.POINTER(abi.KfFrame)), camera=C.byref(cam), xy=o["xy"].ctypes.data_as(abi.c_i32_p),
+                    score=o["score"].ctypes.data_as(abi.c_u8_p), norm=abi._dp(o["norm"]), desc=o["desc"].ctypes.data_as(abi.c_u64_p),
+                    wdesc=o["wdesc"].ctypes.data_as(abi.c_u64_p), results=C.cast(res, C.POINTER(abi.KfResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_kf_extract(self._h, len(frames) if n_frames is None else int(n_frames), args["frames"], args["camera"], args["xy"],
+                                  args["score"], args["norm"], args["desc"], args["wdesc"], args["results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: repacking, upload, kernels, download
+        self.last_device_ms = float(lib().uvs_kf_last_device_ms(self._h))      # HIP events around upload, kernels, download
+        return rc, (self._split(o, [res[b] for b in range(len(frames))], nw) if rc == abi.UVS_OK else [])
+
+    def extract(self, frames, camera):
+        """frames: list of dicts (image [H, W] uint8; window_uv [n, 2] float32 pixels, optional); camera = (fx, fy, cx, cy[, k1, k2, p1, p2]).
+        -> one dict per frame: status, n_keypoints, n_returned, n_corners_before_nms, xy [n, 2] int32 in row-major order, score [n] uint8,
+        norm [n, 2] float64, desc [n, 4] uint64, window_desc [n_window, 4] uint64.  norm / desc are what uvs_lc_verify takes as uv / odesc
+        of an old keyframe, window_desc as qdesc of the current one."""
+        rc, out = self.extract_raw(frames, camera)
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_kf_extract: {lib().uvs_status_string(rc).decode()} / {lib().uvs_kf_last_error(self._h).decode()}")
+        return out
+
+    def debug_frame(self, frame, camera):
+        """ONE frame with the whole blurred image and the whole score map (tests only) -> the frame's dict of extract() plus blur, score_map."""
+        arr, keep = abi.kf_frames([frame])
+        H, W, nw = int(arr[0].height), int(arr[0].width), int(arr[0].n_window)
+        cam = abi.kf_camera(camera)
+        o = self._outputs(1, nw)
+        blur = np.zeros((H, W), np.uint8); smap = np.zeros((H, W), np.uint8)
+        res = abi.KfResult()
+        rc = lib().uvs_kf_debug_frame(self._h, C.cast(arr, C.POINTER(abi.KfFrame)), C.byref(cam), blur.ctypes.data_as(abi.c_u8_p),
+                                      smap.ctypes.data_as(abi.c_u8_p), o["xy"].ctypes.data_as(abi.c_i32_p), o["score"].ctypes.data_as(abi.c_u8_p),
+                                      abi._dp(o["norm"]), o["desc"].ctypes.data_as(abi.c_u64_p), o["wdesc"].ctypes.data_as(abi.c_u64_p), C.byref(res))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_kf_debug_frame: {lib().uvs_status_string(rc).decode()} / {lib().uvs_kf_last_error(self._h).decode()}")
+        out = self._split(o, [res], [nw])[0]
+        out.update(blur=blur, score_map=smap)
         return out

@@ -11,6 +11,32 @@ void KeyFrame::updateLoop(const LoopInfo& info) {          // keyframe.cpp:571-5
     if (std::fabs(info[7]) < 30.0 && std::sqrt(info[0] * info[0] + info[1] * info[1] + info[2] * info[2]) < 20.0) loop_info = info;
 }
 
+KeyFrame::KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R, const uint8_t* image, int width, int height,
+                   const std::vector<Eigen::Vector3d>& point_3d_, const std::vector<std::array<float, 2>>& point_2d_uv_,
+                   const std::vector<std::array<double, 2>>& point_2d_norm_, const std::vector<double>& point_id_, int sequence_,
+                   uvs_kf_extractor* extractor, const uvs_kf_camera& camera)
+    : KeyFrame(stamp, sequence_, vio_T, vio_R) {             // keyframe.cpp:14-41
+    index = index_;
+    point_3d = point_3d_; point_2d_uv = point_2d_uv_; point_2d_norm = point_2d_norm_; point_id = point_id_;
+    uvs_kf_frame fr;
+    fr.image = image; fr.width = width; fr.height = height; fr.n_window = (int)point_2d_uv.size(); fr.reserved = 0;
+    fr.window_uv = point_2d_uv.empty() ? nullptr : point_2d_uv[0].data();
+    // one frame: the strided keypoint arrays start at 0, and no handle returns more than UVS_LC_MAX_OLD keypoints
+    std::vector<std::array<int32_t, 2>> xy(UVS_LC_MAX_OLD);
+    std::vector<uint8_t> score(UVS_LC_MAX_OLD);
+    std::vector<std::array<double, 2>> norm(UVS_LC_MAX_OLD);
+    std::vector<std::array<uint64_t, 4>> desc(UVS_LC_MAX_OLD);
+    window_brief_descriptors.resize(std::max<size_t>(point_2d_uv.size(), 1));
+    const int rc = uvs_kf_extract(extractor, 1, &fr, &camera, xy[0].data(), score.data(), norm[0].data(), desc[0].data(),
+                                  window_brief_descriptors[0].data(), &last_extract);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_kf_extract: ") + uvs_status_string(rc) + " / " + uvs_kf_last_error(extractor));
+    window_brief_descriptors.resize(point_2d_uv.size());
+    const size_t n = (size_t)last_extract.n_returned;
+    keypoints.assign(xy.begin(), xy.begin() + n);
+    keypoints_norm.assign(norm.begin(), norm.begin() + n);
+    brief_descriptors.assign(desc.begin(), desc.begin() + n);
+}
+
 bool KeyFrame::findConnection(KeyFrame* old_kf, uvs_loop_verifier* lc, const Eigen::Vector3d& tic, const Eigen::Quaterniond& qic) {
     const int n = (int)point_3d.size();
     std::vector<double> p3d(3 * (size_t)n);

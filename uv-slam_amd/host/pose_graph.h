@@ -1,10 +1,11 @@
 // pose_graph.h -- mirror of the optimizer half of pose_graph/src/pose_graph.{h,cpp} and keyframe.{h,cpp} (loop closure): the keyframe list,
 // the sequence shift and drift bookkeeping of addKeyFrame (:42-211), updateKeyFrameLoop (:888-...) / KeyFrame::updateLoop (keyframe.cpp:571-578)
 // and a synchronous optimize4DoF (:403-579) whose ceres::Solve is uvs_pg_optimize(); KeyFrame::findConnection (keyframe.cpp:259-521: BRIEF
-// matching, PnP-RANSAC, the loop_info gates) runs on the GPU through uvs_lc_verify().  Place recognition (DBoW2 detectLoop) and BRIEF / FAST
-// extraction are not mirrored: addKeyFrameWithCandidate takes the candidate detectLoop would return, keyframes carry their descriptors and
-// normalized keypoints as the caller extracted them, and addKeyFrame still takes a loop as the caller found it.  No polling thread, no save /
-// load, no visualization.
+// matching, PnP-RANSAC, the loop_info gates) runs on the GPU through uvs_lc_verify(), and the online KeyFrame constructor (keyframe.cpp:14-41:
+// computeWindowBRIEFPoint, computeBRIEFPoint) extracts FAST corners, BRIEF descriptors and normalized keypoints from the image on the GPU
+// through uvs_kf_extract().  Place recognition (DBoW2 detectLoop) is not mirrored: addKeyFrameWithCandidate takes the candidate detectLoop
+// would return, and addKeyFrame still takes a loop as the caller found it.  A keyframe may also carry descriptors and normalized keypoints
+// as the caller extracted them (the first constructor).  No thumbnail, no polling thread, no save / load, no visualization.
 #pragma once
 #include <array>
 #include <list>
@@ -29,11 +30,14 @@ struct KeyFrame {
     Eigen::Vector3d origin_vio_T;
     Eigen::Matrix3d origin_vio_R = Eigen::Matrix3d::Identity();
     std::vector<Eigen::Vector3d> point_3d;
+    std::vector<std::array<float, 2>> point_2d_uv;         // cv::Point2f pixels (the online constructor's)
     std::vector<std::array<double, 2>> point_2d_norm;
     std::vector<double> point_id;
     std::vector<std::array<uint64_t, 4>> window_brief_descriptors;
     std::vector<std::array<double, 2>> keypoints_norm;
     std::vector<std::array<uint64_t, 4>> brief_descriptors;
+    std::vector<std::array<int32_t, 2>> keypoints;         // FAST corners (x, y) in row-major order (the online constructor's)
+    uvs_kf_result last_extract{};                          // counts and status of the online constructor's uvs_kf_extract
     // findConnection's inlier matches (matched_2d_old_norm, matched_id: what Estimator::setReloFrame takes) and its verdict
     std::vector<std::array<double, 2>> matched_2d_old_norm;
     std::vector<double> matched_id;
@@ -41,6 +45,14 @@ struct KeyFrame {
 
     KeyFrame(double stamp, int seq, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R)
         : time_stamp(stamp), sequence(seq), vio_T_w_i(vio_T), T_w_i(vio_T), vio_R_w_i(vio_R), R_w_i(vio_R), origin_vio_T(vio_T), origin_vio_R(vio_R) {}
+    // "create keyframe online" (keyframe.cpp:14-41): window_brief_descriptors at point_2d_uv (computeWindowBRIEFPoint, :75-85), then keypoints,
+    // brief_descriptors and keypoints_norm of the image's FAST corners (computeBRIEFPoint, :87-113), in one uvs_kf_extract call.  `image` is
+    // width x height grey levels and is not kept.  On UVS_KF_OVERFLOW the keyframe carries the extractor's first max_keypoints corners
+    // (last_extract.status tells).  Throws std::runtime_error when the call fails.
+    KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R, const uint8_t* image, int width, int height,
+             const std::vector<Eigen::Vector3d>& point_3d_, const std::vector<std::array<float, 2>>& point_2d_uv_,
+             const std::vector<std::array<double, 2>>& point_2d_norm_, const std::vector<double>& point_id_, int sequence_,
+             uvs_kf_extractor* extractor, const uvs_kf_camera& camera);
     void getVioPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = vio_T_w_i; R = vio_R_w_i; }
     void getPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = T_w_i; R = R_w_i; }
     void updatePose(const Eigen::Vector3d& P, const Eigen::Matrix3d& R) { T_w_i = P; R_w_i = R; }

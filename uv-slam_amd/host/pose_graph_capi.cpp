@@ -3,6 +3,7 @@
 // out_pose[n][7] = corrected (P, q x y z w) of every keyframe, out_drift[4] = (yaw_drift, t_drift), out_yaw_t[m][4] = the solve's raw output
 // for the m keyframes first_looped_index .. cur_index (m returned through *out_m); tum_path (may be NULL) receives the corrected path.
 // uvs_host_pose_graph_verify_run (below): the same stream with loop candidates instead of loops, verified on the GPU by findConnection.
+// uvs_host_pose_graph_image_run (last): the same again from IMAGES: every keyframe extracts its own descriptors and keypoints on the GPU.
 #include <cstdio>
 #include <stdexcept>
 #include "pose_graph.h"
@@ -91,4 +92,75 @@ extern "C" int uvs_host_pose_graph_verify_run(int device, int n, const double* s
         return UVS_ERR_NO_DEVICE;
     }
     return UVS_OK;
+}
+
+// Test hook: image to loop edge through the mirrored PoseGraph.  Keyframe k is built by the online constructor from images[k] (width x height
+// grey levels) and its window points (n_query[k] of them: p3d[.][3] in its VIO frame, uv[.][2] pixels; concatenated over k), so its descriptors
+// and keypoints come from uvs_kf_extract (pattern[4][256] = x1 | y1 | x2 | y2; a handle of max_keypoints); candidate[k] = what detectLoop would
+// return (-1: none).  Every keyframe goes through addKeyFrameWithCandidate; then optimize4DoF runs at the last keyframe with an accepted loop.
+// out_accepted[n], out_loop_info[n][8] (zeros without a loop), out_pose[n][7] = corrected (P, q x y z w), out_n_kp[n] = keypoints of
+// keyframe k, out_kp_norm[n][max_keypoints][2] / out_kp_desc[n][max_keypoints][4] = its keypoints_norm / brief_descriptors,
+// out_window_desc[.][4] = its window_brief_descriptors, concatenated over k.
+extern "C" int uvs_host_pose_graph_image_run(int device, int n, const double* stamps, const double* t, const double* q_xyzw, const int* sequence,
+                                             const double* tic, const double* qic_xyzw, const uvs_kf_camera* camera, const int32_t* pattern,
+                                             int max_keypoints, int width, int height, const uint8_t* images, const int* n_query, const double* p3d,
+                                             const float* uv, const int* candidate, int* out_accepted, double* out_loop_info, double* out_pose,
+                                             int* out_n_kp, double* out_kp_norm, uint64_t* out_kp_desc, uint64_t* out_window_desc) {
+    if (n < 1 || !stamps || !t || !q_xyzw || !sequence || !tic || !qic_xyzw || !camera || !pattern || !images || !n_query || !candidate || !out_accepted ||
+        !out_loop_info || !out_pose || !out_n_kp || !out_kp_norm || !out_kp_desc || !out_window_desc)
+        return UVS_ERR_INVALID_ARG;
+    uvs_kf_extractor* kf = nullptr;
+    int rc = uvs_kf_create(device, 1, width, height, max_keypoints, UVS_LC_MAX_QUERY, pattern, pattern + UVS_KF_PATTERN_BITS,
+                           pattern + 2 * UVS_KF_PATTERN_BITS, pattern + 3 * UVS_KF_PATTERN_BITS, &kf);
+    if (rc != UVS_OK) return rc;
+    rc = UVS_OK;
+    try {
+        PoseGraph graph(device, n, 256);
+        graph.setExtrinsic(Eigen::Vector3d(tic[0], tic[1], tic[2]), Eigen::Quaterniond(qic_xyzw[3], qic_xyzw[0], qic_xyzw[1], qic_xyzw[2]));
+        size_t qo = 0;
+        int last_loop = -1;
+        for (int k = 0; k < n && rc == UVS_OK; ++k) {
+            const Eigen::Quaterniond Q(q_xyzw[4 * k + 3], q_xyzw[4 * k], q_xyzw[4 * k + 1], q_xyzw[4 * k + 2]);
+            std::vector<Eigen::Vector3d> point_3d;
+            std::vector<std::array<float, 2>> point_2d_uv;
+            std::vector<double> point_id;
+            for (int i = 0; i < n_query[k]; ++i, ++qo) {
+                point_3d.push_back(Eigen::Vector3d(p3d[3 * qo], p3d[3 * qo + 1], p3d[3 * qo + 2]));
+                point_2d_uv.push_back({uv[2 * qo], uv[2 * qo + 1]});
+                point_id.push_back((double)i);
+            }
+            KeyFrame* kfr = new KeyFrame(stamps[k], k, Eigen::Vector3d(t[3 * k], t[3 * k + 1], t[3 * k + 2]), Q.toRotationMatrix(),
+                                         images + (size_t)k * width * height, width, height, point_3d, point_2d_uv, {}, point_id, sequence[k], kf, *camera);
+            out_n_kp[k] = (int)kfr->keypoints_norm.size();
+            for (size_t i = 0; i < kfr->keypoints_norm.size(); ++i) {
+                const size_t o = (size_t)k * max_keypoints + i;
+                for (int c = 0; c < 2; ++c) out_kp_norm[2 * o + c] = kfr->keypoints_norm[i][c];
+                for (int c = 0; c < 4; ++c) out_kp_desc[4 * o + c] = kfr->brief_descriptors[i][c];
+            }
+            for (size_t i = 0; i < kfr->window_brief_descriptors.size(); ++i)
+                for (int c = 0; c < 4; ++c) out_window_desc[4 * (qo - kfr->window_brief_descriptors.size() + i) + c] = kfr->window_brief_descriptors[i][c];
+            const bool acc = graph.addKeyFrameWithCandidate(kfr, candidate[k]);      // the graph owns kfr from here
+            if (kfr->last_verify.reason < 0) { std::fprintf(stderr, "findConnection: uvs_lc_verify failed at keyframe %d\n", k); rc = UVS_ERR_INVALID_ARG; break; }
+            out_accepted[k] = acc;
+            for (int c = 0; c < 8; ++c) out_loop_info[8 * k + c] = acc ? kfr->loop_info[c] : 0.0;
+            if (acc) last_loop = kfr->index;
+        }
+        if (rc == UVS_OK && last_loop >= 0) {
+            rc = graph.optimize4DoF(last_loop);
+            if (rc != UVS_OK) std::fprintf(stderr, "optimize4DoF: %s\n", graph.last_error.c_str());
+        }
+        int k = 0;
+        if (rc == UVS_OK)
+            for (const KeyFrame* f : graph.keyframelist) {
+                const Eigen::Quaterniond Q(f->R_w_i);
+                const double v[7] = {f->T_w_i.x(), f->T_w_i.y(), f->T_w_i.z(), Q.x(), Q.y(), Q.z(), Q.w()};
+                for (int c = 0; c < 7; ++c) out_pose[7 * k + c] = v[c];
+                ++k;
+            }
+    } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        rc = UVS_ERR_NO_DEVICE;
+    }
+    uvs_kf_destroy(kf);
+    return rc;
 }
