@@ -698,6 +698,100 @@ int uvs_kf_debug_frame(uvs_kf_extractor *kf, const uvs_kf_frame *frame, const uv
                        int32_t *keypoints_xy, uint8_t *keypoint_score, double *keypoints_norm, uint64_t *desc, uint64_t *window_desc,
                        uvs_kf_result *result);
 
+/* ---- point tracking of the point front end (reference feature_tracker/src/feature_tracker.cpp:54-147: cv::calcOpticalFlowPyrLK(cur_img,
+ * forw_img, cur_pts, forw_pts, status, err, cv::Size(21, 21), 3) at :86, inBorder at :93-95 / utility.cpp:3-9, liftProjective of
+ * undistortedPoints at :240-288) ----
+ * A handle is a tracker with max_streams slots.  Each slot keeps the image pyramid of the last image it was given resident on the device (two
+ * buffers per slot, swapped: an image is uploaded and reduced once).  One call takes a batch of items, at most one per slot: it builds the new
+ * image's pyramid, tracks the item's points from the slot's stored pyramid into it with pyramidal Lucas-Kanade (21 x 21 window, at most 30
+ * iterations per level), and makes the new pyramid the slot's stored one.  A slot that holds nothing (fresh, or after uvs_ft_reset) only stores
+ * the pyramid.  An item gives the same bits alone or in a batch, from run to run and on any machine: every sum over the window is an integer
+ * sum (exact in any order), and the FP64 operations of an iteration are the few below, in the order written (no fused multiply-add).
+ *
+ * Conventions: refl(i, n) is reflect-101 (-i for i < 0, 2 n - 2 - i for i >= n); >> is an arithmetic shift; rint rounds half to even.
+ *   pyramid   level 0 is the image; level l + 1 has size ((W + 1) / 2, (H + 1) / 2);
+ *             out(x, y) = (sum_{i, j = -2..2} k_i k_j in(refl(2 x + i), refl(2 y + j)) + 128) >> 8, k = {1, 4, 6, 4, 1}
+ *   gradient  Scharr: Gx(x, y) = 3 (p(x+1, y-1) - p(x-1, y-1)) + 10 (p(x+1, y) - p(x-1, y)) + 3 (p(x+1, y+1) - p(x-1, y+1)), Gy the transpose;
+ *             every read of p goes through refl, also where (x, y) itself lies outside the image (the gradient of the reflected image)
+ *   window    sample of an image P (a level, its Gx or its Gy) at the FP64 position c:  u = c - 10, iu = floor(u), a = u.x - iu.x, b = u.y - iu.y,
+ *             w00 = rint((1 - a) (1 - b) 16384), w01 = rint(a (1 - b) 16384), w10 = rint((1 - a) b 16384), w11 = 16384 - w00 - w01 - w10;
+ *             for x, y = 0..20: S(x, y) = w00 P(iu.x + x, iu.y + y) + w01 P(iu.x + x + 1, iu.y + y) + w10 P(iu.x + x, iu.y + y + 1)
+ *             + w11 P(iu.x + x + 1, iu.y + y + 1); grey levels: (S + 256) >> 9 (5 fractional bits); gradients: (S + 8192) >> 14
+ *   a point p, levels l = levels - 1 .. 0, with p_l = p 2^-l and W_l x H_l the level's size:
+ *             the estimate q starts at p_l on the coarsest level and is doubled on the way down.
+ *             p_l outside [0, W_l - 1] x [0, H_l - 1]: LOST_OUTSIDE.
+ *             I, Dx, Dy = the window samples of the previous pyramid's level, Gx and Gy at p_l.
+ *             A11 = sum Dx^2, A12 = sum Dx Dy, A22 = sum Dy^2 as int64 (up to 441 x 4080^2 = 7.3e9); converted to FP64 and multiplied by 2^-20.
+ *             D = A11 A22 - A12 A12;  minEig = (A22 + A11 - sqrt((A11 - A22) (A11 - A22) + 4 A12 A12)) / 882.
+ *             minEig < 1e-4 or D < 1.1920929e-7: a level above 0 is skipped with q unchanged, at level 0 the point is LOST_FLAT.
+ *             iterations j = 0..29:  q outside the level's image: LOST_OUTSIDE.  J = the window sample of the new pyramid's level at q;
+ *               b1 = sum (J - I) Dx, b2 = sum (J - I) Dy as int64, times 2^-20;
+ *               delta = ((A12 b2 - A22 b1) / D, (A12 b1 - A11 b2) / D);  q += delta;  stop if delta . delta <= 1e-4;
+ *               if j > 0 and |delta.x + prev.x| < 0.01 and |delta.y + prev.y| < 0.01: q -= 0.5 delta, then stop (prev = the delta before).
+ *             after level 0:  q outside the image: LOST_OUTSIDE;  xr = rint(q.x), yr = rint(q.y): TRACKED iff 1 <= xr < W - 1 and
+ *             1 <= yr < H - 1 (the reference's inBorder), LOST_BORDER otherwise.
+ *             next_xy is written for every status: the last q, scaled to level 0 (times 2^l where the point was lost at level l).
+ * The numerics are restated in tests/ft_ref.py, which the device is held to bit for bit; DESIGN.md 3.10 lists the deviations from
+ * cv::calcOpticalFlowPyrLK.  No CPU path: uvs_ft_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_FT_MAX_STREAMS 64                 /* largest max_streams uvs_ft_create takes */
+#define UVS_FT_MAX_LEVELS 4                   /* levels: 1 .. 4 (the reference's maxLevel = 3 is 4 levels) */
+#define UVS_FT_MIN_SIZE 24                    /* smallest width and height of the coarsest level: an image is at least 24 << (levels - 1) */
+#define UVS_FT_MAX_POINTS 8192                /* largest max_points (points of one item) */
+#define UVS_FT_WINDOW 21                      /* winSize */
+#define UVS_FT_MAX_ITERATIONS 30              /* iterations per level */
+#define UVS_FT_TRACE_HEADER 16                /* uvs_ft_debug_point: doubles at the head of a level's trace */
+#define UVS_FT_TRACE_ITER 10                  /* ... of one iteration */
+#define UVS_FT_TRACE_LEVEL 320                /* ... of one level: 16 + 30 x 10, padded */
+typedef struct uvs_ft_tracker uvs_ft_tracker;      /* opaque: the slots' pyramids, device buffers, pinned staging, stream */
+
+enum {
+    UVS_FT_TRACKED = 0,
+    UVS_FT_LOST_FLAT = 1,          /* no texture in the window at level 0 */
+    UVS_FT_LOST_OUTSIDE = 2,       /* the point or its estimate left the image */
+    UVS_FT_LOST_BORDER = 3         /* converged onto the outermost pixel ring (inBorder) */
+};
+
+typedef struct uvs_ft_item {
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width: the slot's NEW image */
+    int32_t stream;                    /* the slot, 0 .. max_streams - 1; at most once per call */
+    int32_t width;                     /* 24 << (levels - 1) .. max_width; fixed by the slot's first image until uvs_ft_reset */
+    int32_t height;                    /* 24 << (levels - 1) .. max_height */
+    int32_t n_points;                  /* 0 .. max_points; 0 for a slot that holds nothing */
+    const double *points_xy;           /* [n_points][2] pixels in the slot's PREVIOUS image, finite and within UVS_KF_MAX_COORD */
+} uvs_ft_item;
+
+/* UVS_ERR_INVALID_ARG: null out, a capacity < 1, levels outside 1..4, max_width or max_height below 24 << (levels - 1);
+ * UVS_ERR_CAPACITY: max_streams > UVS_FT_MAX_STREAMS, max_width > UVS_KF_MAX_WIDTH, max_height > UVS_KF_MAX_HEIGHT, max_points > UVS_FT_MAX_POINTS. */
+int uvs_ft_create(int device, int max_streams, int max_width, int max_height, int levels, int max_points, uvs_ft_tracker **out);
+void uvs_ft_destroy(uvs_ft_tracker *ft);
+const char *uvs_ft_last_error(const uvs_ft_tracker *ft);
+/* Empties a slot: its next image may have another size and must come without points. */
+int uvs_ft_reset(uvs_ft_tracker *ft, int stream);
+/* The outputs are PACKED over the items in order (as window_desc of uvs_kf_extract is): next_xy[][2], status[] (UVS_FT_*), iterations[] (the
+ * iterations run at level 0), next_norm[][2] (liftProjective of next_xy through `camera`, the uvs_kf_camera of uvs_kf_extract, for TRACKED
+ * points; zero for the others); results[n_items] = the number of TRACKED points of each item.
+ * UVS_ERR_INVALID_ARG: null pointer, n_items < 1, a negative count, a null array behind a positive count, a stream outside the handle's slots
+ * or given twice, points for a slot that holds nothing, a size that differs from the slot's without a reset, a width or height below
+ * 24 << (levels - 1), a point that is not finite or beyond UVS_KF_MAX_COORD, a camera that is not finite or whose fx or fy is not positive;
+ * UVS_ERR_CAPACITY: n_items, a width, a height or n_points above the handle's capacity.  A rejected call changes no slot, and the handle
+ * stays usable after it. */
+int uvs_ft_track(uvs_ft_tracker *ft, int n_items, const uvs_ft_item *items, const uvs_kf_camera *camera, double *next_xy, int32_t *status,
+                 int32_t *iterations, double *next_norm, int32_t *results);
+/* HIP-event time of the last successful uvs_ft_track: upload, the kernels, download, on the handle's stream (milliseconds). */
+double uvs_ft_last_device_ms(const uvs_ft_tracker *ft);
+/* Diagnostic (tests only): the stored pyramid of a slot.  level_sizes[levels][2] = (width, height) of each level; pixels receives the levels
+ * one after the other, each [height_l][width_l] with stride width_l (capacity: pixels_capacity bytes, UVS_ERR_CAPACITY when too small).
+ * UVS_ERR_INVALID_ARG for a slot that holds nothing. */
+int uvs_ft_debug_pyramid(uvs_ft_tracker *ft, int stream, int32_t *level_sizes, uint8_t *pixels, int64_t pixels_capacity);
+/* Diagnostic (tests only): ONE item with ONE point through the same kernels as uvs_ft_track (the slot's state advances as it does there), with
+ * every intermediate value: trace[UVS_FT_MAX_LEVELS][UVS_FT_TRACE_LEVEL], level l at trace[l]; entries of a level that was not visited are 0.
+ *   [0] 1 when the level was visited   [1..2] p_l   [3..6] w00 w01 w10 w11 of the window at p_l   [7..9] A11 A12 A22 (the integer sums)
+ *   [10] D   [11] minEig   [12] 1 when the level was flat   [13] iterations run   [14..15] q when the level was left
+ *   [16 + 10 j ..] iteration j: w00 w01 w10 w11 of the window at q, b1 b2 (the integer sums), delta.x delta.y, q.x q.y after the step
+ * next_xy[2], status, iterations, next_norm[2] as uvs_ft_track returns them. */
+int uvs_ft_debug_point(uvs_ft_tracker *ft, const uvs_ft_item *item, const uvs_kf_camera *camera, double *trace, double *next_xy,
+                       int32_t *status, int32_t *iterations, double *next_norm);
+
 #ifdef __cplusplus
 }
 #endif

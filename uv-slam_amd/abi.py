@@ -600,3 +600,38 @@ def load_brief_pattern(path):
     if pat.shape != (4, KF_PATTERN_BITS):
         raise ValueError(f"{path}: {pat.shape[1]} tests per list, {KF_PATTERN_BITS} expected")
     return pat
+
+
+# ---- point tracking of the point front end (uvs_ft_*, include/uvs_solver.h) -----------------------------------------------
+FT_MAX_STREAMS = 64
+FT_MAX_LEVELS = 4
+FT_MIN_SIZE = 24
+FT_MAX_POINTS = 8192
+FT_WINDOW = 21
+FT_MAX_ITERATIONS = 30
+FT_TRACE_HEADER = 16
+FT_TRACE_ITER = 10
+FT_TRACE_LEVEL = 320
+FT_STATUS = ["TRACKED", "LOST_FLAT", "LOST_OUTSIDE", "LOST_BORDER"]      # status[] of uvs_ft_track
+
+
+class FtItem(C.Structure):
+    _fields_ = [("image", c_u8_p), ("stream", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_points", C.c_int32),
+                ("points_xy", c_double_p)]
+
+
+def ft_items(items):
+    """(FtItem array, keepalive) from dicts with stream, image [H, W] uint8 and points [n, 2] float64 pixels of the slot's previous image
+    (optional)."""
+    arr = (FtItem * max(len(items), 1))()
+    keep = []
+    for b, d in enumerate(items):
+        im = np.ascontiguousarray(d["image"], dtype=np.uint8)
+        pts = np.ascontiguousarray(d.get("points", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
+        keep += [im, pts]
+        arr[b].image = im.ctypes.data_as(c_u8_p)
+        arr[b].stream = int(d.get("stream", 0))
+        arr[b].height, arr[b].width = im.shape
+        arr[b].n_points = len(pts)
+        arr[b].points_xy = pts.ctypes.data_as(c_double_p) if len(pts) else None
+    return arr, keep

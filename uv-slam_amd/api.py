@@ -23,6 +23,7 @@ EXPORTS = [
     "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify",
     "uvs_vp_create", "uvs_vp_destroy", "uvs_vp_last_error", "uvs_vp_estimate", "uvs_vp_last_device_ms", "uvs_vp_debug_frame",
     "uvs_kf_create", "uvs_kf_destroy", "uvs_kf_last_error", "uvs_kf_extract", "uvs_kf_last_device_ms", "uvs_kf_debug_frame",
+    "uvs_ft_create", "uvs_ft_destroy", "uvs_ft_last_error", "uvs_ft_reset", "uvs_ft_track", "uvs_ft_last_device_ms", "uvs_ft_debug_pyramid", "uvs_ft_debug_point",
 ]
 
 
@@ -112,6 +113,18 @@ def lib():
         L.uvs_kf_debug_frame.argtypes = [C.c_void_p, C.POINTER(abi.KfFrame), C.POINTER(abi.KfCamera), abi.c_u8_p, abi.c_u8_p, abi.c_i32_p, abi.c_u8_p,
                                          abi.c_double_p, abi.c_u64_p, abi.c_u64_p, C.POINTER(abi.KfResult)]
         L.uvs_kf_debug_frame.restype = C.c_int
+        L.uvs_ft_create.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_void_p)]; L.uvs_ft_create.restype = C.c_int
+        L.uvs_ft_destroy.argtypes = [C.c_void_p]; L.uvs_ft_destroy.restype = None
+        L.uvs_ft_last_error.argtypes = [C.c_void_p]; L.uvs_ft_last_error.restype = C.c_char_p
+        L.uvs_ft_reset.argtypes = [C.c_void_p, C.c_int]; L.uvs_ft_reset.restype = C.c_int
+        L.uvs_ft_track.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.FtItem), C.POINTER(abi.KfCamera), abi.c_double_p, abi.c_i32_p, abi.c_i32_p,
+                                   abi.c_double_p, abi.c_i32_p]
+        L.uvs_ft_track.restype = C.c_int
+        L.uvs_ft_last_device_ms.argtypes = [C.c_void_p]; L.uvs_ft_last_device_ms.restype = C.c_double
+        L.uvs_ft_debug_pyramid.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_u8_p, C.c_int64]; L.uvs_ft_debug_pyramid.restype = C.c_int
+        L.uvs_ft_debug_point.argtypes = [C.c_void_p, C.POINTER(abi.FtItem), C.POINTER(abi.KfCamera), abi.c_double_p, abi.c_double_p, abi.c_i32_p,
+                                         abi.c_i32_p, abi.c_double_p]
+        L.uvs_ft_debug_point.restype = C.c_int
         _lib = L
     return _lib
 
@@ -695,3 +708,106 @@ class KeyframeExtractor:
         out = self._split(o, [res], [nw])[0]
         out.update(blur=blur, score_map=smap)
         return out
+
+
+class FeatureTracker:
+    """Owns one `uvs_ft_tracker` handle: the tracking step of the reference's point front end (FeatureTracker::readImage: pyramidal Lucas-Kanade
+    with a 21 x 21 window, inBorder, liftProjective of the tracked points) on one GPU.  Each of the `max_streams` slots keeps the pyramid of its
+    last image on the device; a call takes one new image per slot and the points to follow into it.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    def __init__(self, device=0, max_streams=1, max_width=752, max_height=480, levels=4, max_points=1024):
+        self.levels = int(levels)
+        self._pyramid_capacity = 2 * int(max_width) * int(max_height)      # level 0 plus the levels above it, which add less than a third
+        self._h = C.c_void_p()
+        rc = lib().uvs_ft_create(device, max_streams, max_width, max_height, levels, max_points, C.byref(self._h))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_ft_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
+
+    def close(self):
+        if self._h:
+            lib().uvs_ft_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _error(self, what, rc):
+        return RuntimeError(f"{what}: {lib().uvs_status_string(rc).decode()} / {lib().uvs_ft_last_error(self._h).decode()}")
+
+    def last_error(self):
+        return lib().uvs_ft_last_error(self._h).decode()
+
+    def track_raw(self, items, camera, n_items=None, null=()):
+        """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  n_items overrides the count passed; `null`
+        names arguments passed as NULL ("items", "camera", "next_xy", "status", "iterations", "next_norm", "results")."""
+        arr, keep = abi.ft_items(items)
+        npt = [int(arr[b].n_points) for b in range(len(items))]
+        cam = abi.kf_camera(camera)
+        N = max(sum(npt), 1)
+        o = dict(next_xy=np.zeros((N, 2)), status=np.zeros(N, np.int32), iterations=np.zeros(N, np.int32), next_norm=np.zeros((N, 2)),
+                 results=np.zeros(max(len(items), 1), np.int32))
+        args = dict(items=C.cast(arr, C.POINTER(abi.FtItem)), camera=C.byref(cam), next_xy=abi._dp(o["next_xy"]),
+                    status=o["status"].ctypes.data_as(abi.c_i32_p), iterations=o["iterations"].ctypes.data_as(abi.c_i32_p),
+                    next_norm=abi._dp(o["next_norm"]), results=o["results"].ctypes.data_as(abi.c_i32_p))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_ft_track(self._h, len(items) if n_items is None else int(n_items), args["items"], args["camera"], args["next_xy"],
+                                args["status"], args["iterations"], args["next_norm"], args["results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: repacking, upload, kernels, download
+        self.last_device_ms = float(lib().uvs_ft_last_device_ms(self._h))      # HIP events around upload, kernels, download
+        if rc != abi.UVS_OK:
+            return rc, []
+        off = np.r_[0, np.cumsum(npt)].astype(int)
+        out = []
+        for b in range(len(items)):
+            s = slice(off[b], off[b + 1])
+            out.append(dict(next_xy=o["next_xy"][s].copy(), status=o["status"][s].copy(), iterations=o["iterations"][s].copy(),
+                            next_norm=o["next_norm"][s].copy(), n_tracked=int(o["results"][b])))
+        return rc, out
+
+    def track(self, items, camera):
+        """items: list of dicts (stream; image [H, W] uint8, the slot's new image; points [n, 2] float64 pixels in the slot's previous image,
+        optional); camera = (fx, fy, cx, cy[, k1, k2, p1, p2]).  -> one dict per item: next_xy [n, 2] float64, status [n] int32 (index of
+        abi.FT_STATUS), iterations [n] int32, next_norm [n, 2] float64 (zero where the point is not TRACKED), n_tracked."""
+        rc, out = self.track_raw(items, camera)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_track", rc)
+        return out
+
+    def reset(self, stream):
+        rc = lib().uvs_ft_reset(self._h, int(stream))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_reset", rc)
+
+    def debug_pyramid(self, stream):
+        """The stored pyramid of a slot (tests only) -> [level 0, level 1, ..] uint8 arrays."""
+        sizes = np.zeros((abi.FT_MAX_LEVELS, 2), np.int32)
+        cap = self._pyramid_capacity
+        px = np.zeros(cap, np.uint8)
+        rc = lib().uvs_ft_debug_pyramid(self._h, int(stream), sizes.ctypes.data_as(abi.c_i32_p), px.ctypes.data_as(abi.c_u8_p), cap)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_debug_pyramid", rc)
+        out, o = [], 0
+        for l in range(self.levels):
+            w, h = int(sizes[l, 0]), int(sizes[l, 1])
+            out.append(px[o:o + w * h].reshape(h, w).copy()); o += w * h
+        return out
+
+    def debug_point(self, item, camera):
+        """ONE item with ONE point (tests only) -> the item's dict of track() plus trace [4, 320] float64 (include/uvs_solver.h lists its
+        entries)."""
+        arr, keep = abi.ft_items([item])
+        cam = abi.kf_camera(camera)
+        trace = np.zeros((abi.FT_MAX_LEVELS, abi.FT_TRACE_LEVEL)); xy = np.zeros((1, 2)); nm = np.zeros((1, 2))
+        st = np.zeros(1, np.int32); it = np.zeros(1, np.int32)
+        rc = lib().uvs_ft_debug_point(self._h, C.cast(arr, C.POINTER(abi.FtItem)), C.byref(cam), abi._dp(trace), abi._dp(xy),
+                                      st.ctypes.data_as(abi.c_i32_p), it.ctypes.data_as(abi.c_i32_p), abi._dp(nm))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_debug_point", rc)
+        return dict(next_xy=xy, status=st, iterations=it, next_norm=nm, n_tracked=int(st[0] == 0), trace=trace)

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_camera_lift.h"
 #include "uvs_hip_buf.h"
 
 namespace uvskf {
@@ -55,7 +56,7 @@ struct KfFrame {                   // device copy of one uvs_kf_frame
     int seg_off;                   // offset of the first segment in the segment arrays
     long long img_off;             // byte offset of the image / blurred image / score map in their buffers
 };
-struct KfCam { double inv_K11, inv_K13, inv_K22, inv_K23, k1, k2, p1, p2; int distort, pad; };
+using KfCam = UvsLiftCam;         // uvs_camera_lift.h: shared with the feature tracker
 
 // cv::BORDER_REFLECT_101; exact for -n < i < 2 n - 1 (every index an output needs, as n >= 9 and the halo is 4), clamped beyond so that the
 // lanes of a tile that hangs over the image still read inside it
@@ -281,17 +282,8 @@ __global__ void __launch_bounds__(kThreads) k_kf_describe(const KfFrame* __restr
         u = (float)x; v = (float)y;
         out = desc + 4 * o;
         if (lane == 0) {                                      // PinholeCamera::liftProjective
-            const double mx_d = cam.inv_K11 * (double)x + cam.inv_K13, my_d = cam.inv_K22 * (double)y + cam.inv_K23;
-            double mx_u = mx_d, my_u = my_d;
-            if (cam.distort) {
-                for (int it = 0; it < 8; ++it) {              // distortion() at (mx_d, my_d), then 7 times at the running estimate
-                    const double mx2 = mx_u * mx_u, my2 = my_u * my_u, mxy = mx_u * my_u, rho2 = mx2 + my2;
-                    const double rad = cam.k1 * rho2 + cam.k2 * rho2 * rho2;
-                    const double dx = mx_u * rad + 2.0 * cam.p1 * mxy + cam.p2 * (rho2 + 2.0 * mx2);
-                    const double dy = my_u * rad + 2.0 * cam.p2 * mxy + cam.p1 * (rho2 + 2.0 * my2);
-                    mx_u = mx_d - dx; my_u = my_d - dy;
-                }
-            }
+            double mx_u, my_u;
+            uvs_lift_projective(cam, (double)x, (double)y, mx_u, my_u);
             norm[2 * o] = mx_u; norm[2 * o + 1] = my_u;
         }
     } else {
@@ -413,11 +405,7 @@ int kf_run(uvs_kf_extractor* h, const char* who_, int n_frames, const uvs_kf_fra
     unsigned long long* dWdesc = reinterpret_cast<unsigned long long*>(h->d_out + L.wdesc);
     int32_t* dXy = reinterpret_cast<int32_t*>(h->d_out + L.xy);
     uint8_t* dSc = reinterpret_cast<uint8_t*>(h->d_out + L.score);
-    KfCam cam;
-    cam.inv_K11 = 1.0 / camera->fx; cam.inv_K13 = -camera->cx / camera->fx;      // PinholeCamera.cc:292-295
-    cam.inv_K22 = 1.0 / camera->fy; cam.inv_K23 = -camera->cy / camera->fy;
-    cam.k1 = camera->k1; cam.k2 = camera->k2; cam.p1 = camera->p1; cam.p2 = camera->p2;
-    cam.distort = !(camera->k1 == 0.0 && camera->k2 == 0.0 && camera->p1 == 0.0 && camera->p2 == 0.0); cam.pad = 0;
+    const KfCam cam = uvs_lift_camera(*camera);
     const int waves = kThreads / 64;
     const unsigned seg_blocks = (unsigned)((max_h * segs_of(max_w) + waves - 1) / waves);
     const unsigned item_blocks = (unsigned)((h->max_keypoints + max_nw + waves - 1) / waves);

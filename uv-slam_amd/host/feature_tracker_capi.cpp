@@ -1,0 +1,88 @@
+// feature_tracker_capi.cpp -- test hooks for uvs::FeatureTracker (feature_tracker.h): a tracker behind a handle, fed with images (the device
+// path) or with a frame's flow results by hand (the bookkeeping alone, no device), and its vectors read back.  Apart from host_capi.cpp for the
+// reason vanishing_points_capi.cpp gives: the CPU oracle has no uvs_ft_*.
+//   camera[8] = fx, fy, cx, cy, k1, k2, p1, p2; new_xy[n_new][2]: the points the caller's detector adds in this frame.
+#include <cstdio>
+#include <memory>
+#include "feature_tracker.h"
+
+namespace {
+struct HostFt {
+    std::unique_ptr<uvs::FeatureTracker> dev;      // null: bookkeeping only
+    std::unique_ptr<uvs::FeatureTrackerBook> book;
+    uvs::FeatureTrackerBook& b() { return dev ? *dev : *book; }
+};
+std::vector<uvs::Point2d> points(int n, const double* xy) {
+    std::vector<uvs::Point2d> v(n > 0 ? n : 0);
+    for (int i = 0; i < n; ++i) { v[i].x = xy[2 * i]; v[i].y = xy[2 * i + 1]; }
+    return v;
+}
+}  // namespace
+
+extern "C" {
+
+// device < 0: no device is touched, the handle takes uvs_host_ft_read_flow only
+void* uvs_host_ft_create(int device, const double* camera, int max_width, int max_height, int levels, int max_points) {
+    if (!camera) return nullptr;
+    const uvs_kf_camera cam{camera[0], camera[1], camera[2], camera[3], camera[4], camera[5], camera[6], camera[7]};
+    try {
+        HostFt* h = new HostFt();
+        if (device < 0) h->book.reset(new uvs::FeatureTrackerBook(cam));
+        else h->dev.reset(new uvs::FeatureTracker(cam, device, max_width, max_height, levels, max_points));
+        return h;
+    } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return nullptr;
+    }
+}
+
+void uvs_host_ft_destroy(void* h) { delete static_cast<HostFt*>(h); }
+
+int uvs_host_ft_read_image(void* hv, const unsigned char* image, int width, int height, double time, int n_new, const double* new_xy) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev || !image || n_new < 0 || (n_new > 0 && !new_xy)) return UVS_ERR_INVALID_ARG;
+    const std::vector<uvs::Point2d> fresh = points(n_new, new_xy);
+    const int rc = h->dev->readImage(image, width, height, time, [&](const uvs::FeatureTracker&, std::vector<uvs::Point2d>& n_pts) { n_pts = fresh; });
+    if (rc != UVS_OK) std::fprintf(stderr, "uvs_host_ft_read_image: %s\n", h->dev->last_error.c_str());
+    return rc;
+}
+
+// one frame of the bookkeeping from given flow results: next_xy[n][2], ft_status[n] (UVS_FT_*), next_norm[n][2], n = the points held
+int uvs_host_ft_read_flow(void* hv, double time, int n, const double* next_xy, const int* ft_status, const double* next_norm, int n_new, const double* new_xy) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || n < 0 || n_new < 0 || (n > 0 && (!next_xy || !ft_status || !next_norm)) || (n_new > 0 && !new_xy)) return UVS_ERR_INVALID_ARG;
+    uvs::FeatureTrackerBook& b = h->b();
+    if ((size_t)n != b.cur_pts.size()) return UVS_ERR_INVALID_ARG;
+    b.applyFlow(time, points(n, next_xy), std::vector<int32_t>(ft_status, ft_status + n), points(n, next_norm));
+    b.n_pts = points(n_new, new_xy);
+    b.addPoints();
+    b.rotate();
+    return UVS_OK;
+}
+
+// updateID(i) for i = 0, 1, .. as the node does after readImage (feature_tracker_node.cpp); returns the number of points
+int uvs_host_ft_update_ids(void* hv) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h) return -1;
+    unsigned int i = 0;
+    while (h->b().updateID(i)) ++i;
+    return (int)i;
+}
+
+// copies up to `capacity` points out; returns the number held.  Any array may be null.
+int uvs_host_ft_get(void* hv, int capacity, double* cur_pts, int* ids, int* track_cnt, double* cur_un_pts, double* pts_velocity) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h) return -1;
+    const uvs::FeatureTrackerBook& b = h->b();
+    const int n = (int)b.cur_pts.size();
+    for (int i = 0; i < n && i < capacity; ++i) {
+        if (cur_pts) { cur_pts[2 * i] = b.cur_pts[i].x; cur_pts[2 * i + 1] = b.cur_pts[i].y; }
+        if (ids) ids[i] = b.ids[i];
+        if (track_cnt) track_cnt[i] = b.track_cnt[i];
+        if (cur_un_pts) { cur_un_pts[2 * i] = b.cur_un_pts[i].x; cur_un_pts[2 * i + 1] = b.cur_un_pts[i].y; }
+        if (pts_velocity) { pts_velocity[2 * i] = b.pts_velocity[i].x; pts_velocity[2 * i + 1] = b.pts_velocity[i].y; }
+    }
+    return n;
+}
+
+}  // extern "C"
