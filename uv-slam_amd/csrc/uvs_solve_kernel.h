@@ -15,6 +15,7 @@
 //   * the reduced system is factored by a blocked right-looking Cholesky on 16x16 LDS blocks.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <utility>
 #include "../../include/uvs_solver.h"
 #include "uvs_layout.h"
 #include "uvs_factors.h"
@@ -995,6 +996,9 @@ UVS_DEV void chol_factor(const Ctx& c) { if (c.hdr->chol_half_ok) chol_factor_ca
 // back substitution L^T x = y in place (y in L_DLT, produced by chol_factor); the diagonal solves are mat-vecs with W^T.
 // One wave does all of it: the chain x_k -> (update of the rows above) -> x_k-1 is serial anyway, and inside a single wave it
 // needs no workgroup barrier (22 of them otherwise).
+#ifdef UVS_X_TRSV_LDS
+// The form up to round 6 (A/B builds only): b stays in LDS, x_k is handed over through LDS, every update trip is a read-modify-write of b in LDS
+// -- two dependent LDS round trips per block step plus one per trip, ~1.6 k cycles per step.
 UVS_DEV void chol_solve_impl(double* sh) {
     const int tid = lane_tid();
     double* b = sh + L_DLT;
@@ -1036,6 +1040,153 @@ UVS_DEV void chol_solve_impl(double* sh) {
     __syncthreads();
 }
 UVS_DEV void chol_solve(const Ctx& c) { chol_solve_impl(c.sh); }
+#else
+// NO LDS round trip on the chain x_k -> b_(k-1) -> x_(k-1): the right-hand side lives in registers of wave 0 (lane l: entries l, 64 + l, 128 + l, so
+// block k is the 16-lane row k & 3 of register slot k >> 2), the loop over k is unrolled (slots, block offsets and trip counts are constants), and
+// every value that crosses lanes does so in registers:
+//   b_k of its home row -> all four rows            v_permlane32_swap + v_permlane16_swap (trsv_row_all)
+//   b_k[m] -> every lane of a row                   v_mov_b64_dpp row_newbcast (trsv_row_lane)
+//   x_k[r] -> every lane of a row                   the DPP operand of the update's own FMA (trsv_fmac_row_lane)
+// What is left in LDS are the operand loads (W_k, 1 / L_kk, the columns of the blocks (k, j)); they do not depend on x and nothing stores to LDS
+// between the first load and the final store of x, so the compiler requests them ahead of the step that uses them (counted lgkmcnt waits).
+// With the round trips gone the phase is bound by the ISSUE of FP64 instructions (8 cycles each for a wave that has its SIMD's FP64 pipe alone), so
+// the second concern is their number: the mat-vec with W_k^T is split over the four rows of the wave (row q forms partial sum q, four terms instead
+// of sixteen), and no instruction only moves an x_k[r].
+// Arithmetic: the four partial sums, their (0 + 1) + (2 + 3) combination and the order in which a b_j receives its terms (k descending) are those
+// of the LDS form: same bits, except the sign of an exact zero where HALF drops structurally zero products.  No branch depends on data.
+template <int Q> UVS_DEV double trsv_row_all(double v) {      // v of the same (lane & 15) in row Q, in every row
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const auto hl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);      // [0] = rows {0, 1, 0, 1}, [1] = rows {2, 3, 2, 3}
+    const auto hh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    const auto al = __builtin_amdgcn_permlane16_swap(hl[Q >> 1], hl[Q >> 1], false, false);      // [0] = the even row of the pair everywhere, [1] = the odd one
+    const auto ah = __builtin_amdgcn_permlane16_swap(hh[Q >> 1], hh[Q >> 1], false, false);
+    return __hiloint2double((int)ah[Q & 1], (int)al[Q & 1]);
+}
+// ((row 0 + row 1) + (row 2 + row 3)) of v, lane by lane, in every row: the combination of the four partial sums
+UVS_DEV double trsv_rows_sum(double v) {
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const auto al = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);      // [0] = rows {0, 0, 2, 2}, [1] = rows {1, 1, 3, 3}
+    const auto ah = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    const double t = __hiloint2double((int)ah[0], (int)al[0]) + __hiloint2double((int)ah[1], (int)al[1]);
+    const unsigned tlo = (unsigned)__double2loint(t), thi = (unsigned)__double2hiint(t);
+    const auto bl = __builtin_amdgcn_permlane32_swap(tlo, tlo, false, false);    // [0] = rows {0, 1, 0, 1}, [1] = rows {2, 3, 2, 3}
+    const auto bh = __builtin_amdgcn_permlane32_swap(thi, thi, false, false);
+    return __hiloint2double((int)bh[0], (int)bl[0]) + __hiloint2double((int)bh[1], (int)bl[1]);
+}
+template <int M> UVS_DEV double trsv_row_lane(double v) {     // v of lane M of this lane's 16-lane row
+    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + M, 0xf, 0xf, true);      // row_newbcast:M
+}
+// in row q (q = 1 .. 3) every lane takes v of lane q of its quad; row 0 keeps v: lane 4 i of row q then holds entry 4 i + q
+UVS_DEV double trsv_quad_rotate(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    const int l0 = lo, h0 = hi;
+    lo = __builtin_amdgcn_update_dpp(lo, l0, 0x55, 0x2, 0xf, false); hi = __builtin_amdgcn_update_dpp(hi, h0, 0x55, 0x2, 0xf, false);      // quad_perm:[1,1,1,1] row_mask:0x2
+    lo = __builtin_amdgcn_update_dpp(lo, l0, 0xaa, 0x4, 0xf, false); hi = __builtin_amdgcn_update_dpp(hi, h0, 0xaa, 0x4, 0xf, false);      // quad_perm:[2,2,2,2] row_mask:0x4
+    lo = __builtin_amdgcn_update_dpp(lo, l0, 0xff, 0x8, 0xf, false); hi = __builtin_amdgcn_update_dpp(hi, h0, 0xff, 0x8, 0xf, false);      // quad_perm:[3,3,3,3] row_mask:0x8
+    return __hiloint2double(hi, lo);
+}
+// acc + a * (x of lane R of this lane's row) in one instruction.  The compiler's hazard recognizer does not look into inline assembly: a DPP read needs
+// two wait states after the VALU write of its source, which trsv_dpp_source provides once per x (every later read is a read of ITS result);
+// tools/check_dpp_sources.py checks the emitted ISA for it.
+template <int R> UVS_DEV double trsv_fmac_row_lane(double acc, double a, double x) {
+    asm("v_fmac_f64_dpp %0, %2, %1 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(a), "v"(x), "n"(R));
+    return acc;
+}
+UVS_DEV double trsv_dpp_source(double x) { asm volatile("s_nop 1" : "+v"(x)); return x; }
+// trip T of step K: b_j -= L(K, j)^T x_K for the blocks j = 4 T + (row of the lane) < K of register slot T
+template <bool HALF, int K, int T> struct TrsvTrip {
+    static constexpr int QL = (K - 1) & 3;                       // row of block K - 1 in its slot
+    static constexpr bool last = (T == ((K - 1) >> 2));          // the slot that holds block K - 1: rows beyond QL have no block of this step (their load is clamped, their result dropped)
+    static constexpr bool far_only = (4 * T + 3 < K - 1);        // chol_half_ok: blocks (K, j), j < K - 1, are non-zero in rows {0..5, 15} only (uvs_layout.h)
+    static constexpr bool live(int r) { return !(HALF && far_only && r >= 6 && r < 15); }
+    template <int R> static UVS_DEV void term(double* u4, const double* bv, double x) { if constexpr (live(R)) u4[R & 3] = trsv_fmac_row_lane<R>(u4[R & 3], bv[R], x); }
+    template <int... R> static UVS_DEV void terms(double* u4, const double* bv, double x, std::integer_sequence<int, R...>) { (term<R>(u4, bv, x), ...); }
+    static UVS_DEV void load(double* sh, int c16, int q, double* bv) {
+        const int qc = (last && q > QL) ? QL : q;
+        const double* B = sblk(sh, K, 4 * T) + qc * UVS_BLK_SZ + c16;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) if (live(r)) bv[r] = B[r * UVS_BLK_LD];
+    }
+    static UVS_DEV void apply(int q, const double* bv, double x, double& bslot) {
+        double u4[4] = {0.0, 0.0, 0.0, 0.0};
+        terms(u4, bv, x, std::make_integer_sequence<int, 16>());
+        const double nb = bslot - ((u4[0] + u4[1]) + (u4[2] + u4[3]));
+        bslot = (!last || q <= QL) ? nb : bslot;
+    }
+};
+template <int K> UVS_DEV void trsv_load_w(double* sh, int c16, int q, double* w) {      // this row's four entries of row c of the diagonal block (W[m][c], m > c, sits at (c, m)) and 1 / L_cc
+    const double* Dk = sblk(sh, K, K) + c16 * UVS_BLK_LD + q;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = Dk[4 * i];
+    w[4] = sh[L_DINV + 16 * K + c16];
+}
+// Step K; wK = its operands of the diagonal block, requested during step K + 1.  The block columns of this step's updates (at most three trips; the one
+// that holds block K - 1 first, the next step waits only for it) and the diagonal operands of step K - 1 are requested HERE, ahead of the mat-vec whose
+// result they meet: none of them depends on x, and nothing in the whole solve stores to LDS, so the requests are in flight while the chain computes.
+template <bool HALF, int K>
+UVS_DEV void trsv_steps(double* sh, int c16, int q, double* bs, const int* msk, int eq, const double* wK) {
+    constexpr int SK = K >> 2, QK = K & 3, S1 = (K - 1) >> 2;
+    double bv0[16], bv1[16], bv2[16], wN[5];
+    if constexpr (K > 0) {
+        TrsvTrip<HALF, K, S1>::load(sh, c16, q, bv0);
+        if constexpr (S1 > 0) TrsvTrip<HALF, K, S1 - 1>::load(sh, c16, q, bv1);
+        if constexpr (S1 > 1) TrsvTrip<HALF, K, S1 - 2>::load(sh, c16, q, bv2);
+        trsv_load_w<K - 1>(sh, c16, q, wN);
+    }
+    // x_k[c] = sum_{m >= c} W[m][c] b_k[m].  Row q of the wave forms partial sum q (terms m = q, q + 4, q + 8, q + 12) of every x_k[c]; the diagonal
+    // term 1 / L_cc b_k[c] starts the partial sum it belongs to (c & 3), which is +0 until that term in the LDS form, too.
+    // The entries on and below the diagonal, which the LDS form replaced by 0 through two selects per term, are scaled to an exact zero instead
+    // (v_ldexp_f64 by 0 or by -4096: one instruction); a product with a zero leaves a partial sum as it is.
+    double rv[4];
+    const double cur = trsv_row_all<QK>(bs[SK]);      // b_k[c] in lane c of every row
+    const double rot = trsv_quad_rotate(cur);         // b_k[4 i + q] in lane 4 i of row q
+    rv[0] = trsv_row_lane<0>(rot); rv[1] = trsv_row_lane<4>(rot); rv[2] = trsv_row_lane<8>(rot); rv[3] = trsv_row_lane<12>(rot);
+    double p = fma(__builtin_amdgcn_ldexp(wK[4], eq), cur, 0.0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) p += __builtin_amdgcn_ldexp(wK[i], msk[i]) * rv[i];
+    const double s = trsv_dpp_source(trsv_rows_sum(p));      // (p4[0] + p4[1]) + (p4[2] + p4[3]), in every row
+    bs[SK] = (q == QK) ? s : bs[SK];      // x_k replaces b_k in place
+    if constexpr (K > 0) {
+        TrsvTrip<HALF, K, S1>::apply(q, bv0, s, bs[S1]);
+        if constexpr (S1 > 0) TrsvTrip<HALF, K, S1 - 1>::apply(q, bv1, s, bs[S1 - 1]);
+        if constexpr (S1 > 1) TrsvTrip<HALF, K, S1 - 2>::apply(q, bv2, s, bs[S1 - 2]);
+        static_assert(S1 <= 2, "at most three update trips per step");
+        trsv_steps<HALF, K - 1>(sh, c16, q, bs, msk, eq, wN);
+    }
+}
+template <bool HALF>
+UVS_DEV void chol_solve_impl(double* sh) {
+    const int tid = lane_tid();
+    double* b = sh + L_DLT;
+    static_assert(UVS_NF >= 2 && UVS_NF <= 12 && UVS_RD > 128 && UVS_RD <= 192, "three register slots of 64 unknowns");
+    __syncthreads();
+    if (tid < 64) {
+        const int c16 = tid & 15, q = tid >> 4;
+        double bs[3] = {b[tid], b[64 + tid], (128 + tid < UVS_RD) ? b[128 + tid] : 0.0};
+        int msk[4];      // exponent offsets: 0 where term m = 4 i + q lies strictly above the diagonal in this lane's column c, else -4096 (the product underflows to an exact zero)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) msk[i] = (4 * i + q > c16) ? 0 : -4096;
+        const int eq = ((c16 & 3) == q) ? 0 : -4096;      // 0 where the diagonal term belongs to this row's partial sum
+        double w0[5];
+        trsv_load_w<UVS_NF - 1>(sh, c16, q, w0);
+        trsv_steps<HALF, UVS_NF - 1>(sh, c16, q, bs, msk, eq, w0);
+        b[tid] = bs[0]; b[64 + tid] = bs[1];
+        if (128 + tid < UVS_RD) b[128 + tid] = bs[2];
+    }
+    __syncthreads();
+}
+// A real call, for the reason given at chol_factor_call (the unrolled steps hold up to three steps' operands in flight); two instantiations behind one
+// uniform branch: with chol_half_ok the far blocks are read through their seven non-zero rows.
+__device__ __attribute__((noinline)) void chol_solve_call() {
+    extern __shared__ __attribute__((aligned(16))) double sh_chol[];
+    chol_solve_impl<true>(sh_chol);
+}
+__device__ __attribute__((noinline)) void chol_solve_call_full_rows() {
+    extern __shared__ __attribute__((aligned(16))) double sh_chol[];
+    chol_solve_impl<false>(sh_chol);
+}
+UVS_DEV void chol_solve(const Ctx& c) { if (c.hdr->chol_half_ok) chol_solve_call(); else chol_solve_call_full_rows(); }
+#endif
 
 // ------------------------------------------------------------------ linearization: builds S (damped, Schur-reduced), G, HD, cost, gmax
 // Gather work split: the lanes form UVS_NGRP GROUPS of 2 lanes (32 per wave).  A group owns one lower 6x6 pose block -- or one
