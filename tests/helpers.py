@@ -203,3 +203,79 @@ def first_divergence(rg, ro, opts=None):
                 rel_margin=max(abs(pg - thr), abs(po - thr)) / max(abs(pg), abs(po), thr),
                 mcc_over_cost=(abs(rg.model_cost_change[k]) / abs(rg.cost[k]), abs(ro.model_cost_change[k]) / abs(ro.cost[k])), rho_noise=(noise(rg), noise(ro)),
                 cost_rel_diff=abs(rg.cost[k] - ro.cost[k]) / abs(ro.cost[k]), cand_rel_diff=abs(rg.candidate_cost[k] - ro.candidate_cost[k]) / abs(ro.candidate_cost[k]))
+
+
+def prior_information_named(p, flag):
+    """prior_information with the columns NAMED as tests/marg_ref.py names them (15 f + k in the window's ORIGINAL frame numbering, marg_ref.EX + k, marg_ref.TD),
+    for both marginalization kinds: MARGIN_OLD stores block_frame after the shift i -> i - 1, MARGIN_SECOND_NEW after WINDOW_SIZE -> WINDOW_SIZE - 1 (estimator.cpp:1139-1152, 1203-1220)."""
+    EX = 15 * NF; TD = EX + 6
+    J0, r0 = p.J0(), p.r0()
+    cols, src = [], []
+    for b in range(p.n_blocks):
+        kind, fr, size, idx = p.block_kind[b], p.block_frame[b], p.block_size[b], p.block_idx[b]
+        fr = fr + 1 if flag == 0 or fr == abi.WINDOW_SIZE - 1 else fr
+        loc = 6 if size == 7 else size
+        base = {abi.BLOCK_POSE: 15 * fr, abi.BLOCK_SPEEDBIAS: 15 * fr + 6, abi.BLOCK_EX_POSE: EX, abi.BLOCK_TD: TD}[kind]
+        cols += [base + k for k in range(loc)]; src += [idx + k for k in range(loc)]
+    Jc = J0[:, src]
+    return Jc.T @ Jc, Jc.T @ r0, cols
+
+
+MARG_REF_CASES = {      # name: (option set, window index, where its prior comes from); every case with a prior runs under flags 0 and 1
+    "70": ("default", 70, None), "71": ("default", 71, "own"), "72": ("default", 72, "own"), "41": ("default", 41, "own"), "73": ("default", 73, "own"), "74": ("default", 74, "own"),
+    "td88": ("td", 88, None), "td89": ("td", 89, 88),      # 89 with 88's prior: the stiff foreign-prior construction of tests/test_td.py
+    "ex80": ("ex", 80, None), "ex81": ("ex", 81, 80),
+    "tdex83": ("tdex", 83, 183),
+}
+
+
+def marg_ref_options(optset):
+    o = abi.default_options(); o.estimate_td = int("td" in optset); o.estimate_extrinsic = int("ex" in optset)
+    return o
+
+
+def marg_ref_case(name, solve, marginalize):
+    """The post-solve window of a case of MARG_REF_CASES, built as tests/test_marginalization.py and tests/test_td.py build theirs: synth.make_window, the prior from
+    `marginalize(window, flag)` of a predecessor (the previous window of the same trajectory, or the solved window `index` of the third field).
+    `solve` and `marginalize` belong to ONE solver under marg_ref_options of the case's option set."""
+    optset, index, prior = MARG_REF_CASES[name]
+    td = "td" in optset
+    mk = lambda i, **kw: synth.add_time_offset(synth.make_window(i, **kw), td_true=0.005) if td else synth.make_window(i, **kw)
+    if prior == "own":
+        w = synth.make_window(index, with_prior=True, marginalize_fn=marginalize)
+    else:
+        w = mk(index)
+        if prior is not None:
+            prev = mk(prior)
+            st, _ = solve(prev)
+            w.prior = marginalize(prev.with_state(st), 0)
+    st, _ = solve(w)
+    return w.with_state(st)
+
+
+def marg_ref_weak_window(index=75, n_weak=2, offset=1e-9):
+    """A window on which the reference's eps cut ACTS (marginalization_factor.cpp:234-243): `n_weak` points anchored at frame 0 keep ONE observation, in frame 1, of a point on
+    the line through the two camera centres OF THE WINDOW'S STATE (relative offset `offset`: the epipole, no parallax); every other factor keeps its noise and the perturbed
+    start state, so no residual block but those two is zero.  Their information is ~1e-14 <= 1e-8, the next eigenvalue of A_mm 1e-2.  Marginalized as it stands, without a
+    solve: a solve would move the two cameras and give the points their parallax back."""
+    o = synth.make_window(index).copy()
+    keep = np.ones(len(o.pt_lm), bool)
+    o.pt_pi = o.pt_pi.copy(); o.pt_pj = o.pt_pj.copy(); o.pt_fj = o.pt_fj.copy(); o.inv_depth = o.inv_depth.copy()
+    Ri, ti = synth._cam(o.pose[0, :3], o.pose[0, 3:], o.ex_pose); Rj, tj = synth._cam(o.pose[1, :3], o.pose[1, 3:], o.ex_pose)
+    d = (tj - ti) / np.linalg.norm(tj - ti)
+    perp = np.cross(d, [0.3, -0.5, 0.8]); perp /= np.linalg.norm(perp)
+    done = 0
+    for lm in range(len(o.inv_depth)):
+        rows = np.nonzero(o.pt_lm == lm)[0]
+        if done == n_weak or int(o.pt_fi[rows[0]]) != 0: continue
+        for sign in (1.0, -1.0):
+            X = ti + sign * 6.0 * (d + offset * (done + 1) * perp)
+            ci, cj = Ri.T @ (X - ti), Rj.T @ (X - tj)
+            if ci[2] > 0.5 and cj[2] > 0.5: break
+        else: continue
+        k = rows[0]; keep[rows] = False; keep[k] = True
+        o.pt_fj[k] = 1; o.pt_pi[k] = ci / ci[2]; o.pt_pj[k] = cj / cj[2]; o.inv_depth[lm] = 1.0 / ci[2]
+        done += 1
+    assert done == n_weak
+    for nm in ("pt_lm", "pt_fi", "pt_fj", "pt_pi", "pt_pj"): setattr(o, nm, getattr(o, nm)[keep])
+    return o
