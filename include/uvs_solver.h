@@ -792,6 +792,74 @@ int uvs_ft_debug_pyramid(uvs_ft_tracker *ft, int stream, int32_t *level_sizes, u
 int uvs_ft_debug_point(uvs_ft_tracker *ft, const uvs_ft_item *item, const uvs_kf_camera *camera, double *trace, double *next_xy,
                        int32_t *status, int32_t *iterations, double *next_norm);
 
+/* ---- new points of the point front end (reference feature_tracker/src/feature_tracker.cpp:9-42 setMask, :119-131
+ * cv::goodFeaturesToTrack(forw_img, n_pts, MAX_CNT - forw_pts.size(), 0.01, MIN_DIST, mask), :44-52 addPoints) ----
+ * uvs_ft_detect finds Shi-Tomasi corners in the image a slot already holds: level 0 of the pyramid that uvs_ft_track stored, so nothing is
+ * uploaded but the occupied points.  Every window sum is an integer sum; the FP64 of a pixel is one conversion, one square root and one
+ * subtraction, of the threshold one product.  An item gives the same bits alone or in a batch and from run to run, and the slot's pyramid is
+ * not altered.  Conventions as above; p(x, y) is the slot's stored level-0 image, W x H.
+ *   gradient    Sobel, at every pixel of the image, every read of p through refl:
+ *               gx(x, y) = (p(x+1, y-1) - p(x-1, y-1)) + 2 (p(x+1, y) - p(x-1, y)) + (p(x+1, y+1) - p(x-1, y+1)), gy the transpose; |g| <= 1020
+ *   sums        blockSize 3, the PRODUCTS reflected (not the image a second time):
+ *               A(x, y) = sum_{i, j = -1..1} gx(refl(x+i, W), refl(y+j, H))^2, B the same sum of gx gy, C of gy^2; int32 (<= 9 x 1020^2)
+ *   score       S = (A - C)^2 + 4 B^2 as int64 (<= 4.4e14, exact in FP64);  score = (double)(A + C) - sqrt((double)S) >= 0.
+ *               cv::cornerMinEigenVal's value is score / (2 x 3060^2); neither the order nor the relative threshold depends on the factor
+ *   allowed     a pixel is allowed iff the slot's resident mask (uvs_ft_set_mask) is absent or non-zero there, and for no occupied point
+ *               (ox, oy) of the item, xr = rint(ox), yr = rint(oy), is (x - xr)^2 + (y - yr)^2 <= R^2, R = min_distance
+ *   threshold   max_score = the largest score over ALL allowed pixels (the border ring too); threshold = quality_level * max_score.
+ *               No allowed pixel, or max_score == 0: max_score = threshold = 0 and there are no candidates
+ *   candidates  1 <= x <= W - 2, 1 <= y <= H - 2, allowed, score > threshold, and score >= each of the eight neighbours' scores (ties
+ *               survive; neighbours that are not allowed still suppress).  n_candidates is their true count; beyond the handle's
+ *               max_candidates only the first max_candidates in row-major order are ranked, and the status is UVS_FT_DETECT_OVERFLOW
+ *   ranking     by score descending, equal scores by the pixel index y W + x descending
+ *   selection   the ranking is walked in order; a candidate is taken iff dx^2 + dy^2 >= R^2 to every candidate taken before it (two points
+ *               exactly R apart are both taken); the walk stops at max_new taken
+ *   outputs     per taken point, in taking order: (x, y), its score, liftProjective(x, y) through `camera`.
+ * The numerics are restated in tests/fd_ref.py, which the device is held to bit for bit; DESIGN.md 3.11 lists the deviations from OpenCV.
+ * No CPU path. */
+#define UVS_FT_DEFAULT_CANDIDATES 65536       /* max_candidates of a fresh handle */
+#define UVS_FT_MAX_CANDIDATES (1 << 20)       /* largest max_candidates */
+#define UVS_FT_MAX_MIN_DISTANCE 1024          /* largest min_distance */
+enum { UVS_FT_DETECT_OK = 0, UVS_FT_DETECT_OVERFLOW = 1 };
+
+typedef struct uvs_ft_detect_item {
+    int32_t stream;                    /* a slot that holds an image */
+    int32_t n_occupied;                /* 0 .. max_points */
+    int32_t max_new;                   /* 0 .. max_points; 0: nothing is returned */
+    int32_t reserved;
+    const double *occupied_xy;         /* [n_occupied][2], finite, within UVS_KF_MAX_COORD */
+} uvs_ft_detect_item;
+
+typedef struct uvs_ft_detect_result {
+    int32_t status;                    /* UVS_FT_DETECT_OK / UVS_FT_DETECT_OVERFLOW */
+    int32_t n_new;                     /* points taken, <= max_new */
+    int32_t n_candidates;              /* the true count, also on overflow */
+    int32_t reserved;
+    double max_score, threshold;
+} uvs_ft_detect_result;
+
+/* Candidates ranked per item: 1 .. UVS_FT_MAX_CANDIDATES (UVS_ERR_INVALID_ARG outside). */
+int uvs_ft_set_max_candidates(uvs_ft_tracker *ft, int max_candidates);
+/* mask[height][width], stride = width, of the size of the image the slot holds (UVS_ERR_INVALID_ARG otherwise, or when the slot holds nothing):
+ * detection is allowed where it is non-zero.  NULL clears it.  It stays on the device until it is cleared or the slot is reset. */
+int uvs_ft_set_mask(uvs_ft_tracker *ft, int stream, const uint8_t *mask, int width, int height);
+/* The outputs are PACKED by max_new: item i owns entries off_i .. off_i + n_new_i - 1 of new_xy[][2], new_score[] and new_norm[][2], off_i =
+ * the sum of max_new over the items before it; entries past n_new are not written.  results[n_items].
+ * UVS_ERR_INVALID_ARG: null pointer, n_items < 1, a stream outside the handle's slots or given twice, a slot that holds nothing, a negative
+ * count, a null array behind a positive count, an occupied point that is not finite or beyond UVS_KF_MAX_COORD, quality_level outside (0, 1],
+ * min_distance outside 1 .. UVS_FT_MAX_MIN_DISTANCE, a camera that is not finite or whose fx or fy is not positive;
+ * UVS_ERR_CAPACITY: n_items, n_occupied or max_new above the handle's capacity.  A rejected call changes nothing, and the handle stays usable. */
+int uvs_ft_detect(uvs_ft_tracker *ft, int n_items, const uvs_ft_detect_item *items, double quality_level, int min_distance,
+                  const uvs_kf_camera *camera, int32_t *new_xy, double *new_score, double *new_norm, uvs_ft_detect_result *results);
+/* HIP-event time of the last successful uvs_ft_detect: upload, the kernels, download, on the handle's stream (milliseconds). */
+double uvs_ft_last_detect_device_ms(const uvs_ft_tracker *ft);
+/* Diagnostic (tests only): ONE item through the same kernels, with score[H][W], allowed[H][W] (0 or 1), the ranked candidates
+ * cand_index[max_candidates] (y W + x) and cand_score[max_candidates] (the first min(n_candidates, max_candidates) entries are written), and
+ * the outputs of uvs_ft_detect for the item (arrays of max_new entries). */
+int uvs_ft_debug_detect(uvs_ft_tracker *ft, const uvs_ft_detect_item *item, double quality_level, int min_distance,
+                        const uvs_kf_camera *camera, double *score, uint8_t *allowed, int32_t *cand_index, double *cand_score,
+                        int32_t *new_xy, double *new_score, double *new_norm, uvs_ft_detect_result *result);
+
 #ifdef __cplusplus
 }
 #endif

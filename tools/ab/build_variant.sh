@@ -11,7 +11,7 @@ common="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -mllvm -disable-machine-li
 /opt/rocm/bin/hipcc $common "$@" -c $C/uvs_solve_dstep256.hip -o $T/c.o &
 wait
 others=""
-for u in uvs_pose_graph uvs_loop_verify uvs_vanishing_points uvs_keyframe_features uvs_feature_track; do
+for u in uvs_pose_graph uvs_loop_verify uvs_vanishing_points uvs_keyframe_features uvs_feature_track uvs_feature_detect; do
   [ -f $C/$u.o ] || { echo "missing $C/$u.o: run __graft_entry__.build() first"; exit 1; }
   others="$others $C/$u.o"
 done

@@ -635,3 +635,33 @@ def ft_items(items):
         arr[b].n_points = len(pts)
         arr[b].points_xy = pts.ctypes.data_as(c_double_p) if len(pts) else None
     return arr, keep
+
+
+# ---- new points of the point front end (uvs_ft_detect, include/uvs_solver.h) ---------------------------------------------
+FT_DEFAULT_CANDIDATES = 65536
+FT_MAX_CANDIDATES = 1 << 20
+FT_MAX_MIN_DISTANCE = 1024
+FT_DETECT_OK, FT_DETECT_OVERFLOW = 0, 1
+
+
+class FtDetectItem(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("n_occupied", C.c_int32), ("max_new", C.c_int32), ("reserved", C.c_int32), ("occupied_xy", c_double_p)]
+
+
+class FtDetectResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_new", C.c_int32), ("n_candidates", C.c_int32), ("reserved", C.c_int32),
+                ("max_score", C.c_double), ("threshold", C.c_double)]
+
+
+def ft_detect_items(items):
+    """(FtDetectItem array, keepalive) from dicts with stream, occupied [n, 2] float64 pixels (optional) and max_new."""
+    arr = (FtDetectItem * max(len(items), 1))()
+    keep = []
+    for b, d in enumerate(items):
+        occ = np.ascontiguousarray(d.get("occupied", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
+        keep.append(occ)
+        arr[b].stream = int(d.get("stream", 0))
+        arr[b].n_occupied = int(d.get("n_occupied", len(occ)))      # n_occupied: for the tests of the argument checks
+        arr[b].max_new = int(d["max_new"])
+        arr[b].occupied_xy = occ.ctypes.data_as(c_double_p) if len(occ) else None
+    return arr, keep

@@ -24,6 +24,7 @@ EXPORTS = [
     "uvs_vp_create", "uvs_vp_destroy", "uvs_vp_last_error", "uvs_vp_estimate", "uvs_vp_last_device_ms", "uvs_vp_debug_frame",
     "uvs_kf_create", "uvs_kf_destroy", "uvs_kf_last_error", "uvs_kf_extract", "uvs_kf_last_device_ms", "uvs_kf_debug_frame",
     "uvs_ft_create", "uvs_ft_destroy", "uvs_ft_last_error", "uvs_ft_reset", "uvs_ft_track", "uvs_ft_last_device_ms", "uvs_ft_debug_pyramid", "uvs_ft_debug_point",
+    "uvs_ft_set_max_candidates", "uvs_ft_set_mask", "uvs_ft_detect", "uvs_ft_last_detect_device_ms", "uvs_ft_debug_detect",
 ]
 
 
@@ -125,6 +126,15 @@ def lib():
         L.uvs_ft_debug_point.argtypes = [C.c_void_p, C.POINTER(abi.FtItem), C.POINTER(abi.KfCamera), abi.c_double_p, abi.c_double_p, abi.c_i32_p,
                                          abi.c_i32_p, abi.c_double_p]
         L.uvs_ft_debug_point.restype = C.c_int
+        L.uvs_ft_set_max_candidates.argtypes = [C.c_void_p, C.c_int]; L.uvs_ft_set_max_candidates.restype = C.c_int
+        L.uvs_ft_set_mask.argtypes = [C.c_void_p, C.c_int, abi.c_u8_p, C.c_int, C.c_int]; L.uvs_ft_set_mask.restype = C.c_int
+        L.uvs_ft_detect.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.FtDetectItem), C.c_double, C.c_int, C.POINTER(abi.KfCamera), abi.c_i32_p,
+                                    abi.c_double_p, abi.c_double_p, C.POINTER(abi.FtDetectResult)]
+        L.uvs_ft_detect.restype = C.c_int
+        L.uvs_ft_last_detect_device_ms.argtypes = [C.c_void_p]; L.uvs_ft_last_detect_device_ms.restype = C.c_double
+        L.uvs_ft_debug_detect.argtypes = [C.c_void_p, C.POINTER(abi.FtDetectItem), C.c_double, C.c_int, C.POINTER(abi.KfCamera), abi.c_double_p, abi.c_u8_p,
+                                          abi.c_i32_p, abi.c_double_p, abi.c_i32_p, abi.c_double_p, abi.c_double_p, C.POINTER(abi.FtDetectResult)]
+        L.uvs_ft_debug_detect.restype = C.c_int
         _lib = L
     return _lib
 
@@ -719,6 +729,7 @@ class FeatureTracker:
 
     def __init__(self, device=0, max_streams=1, max_width=752, max_height=480, levels=4, max_points=1024):
         self.levels = int(levels)
+        self.max_candidates = abi.FT_DEFAULT_CANDIDATES
         self._pyramid_capacity = 2 * int(max_width) * int(max_height)      # level 0 plus the levels above it, which add less than a third
         self._h = C.c_void_p()
         rc = lib().uvs_ft_create(device, max_streams, max_width, max_height, levels, max_points, C.byref(self._h))
@@ -811,3 +822,86 @@ class FeatureTracker:
         if rc != abi.UVS_OK:
             raise self._error("uvs_ft_debug_point", rc)
         return dict(next_xy=xy, status=st, iterations=it, next_norm=nm, n_tracked=int(st[0] == 0), trace=trace)
+
+    # ---- new points: Shi-Tomasi corners of the image a slot holds (uvs_ft_detect)
+    def set_max_candidates(self, max_candidates):
+        rc = lib().uvs_ft_set_max_candidates(self._h, int(max_candidates))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_set_max_candidates", rc)
+        self.max_candidates = int(max_candidates)
+
+    def set_mask(self, stream, mask):
+        """mask [H, W] uint8 of the size of the slot's image (detection is allowed where it is non-zero), or None to clear it."""
+        if mask is None:
+            rc = lib().uvs_ft_set_mask(self._h, int(stream), None, 0, 0)
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            rc = lib().uvs_ft_set_mask(self._h, int(stream), m.ctypes.data_as(abi.c_u8_p), m.shape[1], m.shape[0])
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_set_mask", rc)
+
+    @staticmethod
+    def _detect_split(o, res, max_new):
+        off = np.r_[0, np.cumsum(max_new)].astype(int)
+        out = []
+        for b, r in enumerate(res):
+            s = slice(off[b], off[b] + int(r.n_new))
+            out.append(dict(xy=o["xy"][s].copy(), score=o["score"][s].copy(), norm=o["norm"][s].copy(), status=int(r.status), n_new=int(r.n_new),
+                            n_candidates=int(r.n_candidates), max_score=float(r.max_score), threshold=float(r.threshold)))
+        return out
+
+    def detect_raw(self, items, camera, quality_level=0.01, min_distance=30, n_items=None, null=()):
+        """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  n_items overrides the count passed; `null`
+        names arguments passed as NULL ("items", "camera", "new_xy", "new_score", "new_norm", "results")."""
+        arr, keep = abi.ft_detect_items(items)
+        max_new = [max(int(arr[b].max_new), 0) for b in range(len(items))]
+        cam = abi.kf_camera(camera)
+        N = max(sum(max_new), 1)
+        o = dict(xy=np.zeros((N, 2), np.int32), score=np.zeros(N), norm=np.zeros((N, 2)))
+        res = (abi.FtDetectResult * max(len(items), 1))()
+        args = dict(items=C.cast(arr, C.POINTER(abi.FtDetectItem)), camera=C.byref(cam), new_xy=o["xy"].ctypes.data_as(abi.c_i32_p),
+                    new_score=abi._dp(o["score"]), new_norm=abi._dp(o["norm"]), results=C.cast(res, C.POINTER(abi.FtDetectResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_ft_detect(self._h, len(items) if n_items is None else int(n_items), args["items"], float(quality_level), int(min_distance),
+                                 args["camera"], args["new_xy"], args["new_score"], args["new_norm"], args["results"])
+        self.last_detect_ms = (time.perf_counter() - t0) * 1e3      # the whole C-ABI call
+        if rc != abi.UVS_OK:
+            return rc, []
+        return rc, self._detect_split(o, [res[b] for b in range(len(items))], max_new)
+
+    def detect(self, items, camera, quality_level=0.01, min_distance=30):
+        """items: list of dicts (stream: a slot that holds an image; occupied [n, 2] float64 pixels, optional: no new point within min_distance
+        of one; max_new); camera as in track().  -> one dict per item: xy [n_new, 2] int32, score [n_new] float64, norm [n_new, 2] float64
+        (liftProjective of xy), in the order the points were taken (best first), status (abi.FT_DETECT_*), n_new, n_candidates, max_score,
+        threshold."""
+        rc, out = self.detect_raw(items, camera, quality_level, min_distance)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_detect", rc)
+        return out
+
+    def last_detect_device_ms(self):
+        """HIP events around upload, kernels and download of the last detect()."""
+        return float(lib().uvs_ft_last_detect_device_ms(self._h))
+
+    def debug_detect(self, item, camera, shape, quality_level=0.01, min_distance=30):
+        """ONE item (tests only); shape = (H, W) of the slot's image -> the item's dict of detect() plus score_map [H, W] float64, allowed [H, W]
+        uint8, cand_index and cand_score: the ranked candidates (min(n_candidates, max_candidates) of them)."""
+        arr, keep = abi.ft_detect_items([item])
+        cam = abi.kf_camera(camera)
+        H, W = int(shape[0]), int(shape[1])
+        M = max(int(arr[0].max_new), 1)
+        o = dict(xy=np.zeros((M, 2), np.int32), score=np.zeros(M), norm=np.zeros((M, 2)))
+        smap = np.zeros((H, W)); allowed = np.zeros((H, W), np.uint8)
+        ci = np.zeros(self.max_candidates, np.int32); cs = np.zeros(self.max_candidates)
+        res = abi.FtDetectResult()
+        rc = lib().uvs_ft_debug_detect(self._h, C.cast(arr, C.POINTER(abi.FtDetectItem)), float(quality_level), int(min_distance), C.byref(cam),
+                                       abi._dp(smap), allowed.ctypes.data_as(abi.c_u8_p), ci.ctypes.data_as(abi.c_i32_p), abi._dp(cs),
+                                       o["xy"].ctypes.data_as(abi.c_i32_p), abi._dp(o["score"]), abi._dp(o["norm"]), C.byref(res))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_debug_detect", rc)
+        out = self._detect_split(o, [res], [M])[0]
+        n = min(out["n_candidates"], self.max_candidates)
+        out.update(score_map=smap, allowed=allowed, cand_index=ci[:n].copy(), cand_score=cs[:n].copy())
+        return out

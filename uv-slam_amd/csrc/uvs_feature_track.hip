@@ -4,6 +4,7 @@
 // sum, so a wave reduction and a numpy .sum() agree; the FP64 of an iteration is a handful of operations in a fixed order, and this unit is
 // compiled with -ffp-contract=off, so they round as written, which is what tests/ft_ref.py (the numpy restatement, the pin) does.
 //
+// The handle is csrc/uvs_ft_handle.h, shared with the detection unit (uvs_feature_detect.hip), which reads level 0 of a slot's stored pyramid.
 // A tracker keeps, for each of its slots, two pyramids in one device buffer: the stored one and the one the next image is built into; a call
 // swaps them.  Rows use the keyframe unit's pitch (the width rounded up to 16 bytes).  Kernels of one call, in stream order:
 //   k_ft_pyramid   one launch per level above 0, the item on the last grid axis, a thread per output pixel: five rows of five reads through
@@ -26,6 +27,7 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_camera_lift.h"
+#include "uvs_ft_handle.h"
 #include "uvs_hip_buf.h"
 
 namespace uvsft {
@@ -248,44 +250,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_track(const FtItem* __restrict_
 
 using namespace uvsft;
 
-struct uvs_ft_tracker {
-    struct Slot { int W = 0, H = 0, cur = 0; bool holds = false; };      // cur: which of the slot's two pyramids is the stored one
-    int device = 0, max_streams = 0, max_width = 0, max_height = 0, levels = 0, max_points = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the device work of one call (uvs_ft_last_device_ms)
-    float device_ms = 0.f;
-    std::string err;
-    std::vector<Slot> slots;
-    size_t pyr_bytes = 0;                       // bytes of one pyramid at the largest size, every level rounded up to 256
-    size_t img_slot = 0;                        // bytes of one level-0 image at the largest size, rounded up to 256
-    size_t in_meta = 0;                         // bytes of (items | item of every point | points) at capacity, rounded up to 256
-    DevBuf<uint8_t> d_pyr;                      // [max_streams][2] pyramids
-    DevBuf<char> d_in, d_out;                   // the call's meta data / outputs (next_xy | next_norm | status | iterations | trace)
-    PinnedBuf<char> h_in, h_out;                // pinned staging: meta data, then the repacked images / the outputs
-    ~uvs_ft_tracker() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
 namespace {
-
-inline size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
-inline int pitch_of(int width) { return (width + 15) & ~15; }
-
-// sizes and byte offsets of the levels of one pyramid of a width x height image -> its bytes
-size_t pyramid_layout(int width, int height, int levels, int* W, int* H, int* P, long long* off) {
-    size_t bytes = 0;
-    for (int l = 0; l < kMaxLevels; ++l) {
-        if (l < levels) {
-            W[l] = l ? (W[l - 1] + 1) / 2 : width; H[l] = l ? (H[l - 1] + 1) / 2 : height; P[l] = pitch_of(W[l]);
-            off[l] = (long long)bytes;
-            bytes += align_up((size_t)P[l] * H[l], 256);
-        } else { W[l] = H[l] = P[l] = 0; off[l] = 0; }
-    }
-    return bytes;
-}
 
 struct FtOutLayout { size_t norm, status, iters, trace, total; };
 // next_xy | next_norm | status | iterations | trace for n points

@@ -1,0 +1,58 @@
+// uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the two units of the point front end: csrc/uvs_feature_track.hip (creates and
+// destroys it, builds the pyramids, tracks) and csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid).  Host only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/uvs_solver.h"
+#include "uvs_hip_buf.h"
+
+struct uvs_ft_tracker {
+    // cur: which of the slot's two pyramids is the stored one; has_mask: the slot's part of d_mask holds a mask (uvs_ft_set_mask)
+    struct Slot { int W = 0, H = 0, cur = 0; bool holds = false, has_mask = false; };
+    int device = 0, max_streams = 0, max_width = 0, max_height = 0, levels = 0, max_points = 0;
+    int max_candidates = UVS_FT_DEFAULT_CANDIDATES;      // uvs_ft_set_max_candidates
+    hipStream_t st = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the device work of one call (uvs_ft_last_device_ms, uvs_ft_last_detect_device_ms)
+    float device_ms = 0.f, detect_ms = 0.f;
+    std::string err;
+    std::vector<Slot> slots;
+    size_t pyr_bytes = 0;                       // bytes of one pyramid at the largest size, every level rounded up to 256
+    size_t img_slot = 0;                        // bytes of one level-0 image at the largest size, rounded up to 256
+    size_t in_meta = 0;                         // bytes of (items | item of every point | points) at capacity, rounded up to 256
+    DevBuf<uint8_t> d_pyr;                      // [max_streams][2] pyramids
+    DevBuf<char> d_in, d_out;                   // the call's meta data / outputs (next_xy | next_norm | status | iterations | trace)
+    PinnedBuf<char> h_in, h_out;                // pinned staging: meta data, then the repacked images / the outputs
+    // detection (uvs_feature_detect.hip): allocated by the first call that needs them, so that a tracker that never detects pays nothing
+    DevBuf<uint8_t> d_mask;                     // [max_streams] resident masks, each laid out as level 0 of a pyramid (first uvs_ft_set_mask)
+    DevBuf<char> d_det;                         // one call's meta data, maps, candidate keys and outputs, sized by the images of the call
+    PinnedBuf<char> h_det_in, h_det_out;        // pinned staging of uvs_ft_detect
+    ~uvs_ft_tracker() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+namespace uvsft {
+
+inline size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
+inline int pitch_of(int width) { return (width + 15) & ~15; }
+
+// sizes and byte offsets of the levels of one pyramid of a width x height image -> its bytes
+inline size_t pyramid_layout(int width, int height, int levels, int* W, int* H, int* P, long long* off) {
+    size_t bytes = 0;
+    for (int l = 0; l < UVS_FT_MAX_LEVELS; ++l) {
+        if (l < levels) {
+            W[l] = l ? (W[l - 1] + 1) / 2 : width; H[l] = l ? (H[l - 1] + 1) / 2 : height; P[l] = pitch_of(W[l]);
+            off[l] = (long long)bytes;
+            bytes += align_up((size_t)P[l] * H[l], 256);
+        } else { W[l] = H[l] = P[l] = 0; off[l] = 0; }
+    }
+    return bytes;
+}
+
+}  // namespace uvsft

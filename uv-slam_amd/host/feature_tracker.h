@@ -1,10 +1,13 @@
-// feature_tracker.h -- the reference's point front end (feature_tracker/src/feature_tracker.cpp:54-147, 184-196, 240-288: readImage, addPoints,
-// updateID, undistortedPoints) in the reference's own terms, above uvs_ft_track(): an image in, cur_pts / ids / track_cnt / cur_un_pts /
-// pts_velocity out.  Header-only.  The optical flow, the inBorder cut and liftProjective of the tracked points are on the GPU
-// (csrc/uvs_feature_track.hip); what is here is the bookkeeping around them.  Differences from the reference, all from the C ABI below:
-// positions are FP64 (cv::Point2f there), new points are the caller's (goodFeaturesToTrack + setMask there), rejectWithF and CLAHE are not here,
-// and n_id is a member, not a static, so that two trackers of one process number their points apart.
+// feature_tracker.h -- the reference's point front end (feature_tracker/src/feature_tracker.cpp:9-147, 184-196, 240-288: setMask, addPoints,
+// readImage, updateID, undistortedPoints) in the reference's own terms, above uvs_ft_track() and uvs_ft_detect(): an image in, cur_pts / ids /
+// track_cnt / cur_un_pts / pts_velocity out.  Header-only.  The optical flow, the inBorder cut, the detection of new points and liftProjective
+// are on the GPU (csrc/uvs_feature_track.hip, csrc/uvs_feature_detect.hip); what is here is the bookkeeping around them.  Differences from the
+// reference, all from the C ABI below: positions are FP64 (cv::Point2f there), setMask orders with a stable sort and keeps no image (the
+// occupied points go to uvs_ft_detect, whose disc is Euclidean), rejectWithF and CLAHE are not here, and n_id is a member, not a static, so
+// that two trackers of one process number their points apart.  With max_cnt = 0 (the default) new points are the caller's, through a Detector.
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -46,6 +49,32 @@ public:
             reduceVector(cur_un_pts, status); reduceVector(track_cnt, status); reduceVector(forw_norm_, status);
         }
         for (auto& n : track_cnt) n++;
+    }
+
+    // :9-42.  The points are ordered by track_cnt descending (a STABLE sort: the reference's std::sort leaves the order of ties open), and a
+    // point is kept iff no point kept before it lies within min_dist of it, dx^2 + dy^2 <= min_dist^2 on the rint centres (the filled cv::circle
+    // of the reference's mask as a Euclidean disc).  forw_pts, ids, track_cnt and the device's normalized points are permuted alike.
+    void setMask(int min_dist) {
+        const size_t n = forw_pts.size();
+        std::vector<size_t> order(n);
+        for (size_t i = 0; i < n; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [this](size_t a, size_t b) { return track_cnt[a] > track_cnt[b]; });
+        const bool with_norm = forw_norm_.size() == n;
+        const long long r2 = (long long)min_dist * min_dist;
+        std::vector<Point2d> pts, norm;
+        std::vector<int> id, cnt;
+        std::vector<long long> cx, cy;
+        for (size_t i : order) {
+            const long long x = (long long)std::nearbyint(forw_pts[i].x), y = (long long)std::nearbyint(forw_pts[i].y);
+            bool keep = true;
+            for (size_t k = 0; k < cx.size() && keep; ++k) keep = (x - cx[k]) * (x - cx[k]) + (y - cy[k]) * (y - cy[k]) > r2;
+            if (!keep) continue;
+            pts.push_back(forw_pts[i]); id.push_back(ids[i]); cnt.push_back(track_cnt[i]);
+            if (with_norm) norm.push_back(forw_norm_[i]);
+            cx.push_back(x); cy.push_back(y);
+        }
+        forw_pts.swap(pts); ids.swap(id); track_cnt.swap(cnt);
+        if (with_norm) forw_norm_.swap(norm);
     }
 
     // :44-52
@@ -116,7 +145,7 @@ public:
 
     // throws std::runtime_error without a GPU (no CPU path)
     FeatureTracker(const uvs_kf_camera& camera, int device = 0, int max_width = 752, int max_height = 480, int levels = 4, int max_points = 1024)
-        : FeatureTrackerBook(camera) {
+        : FeatureTrackerBook(camera), max_points_(max_points) {
         const int rc = uvs_ft_create(device, 1, max_width, max_height, levels, max_points, &ft_);
         if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_ft_create: ") + uvs_status_string(rc));
     }
@@ -124,8 +153,17 @@ public:
     FeatureTracker(const FeatureTracker&) = delete;
     FeatureTracker& operator=(const FeatureTracker&) = delete;
 
+    // the reference's fisheye mask: detection is allowed where it is non-zero.  [height][width] of the images' size; it goes to the device
+    // (uvs_ft_set_mask) with the next image and stays there.  nullptr clears it.
+    void setImageMask(const uint8_t* mask, int width, int height) {
+        if (mask) image_mask_.assign(mask, mask + (size_t)width * height); else image_mask_.clear();
+        mask_w_ = width; mask_h_ = height; mask_pending_ = true;
+    }
+
     // :54-147 with PUB_THIS_FRAME set.  image: [height][width] grey levels (after CLAHE, if the caller wants it).  Returns UVS_OK or the error
-    // of uvs_ft_track (its text in last_error; the vectors are unchanged then).
+    // of uvs_ft_track (its text in last_error; the vectors are unchanged then).  Without a Detector and with max_cnt > 0 the frame goes on as
+    // :109-139 does: setMask, uvs_ft_detect of max_cnt - forw_pts.size() points with the kept points occupied, addPoints; an error of the
+    // detection is returned after the frame has been finished without new points.
     int readImage(const uint8_t* image, int width, int height, double time, const Detector& detect = nullptr) {
         const size_t n = cur_pts.size();
         xy_.resize(2 * n + 2); nxt_.resize(2 * n + 2); nrm_.resize(2 * n + 2); st_.resize(n + 1); it_.resize(n + 1);
@@ -139,15 +177,57 @@ public:
         for (size_t i = 0; i < n; ++i) { next[i].x = nxt_[2 * i]; next[i].y = nxt_[2 * i + 1]; norm[i].x = nrm_[2 * i]; norm[i].y = nrm_[2 * i + 1]; }
         applyFlow(time, next, std::vector<int32_t>(st_.begin(), st_.begin() + n), norm);
         n_pts.clear();
+        int det_rc = UVS_OK;
         if (detect) detect(*this, n_pts);
+        else if (max_cnt > 0) {
+            setMask(min_dist);
+            det_rc = detectNew();
+        }
         addPoints();
         rotate();
-        return UVS_OK;
+        return det_rc;
     }
 
+    int max_cnt = 0;                  // MAX_CNT; 0: new points are the Detector's
+    int min_dist = 30;                // MIN_DIST
+    double quality_level = 0.01;
     std::string last_error;
 
 private:
+    // :119-131: fills n_pts and appends the device's normalized points, so that undistortedPoints uses them for the new points too
+    int detectNew() {
+        if (mask_pending_) {
+            const int rc = uvs_ft_set_mask(ft_, 0, image_mask_.empty() ? nullptr : image_mask_.data(), mask_w_, mask_h_);
+            if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
+            mask_pending_ = false;
+        }
+        const int n_max_cnt = std::min(max_cnt - (int)forw_pts.size(), max_points_);
+        if (n_max_cnt <= 0) return UVS_OK;
+        const size_t n = forw_pts.size();
+        xy_.resize(2 * n + 2);
+        for (size_t i = 0; i < n; ++i) { xy_[2 * i] = forw_pts[i].x; xy_[2 * i + 1] = forw_pts[i].y; }
+        uvs_ft_detect_item item;
+        item.stream = 0; item.n_occupied = (int32_t)n; item.max_new = n_max_cnt; item.reserved = 0; item.occupied_xy = n ? xy_.data() : nullptr;
+        new_xy_.resize(2 * (size_t)n_max_cnt); new_score_.resize(n_max_cnt); new_norm_.resize(2 * (size_t)n_max_cnt);
+        uvs_ft_detect_result res;
+        const int rc = uvs_ft_detect(ft_, 1, &item, quality_level, min_dist, &camera_, new_xy_.data(), new_score_.data(), new_norm_.data(), &res);
+        if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
+        const bool with_norm = forw_norm_.size() == n;
+        for (int i = 0; i < res.n_new; ++i) {
+            Point2d p, m;
+            p.x = (double)new_xy_[2 * i]; p.y = (double)new_xy_[2 * i + 1]; m.x = new_norm_[2 * i]; m.y = new_norm_[2 * i + 1];
+            n_pts.push_back(p);
+            if (with_norm) forw_norm_.push_back(m);
+        }
+        return UVS_OK;
+    }
+
+    int max_points_ = 0;
+    std::vector<uint8_t> image_mask_;
+    int mask_w_ = 0, mask_h_ = 0;
+    bool mask_pending_ = false;
+    std::vector<int32_t> new_xy_;
+    std::vector<double> new_score_, new_norm_;
     uvs_ft_tracker* ft_ = nullptr;
     std::vector<double> xy_, nxt_, nrm_;
     std::vector<int32_t> st_, it_;

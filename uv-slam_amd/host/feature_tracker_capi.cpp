@@ -2,6 +2,8 @@
 // path) or with a frame's flow results by hand (the bookkeeping alone, no device), and its vectors read back.  Apart from host_capi.cpp for the
 // reason vanishing_points_capi.cpp gives: the CPU oracle has no uvs_ft_*.
 //   camera[8] = fx, fy, cx, cy, k1, k2, p1, p2; new_xy[n_new][2]: the points the caller's detector adds in this frame.
+// uvs_host_ft_set_detection turns the tracker's own detection on (max_cnt > 0): uvs_host_ft_read_image_detect then runs a frame without a
+// Detector, and uvs_host_ft_apply_set_mask a frame of the bookkeeping with setMask between the flow and addPoints.
 #include <cstdio>
 #include <memory>
 #include "feature_tracker.h"
@@ -54,6 +56,46 @@ int uvs_host_ft_read_flow(void* hv, double time, int n, const double* next_xy, c
     uvs::FeatureTrackerBook& b = h->b();
     if ((size_t)n != b.cur_pts.size()) return UVS_ERR_INVALID_ARG;
     b.applyFlow(time, points(n, next_xy), std::vector<int32_t>(ft_status, ft_status + n), points(n, next_norm));
+    b.n_pts = points(n_new, new_xy);
+    b.addPoints();
+    b.rotate();
+    return UVS_OK;
+}
+
+// max_cnt, min_dist, quality_level of the tracker's own detection (a device handle)
+int uvs_host_ft_set_detection(void* hv, int max_cnt, int min_dist, double quality_level) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev || max_cnt < 0) return UVS_ERR_INVALID_ARG;
+    h->dev->max_cnt = max_cnt; h->dev->min_dist = min_dist; h->dev->quality_level = quality_level;
+    return UVS_OK;
+}
+
+// the fisheye mask [height][width]; null clears it
+int uvs_host_ft_set_image_mask(void* hv, const unsigned char* mask, int width, int height) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev) return UVS_ERR_INVALID_ARG;
+    h->dev->setImageMask(mask, width, height);
+    return UVS_OK;
+}
+
+// readImage without a Detector: with max_cnt > 0 the new points are uvs_ft_detect's
+int uvs_host_ft_read_image_detect(void* hv, const unsigned char* image, int width, int height, double time) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev || !image) return UVS_ERR_INVALID_ARG;
+    const int rc = h->dev->readImage(image, width, height, time);
+    if (rc != UVS_OK) std::fprintf(stderr, "uvs_host_ft_read_image_detect: %s\n", h->dev->last_error.c_str());
+    return rc;
+}
+
+// uvs_host_ft_read_flow with setMask(min_dist) between the flow and addPoints (the bookkeeping alone: no device is touched)
+int uvs_host_ft_apply_set_mask(void* hv, double time, int n, const double* next_xy, const int* ft_status, const double* next_norm, int min_dist, int n_new,
+                               const double* new_xy) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || n < 0 || n_new < 0 || min_dist < 0 || (n > 0 && (!next_xy || !ft_status || !next_norm)) || (n_new > 0 && !new_xy)) return UVS_ERR_INVALID_ARG;
+    uvs::FeatureTrackerBook& b = h->b();
+    if ((size_t)n != b.cur_pts.size()) return UVS_ERR_INVALID_ARG;
+    b.applyFlow(time, points(n, next_xy), std::vector<int32_t>(ft_status, ft_status + n), points(n, next_norm));
+    b.setMask(min_dist);
     b.n_pts = points(n_new, new_xy);
     b.addPoints();
     b.rotate();
