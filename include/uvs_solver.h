@@ -860,6 +860,85 @@ int uvs_ft_debug_detect(uvs_ft_tracker *ft, const uvs_ft_detect_item *item, doub
                         const uvs_kf_camera *camera, double *score, uint8_t *allowed, int32_t *cand_index, double *cand_score,
                         int32_t *new_xy, double *new_score, double *new_norm, uvs_ft_detect_result *result);
 
+/* ---- outlier rejection of the point front end (reference feature_tracker/src/feature_tracker.cpp:149-182 rejectWithF:
+ * cv::findFundamentalMat(un_cur_pts, un_forw_pts, cv::FM_RANSAC, F_THRESHOLD, 0.99, status)) ----
+ * uvs_ft_reject fits a fundamental matrix to the tracks of a frame by RANSAC over 7-point samples and says which tracks to keep.  It works on
+ * the NORMALIZED points (what uvs_ft_track returns as next_norm): the reference's virtual pinhole image, FOCAL_LENGTH x / z + COL / 2, is an
+ * isotropic scale and a shift of that plane, so the epipolar distances there are FOCAL_LENGTH times these, and the caller passes
+ * threshold = F_THRESHOLD / FOCAL_LENGTH.  It reads no image and alters no slot.  An item gives the same bits alone or in a batch and from run
+ * to run.  Every FP64 operation below is one of + - * / sqrt, rounded once, in the order written (no fused multiply-add); the one log is in the
+ * stopping rule.  Track i is (x1, y1) = prev_norm[i], (x2, y2) = next_norm[i]; F is row-major and x2' F x1 = 0.
+ *   sample      hypothesis h = 0 .. UVS_FT_REJECT_HYPOTHESES - 1 draws with the generator of uvs_lc_verify: z = mix64(seed +
+ *               0x9E3779B97F4A7C15 (1 + (h << 20) + a)) mod 2^64, mix64 = the splitmix64 finalizer, draw a = 0, 1, .. gives the track z % n; a
+ *               duplicate of an earlier draw of the hypothesis is skipped; 7 distinct tracks within 64 draws or the hypothesis is invalid.  No
+ *               collinearity test: a degenerate sample fails the pivot test
+ *   null space  row k of the 7 x 9 matrix, from the k-th track drawn: [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1].  Gauss-Jordan with
+ *               complete pivoting; no row or column is moved.  Step k = 0 .. 6: the pivot is the largest |a| over the rows and columns that
+ *               hold no pivot yet, scanned rows ascending, then columns ascending, taken on a strict >, so ties go to the lowest row, then the
+ *               lowest column.  A pivot p that is not |p| > 1e-10 |first pivot| makes the hypothesis invalid.  Over the columns c that hold no
+ *               pivot (the pivot's own excluded): a[pr][c] = a[pr][c] / p, then for each of the other six rows r, f = a[r][pc],
+ *               a[r][c] = a[r][c] - f a[pr][c].  With c1 < c2 the two columns left over: F1[c1] = 1, F1[c2] = 0, F1[pivot column of row r] =
+ *               -a[r][c1]; F2[c1] = 0, F2[c2] = 1, F2[pivot column of row r] = -a[r][c2]
+ *   cubic       det(F1 + l F2) = c0 + c1 l + c2 l^2 + c3 l^3.  A_j, B_j: column j of F1, F2;
+ *               det3(u, v, w) = (u0 (v1 w2 - v2 w1) - u1 (v0 w2 - v2 w0)) + u2 (v0 w1 - v1 w0);  c0 = det3(A0, A1, A2),
+ *               c1 = (det3(B0, A1, A2) + det3(A0, B1, A2)) + det3(A0, A1, B2), c2 = (det3(B0, B1, A2) + det3(B0, A1, B2)) + det3(A0, B1, B2),
+ *               c3 = det3(B0, B1, B2);  p(x) = ((c3 x + c2) x + c1) x + c0
+ *   roots       the hypothesis is invalid unless c0 .. c3 are finite, c3 != 0 and the Cauchy bound R = 1 + max(|c0|, |c1|, |c2|) / |c3| is
+ *               finite.  D = c2 c2 - (3 c3) c1.  D > 0: s = sqrt(D), e1 = (-c2 - s) / (3 c3), e2 = (-c2 + s) / (3 c3), each clamped to [-R, R],
+ *               lo = the smaller, hi = the larger, and the monotone intervals are [-R, lo], [lo, hi], [hi, R]; otherwise [-R, R] alone.  An
+ *               interval [a, b] holds a root iff (p(a) <= 0 and p(b) > 0) or (p(a) >= 0 and p(b) < 0).  Then 60 bisections: m = 0.5 a + 0.5 b;
+ *               b = m if p(m) is strictly on b's side of zero (> 0 in the first case, < 0 in the second), else a = m.  x = 0.5 a + 0.5 b, then
+ *               4 Newton steps x' = x - p(x) / (((3 c3) x + 2 c2) x + c1), each taken iff a <= x' <= b.  The roots are numbered r = 0, 1, 2
+ *               in ascending interval order; model (h, r) is F = F1 + l_r F2, entry by entry
+ *   error       OpenCV's computeError: a = (F0 x1 + F1 y1) + F2, b = (F3 x1 + F4 y1) + F5, c = (F6 x1 + F7 y1) + F8, s2 = (x2 a + y2 b) + c,
+ *               d2 = s2 s2 / (a a + b b);  a = (F0 x2 + F3 y2) + F6, b = (F1 x2 + F4 y2) + F7, c = (F2 x2 + F5 y2) + F8, s1 = (x1 a + y1 b) + c,
+ *               d1 = s1 s1 / (a a + b b).  A track is an inlier iff d1 <= t t and d2 <= t t, t = threshold (a NaN is an outlier)
+ *   selection   OpenCV's RANSACPointSetRegistrator::run replayed over the counts, h-major, then r: h >= niters ends the loop (niters = 1000 at
+ *               first); count > max(best, 6) makes (h, r) the best and niters = RANSACUpdateNumIters(confidence, (n - count) / n, 7, niters),
+ *               where (1 - ep)^7 is six multiplications, num = log(max(1 - confidence, DBL_MIN)), denom = log(1 - (1 - ep)^7) (niters = 0 if
+ *               that argument is < DBL_MIN), and the result is niters if denom >= 0 or -num >= niters (-denom), else num / denom rounded half
+ *               to even.  iterations = the hypotheses the loop examined.  The device evaluates the hypotheses in rounds and leaves as soon as
+ *               niters <= the hypotheses done, which gives what evaluating all of them gives
+ *   outcome     UVS_FT_REJECT_OK: a model was chosen; keep = its inlier mask, n_inliers = its count = the ones of keep, F = the model divided
+ *               by its entry of largest magnitude (the first such).  UVS_FT_REJECT_SKIPPED: n < 8 (the reference's forw_pts.size() >= 8);
+ *               UVS_FT_REJECT_NO_MODEL: no model reached 7 inliers (a camera at exact rest); in both keep is all ones, n_inliers = n,
+ *               hypothesis = root = -1 and F = 0.
+ * The numerics are restated in tests/fr_ref.py, which the device is held to bit for bit, except that `iterations` may differ where num / denom
+ * lies within rounding of a half-integer, the log being the library's; DESIGN.md 3.12 lists the deviations from OpenCV.  No CPU path. */
+#define UVS_FT_REJECT_HYPOTHESES 1000
+enum { UVS_FT_REJECT_OK = 0, UVS_FT_REJECT_SKIPPED = 1, UVS_FT_REJECT_NO_MODEL = 2 };
+
+typedef struct uvs_ft_reject_item {
+    int32_t n_points;                  /* 0 .. max_points */
+    int32_t reserved;
+    uint64_t seed;                     /* of the item's samples */
+    const double *prev_norm;           /* [n_points][2], finite */
+    const double *next_norm;           /* [n_points][2], finite */
+} uvs_ft_reject_item;
+
+typedef struct uvs_ft_reject_result {
+    int32_t status;                    /* UVS_FT_REJECT_* */
+    int32_t n_inliers;                 /* the ones of the item's keep */
+    int32_t hypothesis, root;          /* the chosen model, -1 if none */
+    int32_t iterations;                /* hypotheses the selection examined */
+    int32_t reserved;
+    double F[9];                       /* row-major, largest |entry| = 1; 0 if none */
+} uvs_ft_reject_result;
+
+/* keep[] is PACKED over the items in order: item i owns n_points_i bytes (1 = keep the track, 0 = drop it).  results[n_items].
+ * UVS_ERR_INVALID_ARG: null pointer, n_items outside 1 .. max_streams, n_points outside 0 .. max_points, a null array behind a positive count,
+ * a threshold that is not finite and positive, a confidence outside (0, 1), a coordinate that is not finite.  A rejected call changes nothing,
+ * and the handle stays usable. */
+int uvs_ft_reject(uvs_ft_tracker *ft, int n_items, const uvs_ft_reject_item *items, double threshold, double confidence, uint8_t *keep,
+                  uvs_ft_reject_result *results);
+/* HIP-event time of the last successful uvs_ft_reject: upload, the kernel, download, on the handle's stream (milliseconds). */
+double uvs_ft_last_reject_device_ms(const uvs_ft_tracker *ft);
+/* Diagnostic (tests only): ONE item through the same kernel with every round evaluated, and every hypothesis's samples[1000][7] (-1 where the
+ * draw failed), models[1000][3][9] (F1 + l_r F2, unscaled; 0 where there is none) and counts[1000][3] (-1 where there is none), besides
+ * keep[n_points] and the result as uvs_ft_reject gives them. */
+int uvs_ft_debug_reject(uvs_ft_tracker *ft, const uvs_ft_reject_item *item, double threshold, double confidence, int32_t *samples, double *models,
+                        int32_t *counts, uint8_t *keep, uvs_ft_reject_result *result);
+
 #ifdef __cplusplus
 }
 #endif

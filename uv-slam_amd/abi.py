@@ -665,3 +665,32 @@ def ft_detect_items(items):
         arr[b].max_new = int(d["max_new"])
         arr[b].occupied_xy = occ.ctypes.data_as(c_double_p) if len(occ) else None
     return arr, keep
+
+
+# ---- outlier rejection of the point front end (uvs_ft_reject, include/uvs_solver.h) ---------------------------------------
+FT_REJECT_HYPOTHESES = 1000
+FT_REJECT_OK, FT_REJECT_SKIPPED, FT_REJECT_NO_MODEL = 0, 1, 2
+
+
+class FtRejectItem(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("prev_norm", c_double_p), ("next_norm", c_double_p)]
+
+
+class FtRejectResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_inliers", C.c_int32), ("hypothesis", C.c_int32), ("root", C.c_int32), ("iterations", C.c_int32),
+                ("reserved", C.c_int32), ("F", C.c_double * 9)]
+
+
+def ft_reject_items(items):
+    """(FtRejectItem array, keepalive) from dicts with prev [n, 2] and next [n, 2] float64 normalized points and seed."""
+    arr = (FtRejectItem * max(len(items), 1))()
+    keep = []
+    for b, d in enumerate(items):
+        prev = np.ascontiguousarray(d["prev"], dtype=np.float64).reshape(-1, 2)
+        nxt = np.ascontiguousarray(d["next"], dtype=np.float64).reshape(-1, 2)
+        keep += [prev, nxt]
+        arr[b].n_points = int(d.get("n_points", len(prev)))          # n_points: for the tests of the argument checks
+        arr[b].seed = int(d.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+        arr[b].prev_norm = prev.ctypes.data_as(c_double_p) if len(prev) else None
+        arr[b].next_norm = nxt.ctypes.data_as(c_double_p) if len(nxt) else None
+    return arr, keep

@@ -25,6 +25,7 @@ EXPORTS = [
     "uvs_kf_create", "uvs_kf_destroy", "uvs_kf_last_error", "uvs_kf_extract", "uvs_kf_last_device_ms", "uvs_kf_debug_frame",
     "uvs_ft_create", "uvs_ft_destroy", "uvs_ft_last_error", "uvs_ft_reset", "uvs_ft_track", "uvs_ft_last_device_ms", "uvs_ft_debug_pyramid", "uvs_ft_debug_point",
     "uvs_ft_set_max_candidates", "uvs_ft_set_mask", "uvs_ft_detect", "uvs_ft_last_detect_device_ms", "uvs_ft_debug_detect",
+    "uvs_ft_reject", "uvs_ft_last_reject_device_ms", "uvs_ft_debug_reject",
 ]
 
 
@@ -135,6 +136,12 @@ def lib():
         L.uvs_ft_debug_detect.argtypes = [C.c_void_p, C.POINTER(abi.FtDetectItem), C.c_double, C.c_int, C.POINTER(abi.KfCamera), abi.c_double_p, abi.c_u8_p,
                                           abi.c_i32_p, abi.c_double_p, abi.c_i32_p, abi.c_double_p, abi.c_double_p, C.POINTER(abi.FtDetectResult)]
         L.uvs_ft_debug_detect.restype = C.c_int
+        L.uvs_ft_reject.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.FtRejectItem), C.c_double, C.c_double, abi.c_u8_p, C.POINTER(abi.FtRejectResult)]
+        L.uvs_ft_reject.restype = C.c_int
+        L.uvs_ft_last_reject_device_ms.argtypes = [C.c_void_p]; L.uvs_ft_last_reject_device_ms.restype = C.c_double
+        L.uvs_ft_debug_reject.argtypes = [C.c_void_p, C.POINTER(abi.FtRejectItem), C.c_double, C.c_double, abi.c_i32_p, abi.c_double_p, abi.c_i32_p,
+                                          abi.c_u8_p, C.POINTER(abi.FtRejectResult)]
+        L.uvs_ft_debug_reject.restype = C.c_int
         _lib = L
     return _lib
 
@@ -904,4 +911,60 @@ class FeatureTracker:
         out = self._detect_split(o, [res], [M])[0]
         n = min(out["n_candidates"], self.max_candidates)
         out.update(score_map=smap, allowed=allowed, cand_index=ci[:n].copy(), cand_score=cs[:n].copy())
+        return out
+
+    # ---- outlier rejection: fundamental-matrix RANSAC over the tracks of a frame (uvs_ft_reject)
+    @staticmethod
+    def _reject_dict(r, keep):
+        return dict(status=int(r.status), n_inliers=int(r.n_inliers), hypothesis=int(r.hypothesis), root=int(r.root), iterations=int(r.iterations),
+                    F=np.array(r.F[:], np.float64), keep=keep.copy())
+
+    def reject_raw(self, items, threshold, confidence=0.99, n_items=None, null=()):
+        """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  n_items overrides the count passed; `null`
+        names arguments passed as NULL ("items", "keep", "results")."""
+        arr, keepalive = abi.ft_reject_items(items)
+        npt = [max(int(arr[b].n_points), 0) for b in range(len(items))]
+        keep = np.zeros(max(sum(npt), 1), np.uint8)
+        res = (abi.FtRejectResult * max(len(items), 1))()
+        args = dict(items=C.cast(arr, C.POINTER(abi.FtRejectItem)), keep=keep.ctypes.data_as(abi.c_u8_p), results=C.cast(res, C.POINTER(abi.FtRejectResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_ft_reject(self._h, len(items) if n_items is None else int(n_items), args["items"], float(threshold), float(confidence),
+                                 args["keep"], args["results"])
+        self.last_reject_ms = (time.perf_counter() - t0) * 1e3      # the whole C-ABI call
+        if rc != abi.UVS_OK:
+            return rc, []
+        off = np.r_[0, np.cumsum(npt)].astype(int)
+        return rc, [self._reject_dict(res[b], keep[off[b]:off[b + 1]]) for b in range(len(items))]
+
+    def reject(self, items, threshold, confidence=0.99):
+        """items: list of dicts (prev [n, 2], next [n, 2] float64 NORMALIZED points of the tracks; seed); threshold in normalized units
+        (F_THRESHOLD / FOCAL_LENGTH).  -> one dict per item: keep [n] uint8 (1 = keep the track), status (abi.FT_REJECT_*), n_inliers,
+        hypothesis, root, iterations, F [9] float64."""
+        rc, out = self.reject_raw(items, threshold, confidence)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_reject", rc)
+        return out
+
+    def last_reject_device_ms(self):
+        """HIP events around upload, kernel and download of the last reject()."""
+        return float(lib().uvs_ft_last_reject_device_ms(self._h))
+
+    def debug_reject(self, item, threshold, confidence=0.99):
+        """ONE item (tests only), every round evaluated -> the item's dict of reject() plus samples [1000, 7] int32, models [1000, 3, 9] float64 and
+        counts [1000, 3] int32 of every hypothesis."""
+        arr, keepalive = abi.ft_reject_items([item])
+        n = max(int(arr[0].n_points), 0)
+        keep = np.zeros(max(n, 1), np.uint8)
+        smp = np.zeros((abi.FT_REJECT_HYPOTHESES, 7), np.int32); mod = np.zeros((abi.FT_REJECT_HYPOTHESES, 3, 9))
+        cnt = np.zeros((abi.FT_REJECT_HYPOTHESES, 3), np.int32)
+        res = abi.FtRejectResult()
+        rc = lib().uvs_ft_debug_reject(self._h, C.cast(arr, C.POINTER(abi.FtRejectItem)), float(threshold), float(confidence),
+                                       smp.ctypes.data_as(abi.c_i32_p), abi._dp(mod), cnt.ctypes.data_as(abi.c_i32_p), keep.ctypes.data_as(abi.c_u8_p),
+                                       C.byref(res))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_debug_reject", rc)
+        out = self._reject_dict(res, keep[:n])
+        out.update(samples=smp, models=mod, counts=cnt)
         return out

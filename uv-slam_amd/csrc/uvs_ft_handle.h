@@ -1,5 +1,6 @@
-// uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the two units of the point front end: csrc/uvs_feature_track.hip (creates and
-// destroys it, builds the pyramids, tracks) and csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid).  Host only.
+// uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the three units of the point front end: csrc/uvs_feature_track.hip (creates
+// and destroys it, builds the pyramids, tracks), csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid) and
+// csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -30,6 +31,10 @@ struct uvs_ft_tracker {
     DevBuf<uint8_t> d_mask;                     // [max_streams] resident masks, each laid out as level 0 of a pyramid (first uvs_ft_set_mask)
     DevBuf<char> d_det;                         // one call's meta data, maps, candidate keys and outputs, sized by the images of the call
     PinnedBuf<char> h_det_in, h_det_out;        // pinned staging of uvs_ft_detect
+    // outlier rejection (uvs_feature_reject.hip): allocated by the first call that needs them
+    DevBuf<char> d_rej;                         // one call's item table and points, results and keep masks, and the debug arrays
+    PinnedBuf<char> h_rej_in, h_rej_out;        // pinned staging of uvs_ft_reject
+    float reject_ms = 0.f;                      // uvs_ft_last_reject_device_ms
     ~uvs_ft_tracker() {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);

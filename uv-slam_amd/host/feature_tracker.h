@@ -1,10 +1,12 @@
-// feature_tracker.h -- the reference's point front end (feature_tracker/src/feature_tracker.cpp:9-147, 184-196, 240-288: setMask, addPoints,
-// readImage, updateID, undistortedPoints) in the reference's own terms, above uvs_ft_track() and uvs_ft_detect(): an image in, cur_pts / ids /
-// track_cnt / cur_un_pts / pts_velocity out.  Header-only.  The optical flow, the inBorder cut, the detection of new points and liftProjective
-// are on the GPU (csrc/uvs_feature_track.hip, csrc/uvs_feature_detect.hip); what is here is the bookkeeping around them.  Differences from the
-// reference, all from the C ABI below: positions are FP64 (cv::Point2f there), setMask orders with a stable sort and keeps no image (the
-// occupied points go to uvs_ft_detect, whose disc is Euclidean), rejectWithF and CLAHE are not here, and n_id is a member, not a static, so
-// that two trackers of one process number their points apart.  With max_cnt = 0 (the default) new points are the caller's, through a Detector.
+// feature_tracker.h -- the reference's point front end (feature_tracker/src/feature_tracker.cpp:9-196, 240-288: setMask, addPoints, readImage,
+// rejectWithF, updateID, undistortedPoints) in the reference's own terms, above uvs_ft_track(), uvs_ft_reject() and uvs_ft_detect(): an image
+// in, cur_pts / ids / track_cnt / cur_un_pts / pts_velocity out.  Header-only.  The optical flow, the inBorder cut, the fundamental-matrix
+// RANSAC, the detection of new points and liftProjective are on the GPU (csrc/uvs_feature_track.hip, csrc/uvs_feature_reject.hip,
+// csrc/uvs_feature_detect.hip); what is here is the bookkeeping around them.  Differences from the reference, all from the C ABI below:
+// positions are FP64 (cv::Point2f there), setMask orders with a stable sort and keeps no image (the occupied points go to uvs_ft_detect, whose
+// disc is Euclidean), rejectWithF works on the normalized points with F_THRESHOLD / FOCAL_LENGTH (the same test as on the reference's virtual
+// image) and is off unless f_threshold > 0, CLAHE is not here, and n_id is a member, not a static, so that two trackers of one process number
+// their points apart.  With max_cnt = 0 (the default) new points are the caller's, through a Detector.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -49,6 +51,18 @@ public:
             reduceVector(cur_un_pts, status); reduceVector(track_cnt, status); reduceVector(forw_norm_, status);
         }
         for (auto& n : track_cnt) n++;
+    }
+
+    // :149-182 after findFundamentalMat: the six reduceVector calls by its status (keep[i] != 0 keeps track i), and the device's normalized
+    // forward points alike.  keep has one entry per forward point; any other size changes nothing and returns false.
+    bool applyReject(const std::vector<uint8_t>& keep) {
+        if (keep.size() != forw_pts.size()) return false;
+        const bool with_norm = forw_norm_.size() == forw_pts.size();
+        if (prev_pts.size() <= keep.size()) reduceVector(prev_pts, keep);      // (longer than the tracks: the reference reads past its status there)
+        reduceVector(cur_pts, keep); reduceVector(forw_pts, keep); reduceVector(cur_un_pts, keep);
+        reduceVector(ids, keep); reduceVector(track_cnt, keep);
+        if (with_norm) reduceVector(forw_norm_, keep);
+        return true;
     }
 
     // :9-42.  The points are ordered by track_cnt descending (a STABLE sort: the reference's std::sort leaves the order of ties open), and a
@@ -163,7 +177,9 @@ public:
     // :54-147 with PUB_THIS_FRAME set.  image: [height][width] grey levels (after CLAHE, if the caller wants it).  Returns UVS_OK or the error
     // of uvs_ft_track (its text in last_error; the vectors are unchanged then).  Without a Detector and with max_cnt > 0 the frame goes on as
     // :109-139 does: setMask, uvs_ft_detect of max_cnt - forw_pts.size() points with the kept points occupied, addPoints; an error of the
-    // detection is returned after the frame has been finished without new points.
+    // detection is returned after the frame has been finished without new points.  With f_threshold > 0 rejectWithF (:111) runs between the
+    // flow and setMask / the Detector, on frames that carry at least 8 tracks; an error of it is returned after the frame has been finished
+    // with every track kept.
     int readImage(const uint8_t* image, int width, int height, double time, const Detector& detect = nullptr) {
         const size_t n = cur_pts.size();
         xy_.resize(2 * n + 2); nxt_.resize(2 * n + 2); nrm_.resize(2 * n + 2); st_.resize(n + 1); it_.resize(n + 1);
@@ -176,6 +192,8 @@ public:
         std::vector<Point2d> next(n), norm(n);
         for (size_t i = 0; i < n; ++i) { next[i].x = nxt_[2 * i]; next[i].y = nxt_[2 * i + 1]; norm[i].x = nrm_[2 * i]; norm[i].y = nrm_[2 * i + 1]; }
         applyFlow(time, next, std::vector<int32_t>(st_.begin(), st_.begin() + n), norm);
+        const int rej_rc = f_threshold > 0.0 ? rejectWithF() : UVS_OK;
+        ++frame_cnt_;
         n_pts.clear();
         int det_rc = UVS_OK;
         if (detect) detect(*this, n_pts);
@@ -185,15 +203,34 @@ public:
         }
         addPoints();
         rotate();
-        return det_rc;
+        return rej_rc != UVS_OK ? rej_rc : det_rc;
     }
 
     int max_cnt = 0;                  // MAX_CNT; 0: new points are the Detector's
     int min_dist = 30;                // MIN_DIST
     double quality_level = 0.01;
+    double f_threshold = 0.0;         // F_THRESHOLD in pixels of the virtual image; 0: rejectWithF is off
+    double focal_length = 460.0;      // FOCAL_LENGTH
+    uint64_t ransac_seed = 0;         // frame k (0, 1, ..) samples with ransac_seed + k
+    uvs_ft_reject_result last_reject = {};      // of the last frame that ran rejectWithF
     std::string last_error;
 
 private:
+    // :149-182: cur_un_pts and the device's normalized forward points through uvs_ft_reject, then the reduceVector calls
+    int rejectWithF() {
+        const size_t n = forw_pts.size();
+        if (n < 8 || cur_un_pts.size() != n || forw_norm_.size() != n) return UVS_OK;
+        xy_.resize(2 * n + 2); nrm_.resize(2 * n + 2);
+        for (size_t i = 0; i < n; ++i) { xy_[2 * i] = cur_un_pts[i].x; xy_[2 * i + 1] = cur_un_pts[i].y; nrm_[2 * i] = forw_norm_[i].x; nrm_[2 * i + 1] = forw_norm_[i].y; }
+        uvs_ft_reject_item item;
+        item.n_points = (int32_t)n; item.reserved = 0; item.seed = ransac_seed + frame_cnt_; item.prev_norm = xy_.data(); item.next_norm = nrm_.data();
+        std::vector<uint8_t> keep(n);
+        const int rc = uvs_ft_reject(ft_, 1, &item, f_threshold / focal_length, 0.99, keep.data(), &last_reject);
+        if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
+        applyReject(keep);
+        return UVS_OK;
+    }
+
     // :119-131: fills n_pts and appends the device's normalized points, so that undistortedPoints uses them for the new points too
     int detectNew() {
         if (mask_pending_) {
@@ -223,6 +260,7 @@ private:
     }
 
     int max_points_ = 0;
+    uint64_t frame_cnt_ = 0;          // frames read
     std::vector<uint8_t> image_mask_;
     int mask_w_ = 0, mask_h_ = 0;
     bool mask_pending_ = false;

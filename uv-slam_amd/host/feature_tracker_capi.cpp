@@ -4,6 +4,8 @@
 //   camera[8] = fx, fy, cx, cy, k1, k2, p1, p2; new_xy[n_new][2]: the points the caller's detector adds in this frame.
 // uvs_host_ft_set_detection turns the tracker's own detection on (max_cnt > 0): uvs_host_ft_read_image_detect then runs a frame without a
 // Detector, and uvs_host_ft_apply_set_mask a frame of the bookkeeping with setMask between the flow and addPoints.
+// uvs_host_ft_set_rejection turns rejectWithF on (f_threshold > 0) for the frames that follow, and uvs_host_ft_apply_reject is a frame of the
+// bookkeeping with a given keep mask between the flow and addPoints.
 #include <cstdio>
 #include <memory>
 #include "feature_tracker.h"
@@ -100,6 +102,40 @@ int uvs_host_ft_apply_set_mask(void* hv, double time, int n, const double* next_
     b.addPoints();
     b.rotate();
     return UVS_OK;
+}
+
+// f_threshold (pixels at focal_length; 0 turns rejectWithF off), focal_length, ransac_seed of a device handle
+int uvs_host_ft_set_rejection(void* hv, double f_threshold, double focal_length, unsigned long long ransac_seed) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev || !(f_threshold >= 0.0) || !(focal_length > 0.0)) return UVS_ERR_INVALID_ARG;
+    h->dev->f_threshold = f_threshold; h->dev->focal_length = focal_length; h->dev->ransac_seed = ransac_seed;
+    return UVS_OK;
+}
+
+// status, n_inliers, hypothesis, root, iterations of the last frame that ran rejectWithF (a device handle)
+int uvs_host_ft_last_reject(void* hv, int* out5) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev || !out5) return UVS_ERR_INVALID_ARG;
+    const uvs_ft_reject_result& r = h->dev->last_reject;
+    out5[0] = r.status; out5[1] = r.n_inliers; out5[2] = r.hypothesis; out5[3] = r.root; out5[4] = r.iterations;
+    return UVS_OK;
+}
+
+// uvs_host_ft_read_flow with applyReject(keep) between the flow and addPoints (the bookkeeping alone: no device is touched); keep[n_keep], n_keep
+// = the points the flow left
+int uvs_host_ft_apply_reject(void* hv, double time, int n, const double* next_xy, const int* ft_status, const double* next_norm, int n_keep,
+                             const unsigned char* keep, int n_new, const double* new_xy) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || n < 0 || n_new < 0 || n_keep < 0 || (n > 0 && (!next_xy || !ft_status || !next_norm)) || (n_keep > 0 && !keep) || (n_new > 0 && !new_xy))
+        return UVS_ERR_INVALID_ARG;
+    uvs::FeatureTrackerBook& b = h->b();
+    if ((size_t)n != b.cur_pts.size()) return UVS_ERR_INVALID_ARG;
+    b.applyFlow(time, points(n, next_xy), std::vector<int32_t>(ft_status, ft_status + n), points(n, next_norm));
+    const bool ok = b.applyReject(std::vector<uint8_t>(keep, keep + n_keep));
+    b.n_pts = points(n_new, new_xy);
+    b.addPoints();
+    b.rotate();
+    return ok ? UVS_OK : UVS_ERR_INVALID_ARG;
 }
 
 // updateID(i) for i = 0, 1, .. as the node does after readImage (feature_tracker_node.cpp); returns the number of points
