@@ -553,6 +553,27 @@ const char *uvs_lc_last_error(const uvs_loop_verifier *lc);
 int uvs_lc_verify(uvs_loop_verifier *lc, int n_pairs, const uvs_lc_pair *pairs, const double tic[3], const double qic_xyzw[4],
                   int32_t *match_old, uint8_t *inlier, uvs_lc_result *results);
 
+/* Diagnostic (tests only): ONE pair through a second instantiation of the same kernel body, which also writes every intermediate value of
+ * the PnP-RANSAC into trace[UVS_LC_TRACE_LEN] (doubles; integers and flags as 0.0 / 1.0 / counts; zeroed before the run, so what the kernel
+ * did not reach stays 0).  match_old[n_query], inlier[n_query] and *result are bit for bit what uvs_lc_verify gives for the pair.
+ *   record r = 0 .. 99 (hypothesis r) and r = 100 (the refinement) at trace + r * UVS_LC_TRACE_REC_LEN:
+ *     [0..4] sample match indices (-1 where the draw failed; hypotheses only)   [5] valid (refinement: 1 once it ran)
+ *     [6] iteration records written   [7] initial cost   [8..19] final R (row-major), t   [20] draw succeeded (hypotheses);
+ *     [20..31] start R, t (refinement: the chosen hypothesis's final pose)
+ *     iteration i at + UVS_LC_TRACE_HEAD_LEN + i * UVS_LC_TRACE_ITER_LEN:
+ *       [0..11] start R, t   [12] lambda   [13..40] packed upper J^T J (21), J^T r (6), cost (the block sum in the refinement)
+ *       [41] Cholesky succeeded   [42..47] delta   [48..59] candidate R, t   [60] candidate cost   [61] current cost   [62] accepted
+ *       [63] stop (|delta| below the threshold).  After a failed Cholesky [42..63] stay 0.
+ *   at trace + UVS_LC_TRACE_STAGE_OFF: [0] n matches, then X[UVS_LC_MAX_QUERY][3], uv[UVS_LC_MAX_QUERY][2] and the query index
+ *     [UVS_LC_MAX_QUERY] of match m as the kernel staged them (the first n rows of each). */
+#define UVS_LC_TRACE_HEAD_LEN 32
+#define UVS_LC_TRACE_ITER_LEN 64
+#define UVS_LC_TRACE_REC_LEN (UVS_LC_TRACE_HEAD_LEN + 20 * UVS_LC_TRACE_ITER_LEN)
+#define UVS_LC_TRACE_STAGE_OFF ((UVS_LC_N_HYPOTHESES + 1) * UVS_LC_TRACE_REC_LEN)
+#define UVS_LC_TRACE_LEN (UVS_LC_TRACE_STAGE_OFF + 1 + 6 * UVS_LC_MAX_QUERY)
+int uvs_lc_debug_pair(uvs_loop_verifier *lc, const uvs_lc_pair *pair, const double tic[3], const double qic_xyzw[4],
+                      int32_t *match_old, uint8_t *inlier, uvs_lc_result *result, double *trace);
+
 /* ---- vanishing points of the line front end (reference feature_tracker/src/line_feature_tracker.cpp:1977-2299) ----
  * Estimates, for a batch of frames in one call, the three orthogonal vanishing points of each frame's line segments and tags every line with
  * the one it runs towards; a frame gives the same bits alone or in a batch, and from run to run.  Per frame: 105 line pairs (a counter-based

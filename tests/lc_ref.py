@@ -34,6 +34,14 @@ CONFIDENCE = 0.99
 GOLD = 0x9E3779B97F4A7C15
 M64 = (1 << 64) - 1
 
+# the trace of uvs_lc_debug_pair (UVS_LC_TRACE_* of include/uvs_solver.h), which verify(trace=True) fills from this file's own FP64 run
+TRACE_HEAD, TRACE_ITER = 32, 64
+TRACE_REC = TRACE_HEAD + LM_ITERS * TRACE_ITER
+TRACE_STAGE = (N_HYP + 1) * TRACE_REC
+MAX_QUERY = 1024
+TRACE_LEN = TRACE_STAGE + 1 + 6 * MAX_QUERY
+_IU = np.triu_indices(6)
+
 REASON = dict(ACCEPTED=0, NO_MATCHES=1, FEW_MATCHES=2, RANSAC_FAILED=3, FEW_INLIERS=4, YAW_GATE=5, T_GATE=6)
 
 
@@ -137,8 +145,10 @@ def cholesky_solve(M, g):
     return x, ok
 
 
-def lm(R0, t0, X, uv, refine=False):
-    """The LM of the header, batched over H problems of m points each.  -> (R [H,3,3], t [H,3], valid [H])."""
+def lm(R0, t0, X, uv, refine=False, rec=None):
+    """The LM of the header, batched over H problems of m points each.  -> (R [H,3,3], t [H,3], valid [H]).
+    rec [H, TRACE_REC] (optional): the trace records of the H problems, filled as uvs_lc_debug_pair fills them (iterations, initial cost,
+    iteration records; the caller writes samples, validity and poses)."""
     R = np.array(R0, np.float64); t = np.array(t0, np.float64)
     H = R.shape[0]
     with np.errstate(all="ignore"):
@@ -146,7 +156,10 @@ def lm(R0, t0, X, uv, refine=False):
         valid = np.isfinite(cost) if not refine else np.ones(H, bool)
         active = valid.copy()
         lam = np.full(H, LAMBDA0)
-        for _ in range(LM_ITERS):
+        if rec is not None:
+            rec[:, 7] = cost
+            its = rec[:, TRACE_HEAD:].reshape(H, LM_ITERS, TRACE_ITER)
+        for it in range(LM_ITERS):
             if not active.any():
                 break
             r, J, _ = residual_jacobian(R, t, X, uv)
@@ -154,6 +167,12 @@ def lm(R0, t0, X, uv, refine=False):
             g = np.einsum("hmki,hmk->hi", J, r)
             M = A + lam[:, None, None] * (np.eye(6) * np.diagonal(A, 0, 1, 2)[:, None, :])
             d, ok = cholesky_solve(M, g)
+            if rec is not None:
+                a = np.flatnonzero(active)
+                rec[a, 6] = it + 1
+                its[a, it, 0:9] = R[a].reshape(-1, 9); its[a, it, 9:12] = t[a]; its[a, it, 12] = lam[a]
+                its[a, it, 13:34] = A[a][:, _IU[0], _IU[1]]; its[a, it, 34:40] = g[a]; its[a, it, 40] = (r[a] * r[a]).sum((-1, -2))
+                its[a, it, 41] = ok[a]
             fail = active & ~ok
             if refine:
                 active &= ~fail
@@ -163,10 +182,16 @@ def lm(R0, t0, X, uv, refine=False):
             tc = t + d[:, 3:]
             cc = cost_of(Rc, tc, X, uv)
             acc = active & (cc < cost)
+            if rec is not None:
+                a = np.flatnonzero(active)
+                its[a, it, 42:48] = d[a]; its[a, it, 48:57] = Rc[a].reshape(-1, 9); its[a, it, 57:60] = tc[a]
+                its[a, it, 60] = cc[a]; its[a, it, 61] = cost[a]; its[a, it, 62] = acc[a]
             R = np.where(acc[:, None, None], Rc, R); t = np.where(acc[:, None], tc, t)
             cost = np.where(acc, cc, cost)
             lam = np.where(active, np.where(acc, lam / 10.0, lam * 10.0), lam)
             small = np.sqrt((d * d).sum(-1)) < FLT_EPSILON * np.maximum(1.0, np.sqrt((t * t).sum(-1)))
+            if rec is not None:
+                its[a, it, 63] = small[a]
             active &= ~small
     return R, t, valid
 
@@ -251,9 +276,17 @@ def normalize_angle(a):
 
 
 # ---------------------------------------------------------------- one pair
-def verify(pair, tic, qic):
+def verify(pair, tic, qic, trace=False):
     """pair: dict(p3d [nq,3], qdesc [nq,4] u64, vio_t [3], vio_q [4] xyzw, uv [no,2], odesc [no,4] u64, seed).
-    -> dict with the fields of uvs_lc_result plus match_old [nq], inlier [nq] (uint8), margin (threshold_margin over every hypothesis)."""
+    -> dict with the fields of uvs_lc_result plus match_old [nq], inlier [nq] (uint8), margin (threshold_margin over every hypothesis).
+    trace=True: -> (that dict, raw [TRACE_LEN]): the trace of uvs_lc_debug_pair from this FP64 run, in the header's layout."""
+    if trace:
+        raw = np.zeros(TRACE_LEN)
+        return _verify(pair, tic, qic, raw), raw
+    return _verify(pair, tic, qic, None)
+
+
+def _verify(pair, tic, qic, raw):
     p3d = np.asarray(pair["p3d"], np.float64).reshape(-1, 3); uvo = np.asarray(pair["uv"], np.float64).reshape(-1, 2)
     nq = len(p3d)
     out = dict(accepted=0, reason=REASON["NO_MATCHES"], n_matches=0, n_inliers=0, best_hypothesis=-1, ransac_iters=0,
@@ -262,6 +295,13 @@ def verify(pair, tic, qic):
     mi = np.flatnonzero(out["match_old"] >= 0)
     n = len(mi)
     out["n_matches"] = n
+    rec = None
+    if raw is not None:
+        rec = raw[:TRACE_STAGE].reshape(N_HYP + 1, TRACE_REC)
+        st = raw[TRACE_STAGE:]
+        st[0] = n
+        st[1:1 + 3 * n] = p3d[mi].ravel(); st[1 + 3 * MAX_QUERY:1 + 3 * MAX_QUERY + 2 * n] = uvo[out["match_old"][mi]].ravel()
+        st[1 + 5 * MAX_QUERY:1 + 5 * MAX_QUERY + n] = mi
     if n == 0:
         return out
     if n <= MIN_LOOP_NUM:
@@ -275,8 +315,16 @@ def verify(pair, tic, qic):
     samples = [draw(seed, h, n) for h in range(N_HYP)]
     ok = np.array([s is not None for s in samples])
     S = np.array([s if s is not None else [0] * MODEL_POINTS for s in samples])
-    Rh, th, valid = lm(np.broadcast_to(R0, (N_HYP, 3, 3)), np.broadcast_to(t0, (N_HYP, 3)), X[S], uv[S])
-    valid &= ok
+    if rec is not None:       # a failed draw runs no LM on the device: this file's batched LM runs it on the stand-in sample, so its record is cleared below
+        Rh, th, valid = lm(np.broadcast_to(R0, (N_HYP, 3, 3)), np.broadcast_to(t0, (N_HYP, 3)), X[S], uv[S], rec=rec[:N_HYP])
+        rec[:N_HYP][~ok] = 0.0
+        Rh[~ok] = R0; th[~ok] = t0
+        valid &= ok
+        rec[:N_HYP, 0:5] = np.where(ok[:, None], S, -1); rec[:N_HYP, 5] = valid; rec[:N_HYP, 20] = ok
+        rec[:N_HYP, 8:17] = Rh.reshape(N_HYP, 9); rec[:N_HYP, 17:20] = th
+    else:
+        Rh, th, valid = lm(np.broadcast_to(R0, (N_HYP, 3, 3)), np.broadcast_to(t0, (N_HYP, 3)), X[S], uv[S])
+        valid &= ok
     counts = -np.ones(N_HYP, np.int32)
     for h in np.flatnonzero(valid):
         counts[h] = int(inlier_mask(Rh[h], th[h], X, uv).sum())
@@ -289,8 +337,12 @@ def verify(pair, tic, qic):
     mask = inlier_mask(Rh[best], th[best], X, uv)
     out["inlier"][mi[mask]] = 1
     out["n_inliers"] = int(mask.sum())
-    Rr, tr, _ = lm(Rh[best][None], th[best][None], X[mask][None], uv[mask][None], refine=True)
+    Rr, tr, _ = lm(Rh[best][None], th[best][None], X[mask][None], uv[mask][None], refine=True, rec=None if rec is None else rec[N_HYP:])
     R_pnp, T_pnp = Rr[0], tr[0]
+    if rec is not None:
+        rec[N_HYP, 5] = 1.0
+        rec[N_HYP, 8:17] = R_pnp.ravel(); rec[N_HYP, 17:20] = T_pnp
+        rec[N_HYP, 20:29] = Rh[best].ravel(); rec[N_HYP, 29:32] = th[best]
     R_w_c_old = R_pnp.T; T_w_c_old = R_w_c_old @ (-T_pnp)
     PnP_R_old = R_w_c_old @ ric.T; PnP_T_old = T_w_c_old - PnP_R_old @ tic
     qw = R_to_quat_eigen(PnP_R_old)

@@ -111,7 +111,7 @@ def test_noiseless_pnp_recovers_the_pose():
 
 
 # ================================================================ CPU: the ABI
-LC_SYMBOLS = ["uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify"]
+LC_SYMBOLS = ["uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify", "uvs_lc_debug_pair"]
 
 
 def test_lc_symbols_exported():
@@ -304,6 +304,61 @@ def test_gpu_mh05_end_to_end_loops_correct_the_drift():
     a_before, a_after = _check_mh05(run, yaw_t[:, 1:])
     print(f"MH_05: {len(run['eligible'])} eligible candidates, accepted {run['accept_rate']:.2f}; decoys accepted {run['decoys_accepted']} of "
           f"{len(run['decoys'])}; loop_info error <= {run['t_err'] * 100:.2f} cm / {run['yaw_err']:.3f} deg; ATE {a_before:.3f} -> {a_after:.3f} m")
+    v.close()
+
+
+def _non_finite_cases():
+    """`clean` with one matched input made non-finite -> name -> (pair, the match index m that is bad, or None for vio_t)."""
+    base = lc.unit_pairs()["clean"]
+    mo = lc_ref.match(base["qdesc"], base["odesc"])
+    mi = np.flatnonzero(mo >= 0)
+    m = 7; q = int(mi[m])
+    out = {}
+    for name, val in (("p3d_nan", np.nan), ("p3d_inf", np.inf)):
+        p = dict(base); p["p3d"] = np.array(base["p3d"], np.float64); p["p3d"][q, 1] = val
+        out[name] = (p, m)
+    p = dict(base); p["uv"] = np.array(base["uv"], np.float64); p["uv"][mo[q], 0] = np.nan
+    out["uv_nan"] = (p, m)
+    p = dict(base); p["vio_t"] = np.array(base["vio_t"], np.float64); p["vio_t"][2] = np.nan
+    out["vio_t_nan"] = (p, None)
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_non_finite_inputs_follow_the_kernels_rules():
+    """uvs_lc_verify forwards non-finite coordinates to the kernel, whose rules then apply: a hypothesis whose initial cost is not finite is
+    invalid (-1), and a match whose error is NaN is never an inlier.  The call succeeds and every double it returns is finite."""
+    v = _gpu_verifier(max_pairs=1)
+    tic, qic = lc.extrinsic()
+    for name, (pair, m) in _non_finite_cases().items():
+        rc, res, mo, inl = v.verify_raw([pair], tic, qic)
+        assert rc == abi.UVS_OK, name
+        r, mo, inl = res[0], mo[0], inl[0]
+        ref = lc_ref.verify(pair, tic, qic)
+        n = ref["n_matches"]
+        assert np.array_equal(mo, ref["match_old"]) and r["n_matches"] == n == 60, name
+        for k in ("loop_info", "PnP_T_old", "PnP_q_old"):
+            assert np.all(np.isfinite(r[k])), (name, k, r[k])
+        if m is None:
+            assert r["reason"] == R["RANSAC_FAILED"] and r["accepted"] == 0 and r["best_hypothesis"] == -1 and r["ransac_iters"] == 100, name
+            assert np.all(r["hyp_inliers"] == -1) and not inl.any() and r["n_inliers"] == 0, name
+            assert not r["loop_info"].any() and not r["PnP_T_old"].any() and np.array_equal(r["PnP_q_old"], [0.0, 0.0, 0.0, 1.0]), name
+            assert ref["reason"] == R["RANSAC_FAILED"] and np.all(ref["hyp_inliers"] == -1), name
+            continue
+        seed = int(pair["seed"]) & lc_ref.M64
+        drew = np.array([m in lc_ref.draw(seed, h, n) for h in range(lc_ref.N_HYP)])
+        assert 0 < drew.sum() < lc_ref.N_HYP, name
+        assert np.all(r["hyp_inliers"][drew] == -1) and np.all(r["hyp_inliers"][~drew] >= 0), (name, r["hyp_inliers"])
+        assert ref["margin"] > 1e-9, (name, ref["margin"])
+        assert np.array_equal(r["hyp_inliers"], ref["hyp_inliers"]), (name, np.flatnonzero(r["hyp_inliers"] != ref["hyp_inliers"]))
+        for k in ("accepted", "reason", "n_inliers", "best_hypothesis", "ransac_iters"):
+            assert r[k] == ref[k], (name, k, r[k], ref[k])
+        assert np.array_equal(inl, ref["inlier"]), name
+        q = int(np.flatnonzero(mo >= 0)[m])
+        assert inl[q] == 0 and r["n_inliers"] == 59 and r["accepted"] == 1, name
+        for k in ("loop_info", "PnP_T_old", "PnP_q_old"):
+            a, b = np.asarray(r[k]), np.asarray(ref[k])
+            assert np.all(np.abs(a - b) <= POSE_TOL * np.maximum(1.0, np.abs(b))), (name, k, a, b)
     v.close()
 
 

@@ -473,6 +473,32 @@ def lc_pairs(pairs):
     return arr, keep
 
 
+# the trace of uvs_lc_debug_pair (UVS_LC_TRACE_* of the header)
+LC_LM_ITERS = 20
+LC_TRACE_HEAD_LEN = 32
+LC_TRACE_ITER_LEN = 64
+LC_TRACE_REC_LEN = LC_TRACE_HEAD_LEN + LC_LM_ITERS * LC_TRACE_ITER_LEN
+LC_TRACE_STAGE_OFF = (LC_N_HYPOTHESES + 1) * LC_TRACE_REC_LEN
+LC_TRACE_LEN = LC_TRACE_STAGE_OFF + 1 + 6 * LC_MAX_QUERY
+
+
+def lc_trace(raw):
+    """The raw doubles of uvs_lc_debug_pair -> dict of views: raw; n; X [n,3], uv [n,2], mq [n] (the staged matches); per record r (0 .. 99 the
+    hypotheses, 100 the refinement): samples [101,5], valid [101], iters [101], cost0 [101], pose [101,12] (final R row-major, t), drew [101],
+    start [12] (the refinement's start pose), and it [101,20,64] (the iteration records: start 0:12, lambda 12, acc 13:41, chol_ok 41,
+    d 42:48, cand 48:60, cc 60, cost 61, accepted 62, stop 63)."""
+    raw = np.asarray(raw, np.float64)
+    assert raw.shape == (LC_TRACE_LEN,)
+    rec = raw[:LC_TRACE_STAGE_OFF].reshape(LC_N_HYPOTHESES + 1, LC_TRACE_REC_LEN)
+    st = raw[LC_TRACE_STAGE_OFF:]
+    n = int(st[0])
+    Q = LC_MAX_QUERY
+    return dict(raw=raw, n=n, X=st[1:1 + 3 * Q].reshape(Q, 3)[:n], uv=st[1 + 3 * Q:1 + 5 * Q].reshape(Q, 2)[:n], mq=st[1 + 5 * Q:1 + 6 * Q][:n].astype(np.int64),
+                samples=rec[:, 0:5].astype(np.int64), valid=rec[:, 5].astype(np.int64), iters=rec[:, 6].astype(np.int64), cost0=rec[:, 7],
+                pose=rec[:, 8:20], drew=rec[:, 20].astype(np.int64), start=rec[LC_N_HYPOTHESES, 20:32],
+                it=rec[:, LC_TRACE_HEAD_LEN:].reshape(LC_N_HYPOTHESES + 1, LC_LM_ITERS, LC_TRACE_ITER_LEN))
+
+
 # ---- vanishing points of the line front end (uvs_vp_*, include/uvs_solver.h) ------------------------------------------------
 VP_MAX_FRAMES = 1024
 VP_MAX_LINES = 1024

@@ -20,7 +20,7 @@ EXPORTS = [
     "uvs_abi_version", "uvs_default_options", "uvs_create", "uvs_destroy", "uvs_last_error", "uvs_status_string",
     "uvs_solve_window", "uvs_batch_upload", "uvs_batch_solve", "uvs_batch_download", "uvs_batch_stream", "uvs_evaluate", "uvs_marginalize", "uvs_marginalize_resident", "uvs_marginalize_batch",
     "uvs_reduced_dim", "uvs_pg_create", "uvs_pg_destroy", "uvs_pg_last_error", "uvs_pg_optimize", "uvs_pg_debug_step",
-    "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify",
+    "uvs_lc_create", "uvs_lc_destroy", "uvs_lc_last_error", "uvs_lc_verify", "uvs_lc_debug_pair",
     "uvs_vp_create", "uvs_vp_destroy", "uvs_vp_last_error", "uvs_vp_estimate", "uvs_vp_last_device_ms", "uvs_vp_debug_frame",
     "uvs_kf_create", "uvs_kf_destroy", "uvs_kf_last_error", "uvs_kf_extract", "uvs_kf_last_device_ms", "uvs_kf_debug_frame",
     "uvs_ft_create", "uvs_ft_destroy", "uvs_ft_last_error", "uvs_ft_reset", "uvs_ft_track", "uvs_ft_last_device_ms", "uvs_ft_debug_pyramid", "uvs_ft_debug_point",
@@ -95,6 +95,9 @@ def lib():
         L.uvs_lc_verify.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LcPair), abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_uint8), C.POINTER(abi.LcResult)]
         L.uvs_lc_verify.restype = C.c_int
+        L.uvs_lc_debug_pair.argtypes = [C.c_void_p, C.POINTER(abi.LcPair), abi.c_double_p, abi.c_double_p, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_uint8), C.POINTER(abi.LcResult), abi.c_double_p]
+        L.uvs_lc_debug_pair.restype = C.c_int
         L.uvs_vp_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_vp_create.restype = C.c_int
         L.uvs_vp_destroy.argtypes = [C.c_void_p]; L.uvs_vp_destroy.restype = None
         L.uvs_vp_last_error.argtypes = [C.c_void_p]; L.uvs_vp_last_error.restype = C.c_char_p
@@ -555,6 +558,21 @@ class LoopVerifier:
         if rc != abi.UVS_OK:
             raise RuntimeError(f"uvs_lc_verify: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
         return res, mo, inl
+
+    def debug_pair(self, pair, tic, qic):
+        """Diagnostic (tests only): one pair through the trace instantiation of the kernel.  -> (result dict, match_old [nq], inlier [nq],
+        trace: abi.lc_trace of the raw doubles), the first three bit for bit what verify gives."""
+        arr, keep = abi.lc_pairs([pair])
+        nq = int(arr[0].n_query)
+        tic = np.ascontiguousarray(tic, dtype=np.float64); qic = np.ascontiguousarray(qic, dtype=np.float64)
+        mo = np.zeros(max(nq, 1), np.int32); inl = np.zeros(max(nq, 1), np.uint8)
+        res = (abi.LcResult * 1)()
+        raw = np.zeros(abi.LC_TRACE_LEN, np.float64)
+        rc = lib().uvs_lc_debug_pair(self._h, C.cast(arr, C.POINTER(abi.LcPair)), abi._dp(tic), abi._dp(qic), mo.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.cast(res, C.POINTER(abi.LcResult)), abi._dp(raw))
+        if rc != abi.UVS_OK:
+            raise RuntimeError(f"uvs_lc_debug_pair: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
+        return res[0].as_dict(), mo[:nq].copy(), inl[:nq].copy(), abi.lc_trace(raw)
 
 
 class VanishingPointEstimator:

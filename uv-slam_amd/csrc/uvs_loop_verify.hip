@@ -28,6 +28,10 @@
 //   inlier     z > 0 and dx^2 + dy^2 <= (10 / 460)^2, evaluated without FMA contraction so the count and the mask agree bit for bit.
 //   selection  h >= niters ends the loop; count > max(best, 4) makes h the best and niters = RANSACUpdateNumIters(0.99, (n - count) / n,
 //              5, niters).  The reported inlier set is the chosen hypothesis's mask, not recomputed after the refinement (as OpenCV).
+//
+// uvs_lc_debug_pair (tests only) runs one pair through k_lc_verify<true>, the same body with stores of every intermediate value of the PnP
+// (samples, the normal equations, steps, candidates, costs and decisions of every LM iteration, the staged matches) into a trace buffer;
+// tests/lc_hp.py checks that trace against a 60-digit reference stage by stage.  k_lc_verify<false> is what uvs_lc_verify launches.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cfloat>
@@ -254,11 +258,21 @@ __device__ __forceinline__ void block_sum(double* v, double (*wred)[kRed], doubl
 
 struct HypSlot { double pose[12]; };
 
+// The trace of uvs_lc_debug_pair (layout: include/uvs_solver.h).  Every store goes from registers to global memory at an offset made of the
+// hypothesis, the iteration counter and these constants; the shipped instantiation (kTrace = false) has none of them.
+constexpr int kTrHead = UVS_LC_TRACE_HEAD_LEN, kTrIter = UVS_LC_TRACE_ITER_LEN, kTrRec = UVS_LC_TRACE_REC_LEN;
+constexpr int kTrStage = UVS_LC_TRACE_STAGE_OFF;
+static_assert(kTrRec == kTrHead + kLmIters * kTrIter && kTrStage == (kHyp + 1) * kTrRec, "trace layout");
+static_assert(UVS_LC_TRACE_LEN == kTrStage + 1 + 6 * kMaxQ, "trace layout");
+
+// k_lc_verify<false> is the shipped kernel (`trace` unused); k_lc_verify<true> is uvs_lc_debug_pair's instantiation of the same body (tests
+// only: one pair, `trace` zeroed before the launch).
+template <bool kTrace>
 __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict__ pairs, const double* __restrict__ ex,
                                                       const double* __restrict__ p3d, const unsigned long long* __restrict__ qdesc,
                                                       const double* __restrict__ ouv, const unsigned long long* __restrict__ odesc,
                                                       uvs_lc_result* __restrict__ results, int32_t* __restrict__ match_old,
-                                                      uint8_t* __restrict__ inlier) {
+                                                      uint8_t* __restrict__ inlier, double* __restrict__ trace) {
     __shared__ double sX[kMaxQ * 3];
     __shared__ double sUV[kMaxQ * 2];
     __shared__ short sMq[kMaxQ];                 // query index of match m
@@ -352,6 +366,15 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         res->PnP_q_old[0] = res->PnP_q_old[1] = res->PnP_q_old[2] = 0.0; res->PnP_q_old[3] = 1.0;
     }
     if (tid < kHyp) res->hyp_inliers[tid] = -1;
+    if constexpr (kTrace) {                                     // what the kernel staged: n, sX, sUV, sMq
+        double* ts = trace + kTrStage;
+        if (tid == 0) ts[0] = n;
+        for (int j = tid; j < n; j += kThreads) {
+            for (int a = 0; a < 3; ++a) ts[1 + 3 * j + a] = sX[3 * j + a];
+            for (int a = 0; a < 2; ++a) ts[1 + 3 * kMaxQ + 2 * j + a] = sUV[2 * j + a];
+            ts[1 + 5 * kMaxQ + j] = sMq[j];
+        }
+    }
     if (n <= kMinLoop) return;                                  // gate 1 (uniform across the workgroup)
 
     // ---- the VIO prior: camera pose of origin_vio through the extrinsic (PnPRANSAC :213-219)
@@ -383,6 +406,14 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
             }
         }
         bool valid = got == kModel;
+        double* th = nullptr;                                   // this hypothesis's trace record
+        int nrec = 0;
+        if constexpr (kTrace) {
+            th = trace + h * kTrRec;
+#pragma unroll
+            for (int k = 0; k < kModel; ++k) th[k] = valid ? s[k] : -1;
+            th[20] = valid;
+        }
         double R[9], t[3];
         for (int k = 0; k < 9; ++k) R[k] = R0[k];
         for (int k = 0; k < 3; ++k) t[k] = t0[k];
@@ -391,13 +422,25 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
 #pragma unroll
             for (int k = 0; k < kModel; ++k) cost += point_cost(R, t, sX + 3 * s[k], sUV + 2 * s[k]);
             valid = isfinite(cost);
+            if constexpr (kTrace) th[7] = cost;
             double lam = kLambda0;
             for (int it = 0; it < kLmIters && valid; ++it) {
+                double* ti = nullptr;
+                if constexpr (kTrace) {
+                    ti = th + kTrHead + it * kTrIter; nrec = it + 1;
+                    for (int k = 0; k < 9; ++k) ti[k] = R[k];
+                    for (int k = 0; k < 3; ++k) ti[9 + k] = t[k];
+                    ti[12] = lam;
+                }
                 double acc[kRed];
 #pragma unroll
                 for (int k = 0; k < kRed; ++k) acc[k] = 0.0;
 #pragma unroll
                 for (int k = 0; k < kModel; ++k) accum_point(R, t, sX + 3 * s[k], sUV + 2 * s[k], acc);
+                if constexpr (kTrace) {
+#pragma unroll
+                    for (int k = 0; k < kRed; ++k) ti[13 + k] = acc[k];
+                }
                 double d[6];
                 if (!chol_solve6(acc, lam, d)) { valid = false; break; }
                 double Rc[9], tc[3];
@@ -405,6 +448,13 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
                 double cc = 0.0;
 #pragma unroll
                 for (int k = 0; k < kModel; ++k) cc += point_cost(Rc, tc, sX + 3 * s[k], sUV + 2 * s[k]);
+                if constexpr (kTrace) {
+                    ti[41] = 1.0;
+                    for (int k = 0; k < 6; ++k) ti[42 + k] = d[k];
+                    for (int k = 0; k < 9; ++k) ti[48 + k] = Rc[k];
+                    for (int k = 0; k < 3; ++k) ti[57 + k] = tc[k];
+                    ti[60] = cc; ti[61] = cost; ti[62] = cc < cost;
+                }
                 if (cc < cost) {
                     for (int k = 0; k < 9; ++k) R[k] = Rc[k];
                     for (int k = 0; k < 3; ++k) t[k] = tc[k];
@@ -412,8 +462,19 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
                 } else {
                     lam *= 10.0;
                 }
-                if (step_small(d, t)) break;
+                if constexpr (kTrace) {
+                    const bool stop = step_small(d, t);
+                    ti[63] = stop;
+                    if (stop) break;
+                } else {
+                    if (step_small(d, t)) break;
+                }
             }
+        }
+        if constexpr (kTrace) {
+            th[5] = valid; th[6] = nrec;
+            for (int k = 0; k < 9; ++k) th[8 + k] = R[k];
+            for (int k = 0; k < 3; ++k) th[17 + k] = t[k];
         }
         int c = -1;
         if (valid) {
@@ -441,6 +502,9 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         res->best_hypothesis = bh; res->ransac_iters = h;
         if (bh < 0) res->reason = UVS_LC_RANSAC_FAILED;
         else for (int k = 0; k < 12; ++k) sPose[k] = sU.h.hyp[bh].pose[k];
+        if constexpr (kTrace) {
+            if (bh >= 0) for (int k = 0; k < 12; ++k) trace[kHyp * kTrRec + 20 + k] = sPose[k];       // the refinement's start pose
+        }
     }
     __syncthreads();
     const int bh = sCtl[0];
@@ -463,6 +527,9 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
 
     // ---- refinement LM on the inliers from the hypothesis's pose (fixed-order reductions)
     double cost = 0.0, lam = kLambda0;
+    double* tr = nullptr;                                       // the refinement's trace record (thread 0 writes it)
+    int nrec = 0;
+    if constexpr (kTrace) tr = trace + kHyp * kTrRec;
     for (int it = 0; it < kLmIters; ++it) {
         double acc[kRed];
 #pragma unroll
@@ -476,11 +543,24 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         block_sum(acc, sWred, sSum);
         if (tid == 0) {
             if (it == 0) cost = sSum[27];
+            double* ti = nullptr;
+            if constexpr (kTrace) {
+                ti = tr + kTrHead + it * kTrIter; nrec = it + 1;
+                if (it == 0) tr[7] = cost;
+                for (int k = 0; k < 12; ++k) ti[k] = sPose[k];
+                ti[12] = lam;
+                for (int k = 0; k < kRed; ++k) ti[13 + k] = sSum[k];
+            }
             double d[6];
             if (!chol_solve6(sSum, lam, d)) sCtl[2] = 1;
             else {
                 apply_step(sPose, sPose + 9, d, sCand, sCand + 9);
                 for (int k = 0; k < 6; ++k) sSum[k] = d[k];        // keep the step for the stop test
+                if constexpr (kTrace) {
+                    ti[41] = 1.0;
+                    for (int k = 0; k < 6; ++k) ti[42 + k] = d[k];
+                    for (int k = 0; k < 12; ++k) ti[48 + k] = sCand[k];
+                }
             }
         }
         __syncthreads();
@@ -499,13 +579,24 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         block_sum(pc, sWred, sSum);
         if (tid == 0) {
             const double cc = sSum[27];
+            double* ti = nullptr;
+            if constexpr (kTrace) {
+                ti = tr + kTrHead + it * kTrIter;
+                ti[60] = cc; ti[61] = cost; ti[62] = cc < cost;
+            }
             if (cc < cost) {
                 for (int k = 0; k < 12; ++k) sPose[k] = sCand[k];
                 cost = cc; lam /= 10.0;
             } else {
                 lam *= 10.0;
             }
-            if (step_small(d, sPose + 9)) sCtl[2] = 1;
+            if constexpr (kTrace) {
+                const bool stop = step_small(d, sPose + 9);
+                ti[63] = stop;
+                if (stop) sCtl[2] = 1;
+            } else {
+                if (step_small(d, sPose + 9)) sCtl[2] = 1;
+            }
         }
         __syncthreads();
         if (sCtl[2]) break;
@@ -522,6 +613,10 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         int ni = 0;
         for (int w = 0; w < kWaves; ++w) ni += sScan[0][w];
         res->n_inliers = ni;
+        if constexpr (kTrace) {
+            tr[5] = 1.0; tr[6] = nrec;
+            for (int k = 0; k < 12; ++k) tr[8 + k] = sPose[k];
+        }
         double Rwco[9], PR[9], Two[3], PT[3];
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) Rwco[3 * i + j] = sPose[3 * j + i];             // R_w_c_old = R_pnp^T
@@ -562,6 +657,7 @@ struct uvs_loop_verifier {
     std::string err;
     size_t in_bytes = 0, out_bytes = 0;
     DevBuf<char> d_in, d_out;                   // packed inputs / outputs of one call
+    DevBuf<double> d_trace;                     // uvs_lc_debug_pair's trace, allocated by its first call
     PinnedBuf<char> h_in, h_out;                // pinned staging
     ~uvs_loop_verifier() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -609,10 +705,13 @@ void uvs_lc_destroy(uvs_loop_verifier* lc) {
 
 const char* uvs_lc_last_error(const uvs_loop_verifier* lc) { return lc ? lc->err.c_str() : "null loop verifier"; }
 
-int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, const double tic[3], const double qic_xyzw[4],
-                  int32_t* match_old, uint8_t* inlier, uvs_lc_result* results) {
-    if (!lc) return UVS_ERR_INVALID_ARG;
-    lc->err.clear();
+}  // extern "C"
+
+namespace {
+
+// uvs_lc_verify (trace = nullptr) and uvs_lc_debug_pair (one pair, trace[UVS_LC_TRACE_LEN]): the same checks, packing and copies
+int lc_run(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, const double tic[3], const double qic_xyzw[4],
+           int32_t* match_old, uint8_t* inlier, uvs_lc_result* results, double* trace) {
     if (n_pairs < 1 || !pairs || !tic || !qic_xyzw || !match_old || !inlier || !results) {
         lc->err = "uvs_lc_verify: null pointer or bad count"; return UVS_ERR_INVALID_ARG;
     }
@@ -664,12 +763,25 @@ int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, 
     hipStream_t st = lc->st;
     UVS_HIP(lc->err, hipSetDevice(lc->device));
     UVS_HIP(lc->err, hipMemcpyAsync(lc->d_in, lc->h_in, in_used, hipMemcpyHostToDevice, st));
-    k_lc_verify<<<n_pairs, kThreads, 0, st>>>(reinterpret_cast<const LcPair*>(lc->d_in.get()), reinterpret_cast<const double*>(lc->d_in + o_ex),
-                                             reinterpret_cast<const double*>(lc->d_in + o_p3d), reinterpret_cast<const unsigned long long*>(lc->d_in + o_qd),
-                                             reinterpret_cast<const double*>(lc->d_in + o_uv), reinterpret_cast<const unsigned long long*>(lc->d_in + o_od),
-                                             reinterpret_cast<uvs_lc_result*>(lc->d_out.get()), reinterpret_cast<int32_t*>(lc->d_out + o_mo),
-                                             reinterpret_cast<uint8_t*>(lc->d_out + o_in));
-    UVS_HIP(lc->err, hipGetLastError());
+    if (trace) {
+        const size_t t_bytes = sizeof(double) * UVS_LC_TRACE_LEN;
+        if (const int rc = lc->d_trace.ensure(t_bytes, lc->err)) return rc;
+        UVS_HIP(lc->err, hipMemsetAsync(lc->d_trace, 0, t_bytes, st));
+        k_lc_verify<true><<<1, kThreads, 0, st>>>(reinterpret_cast<const LcPair*>(lc->d_in.get()), reinterpret_cast<const double*>(lc->d_in + o_ex),
+                                                 reinterpret_cast<const double*>(lc->d_in + o_p3d), reinterpret_cast<const unsigned long long*>(lc->d_in + o_qd),
+                                                 reinterpret_cast<const double*>(lc->d_in + o_uv), reinterpret_cast<const unsigned long long*>(lc->d_in + o_od),
+                                                 reinterpret_cast<uvs_lc_result*>(lc->d_out.get()), reinterpret_cast<int32_t*>(lc->d_out + o_mo),
+                                                 reinterpret_cast<uint8_t*>(lc->d_out + o_in), lc->d_trace.get());
+        UVS_HIP(lc->err, hipGetLastError());
+        UVS_HIP(lc->err, hipMemcpyAsync(trace, lc->d_trace, t_bytes, hipMemcpyDeviceToHost, st));
+    } else {
+        k_lc_verify<false><<<n_pairs, kThreads, 0, st>>>(reinterpret_cast<const LcPair*>(lc->d_in.get()), reinterpret_cast<const double*>(lc->d_in + o_ex),
+                                                 reinterpret_cast<const double*>(lc->d_in + o_p3d), reinterpret_cast<const unsigned long long*>(lc->d_in + o_qd),
+                                                 reinterpret_cast<const double*>(lc->d_in + o_uv), reinterpret_cast<const unsigned long long*>(lc->d_in + o_od),
+                                                 reinterpret_cast<uvs_lc_result*>(lc->d_out.get()), reinterpret_cast<int32_t*>(lc->d_out + o_mo),
+                                                 reinterpret_cast<uint8_t*>(lc->d_out + o_in), nullptr);
+        UVS_HIP(lc->err, hipGetLastError());
+    }
     UVS_HIP(lc->err, hipMemcpyAsync(lc->h_out, lc->d_out, out_used, hipMemcpyDeviceToHost, st));
     UVS_HIP(lc->err, hipStreamSynchronize(st));
     std::memcpy(results, lc->h_out, n_pairs * sizeof(uvs_lc_result));
@@ -678,6 +790,25 @@ int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, 
         std::memcpy(inlier, lc->h_out + o_in, tq);
     }
     return UVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uvs_lc_verify(uvs_loop_verifier* lc, int n_pairs, const uvs_lc_pair* pairs, const double tic[3], const double qic_xyzw[4],
+                  int32_t* match_old, uint8_t* inlier, uvs_lc_result* results) {
+    if (!lc) return UVS_ERR_INVALID_ARG;
+    lc->err.clear();
+    return lc_run(lc, n_pairs, pairs, tic, qic_xyzw, match_old, inlier, results, nullptr);
+}
+
+int uvs_lc_debug_pair(uvs_loop_verifier* lc, const uvs_lc_pair* pair, const double tic[3], const double qic_xyzw[4],
+                      int32_t* match_old, uint8_t* inlier, uvs_lc_result* result, double* trace) {
+    if (!lc) return UVS_ERR_INVALID_ARG;
+    lc->err.clear();
+    if (!trace) { lc->err = "uvs_lc_debug_pair: null pointer"; return UVS_ERR_INVALID_ARG; }
+    return lc_run(lc, 1, pair, tic, qic_xyzw, match_old, inlier, result, trace);
 }
 
 }  // extern "C"
