@@ -1,0 +1,30 @@
+"""build()'s unit table is the one list of the library's translation units: it names every *.hip of csrc/, and the variant build keeps no
+list of its own (it once did, and a variant library then lacked the unit the list had not caught up with)."""
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry      # noqa: E402
+
+REBUILT_BY_VARIANT = {"uvs_solver", "uvs_solve512", "uvs_solve_dstep256"}      # the persistent kernel's units: what a variant varies
+
+
+def test_unit_table_is_the_hip_sources():
+    csrc = os.path.join(ROOT, "uv-slam_amd", "csrc")
+    on_disk = sorted(f[:-4] for f in os.listdir(csrc) if f.endswith(".hip"))
+    table = [row[0] for row in entry.UNITS]
+    assert sorted(table) == on_disk
+    assert len(set(table)) == len(table)
+
+
+def test_variant_build_names_no_front_end_unit():
+    with open(os.path.join(ROOT, "tools", "ab", "build_variant.sh")) as f:
+        script = f.read()
+    front_end = [row[0] for row in entry.UNITS if row[0] not in REBUILT_BY_VARIANT]
+    assert len(front_end) >= 7
+    named = [stem for stem in front_end if re.search(rf"\b{stem}\b", script)]
+    assert named == []
+    for stem in REBUILT_BY_VARIANT:      # it does rebuild, and leave out of the link, exactly these
+        assert f"{stem}.hip" in script and f"{stem}.o" in script

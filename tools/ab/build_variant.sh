@@ -1,7 +1,7 @@
 #!/bin/bash
 # builds a variant of the solver library into ab/lib_<name>.so:  tools/ab/build_variant.sh <name> [-D... flags for the translation units of the persistent kernel]
-# (same flags as __graft_entry__.build, which must have run first: the other units are linked from its object files; run A/B with
-# tools/ab/run_ab.sh cur ab/lib_<name>.so on the GPU box)
+# (same flags as __graft_entry__.build, which must have run first: every other unit, i.e. every other *.hip of csrc/, is linked from the
+# object file build() made of it; run A/B with tools/ab/run_ab.sh cur ab/lib_<name>.so on the GPU box)
 set -e
 name=$1; shift
 R=$(cd "$(dirname "$0")/../.." && pwd); C=$R/uv-slam_amd/csrc; T=${TMPDIR:-/tmp}/abv_$name; mkdir -p $R/ab $T
@@ -11,9 +11,11 @@ common="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -mllvm -disable-machine-li
 /opt/rocm/bin/hipcc $common "$@" -c $C/uvs_solve_dstep256.hip -o $T/c.o &
 wait
 others=""
-for u in uvs_pose_graph uvs_loop_verify uvs_vanishing_points uvs_keyframe_features uvs_feature_track uvs_feature_detect; do
-  [ -f $C/$u.o ] || { echo "missing $C/$u.o: run __graft_entry__.build() first"; exit 1; }
-  others="$others $C/$u.o"
+for src in $C/*.hip; do
+  obj=${src%.hip}.o
+  case $obj in $C/uvs_solver.o|$C/uvs_solve512.o|$C/uvs_solve_dstep256.o) continue;; esac      # rebuilt above
+  [ -f $obj ] || { echo "missing $obj: run __graft_entry__.build() first"; exit 1; }
+  others="$others $obj"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $T/a.o $T/b.o $T/c.o $others -o $R/ab/lib_$name.so -ldl -pthread
 echo built ab/lib_$name.so

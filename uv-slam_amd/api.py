@@ -161,21 +161,21 @@ def _device_tensor(ptr, n, device=None):
     return torch.as_tensor(_DevPtr(ptr, n), device=device or "cuda")
 
 
-class Solver:
-    """Owns one `uvs_solver` handle (device buffers + stream) on one GPU."""
+class _Handle:
+    """Owns one native handle of the unit whose C calls start with `_UNIT`: <_UNIT>_create, _destroy and _last_error."""
 
-    def __init__(self, opts=None, device=0, max_batch=1024, max_points=1000, max_point_obs=16000, max_lines=1000, max_line_obs=16000):
-        self.opts = opts or abi.default_options()
+    _UNIT = None
+
+    def _create(self, *args):
+        """<_UNIT>_create(*args, &handle), or a RuntimeError."""
         self._h = C.c_void_p()
-        rc = lib().uvs_create(C.byref(self.opts), device, max_batch, max_points, max_point_obs, max_lines, max_line_obs, C.byref(self._h))
+        rc = getattr(lib(), self._UNIT + "_create")(*args, C.byref(self._h))
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-        self._keep = None
-        self._windows = None
+            raise RuntimeError(f"{self._UNIT}_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
 
     def close(self):
         if self._h:
-            lib().uvs_destroy(self._h)
+            getattr(lib(), self._UNIT + "_destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -184,9 +184,27 @@ class Solver:
         except Exception:
             pass
 
+    def last_error(self):
+        return getattr(lib(), self._UNIT + "_last_error")(self._h).decode()
+
+    def _error(self, what, rc):
+        return RuntimeError(f"{what}: {lib().uvs_status_string(rc).decode()} / {self.last_error()}")
+
+
+class Solver(_Handle):
+    """Owns one `uvs_solver` handle (device buffers + stream) on one GPU."""
+
+    _UNIT = "uvs"
+
+    def __init__(self, opts=None, device=0, max_batch=1024, max_points=1000, max_point_obs=16000, max_lines=1000, max_line_obs=16000):
+        self.opts = opts or abi.default_options()
+        self._create(C.byref(self.opts), device, max_batch, max_points, max_point_obs, max_lines, max_line_obs)
+        self._keep = None
+        self._windows = None
+
     def _check(self, rc, allow=(abi.UVS_OK,)):
         if rc not in allow:
-            raise RuntimeError(f"uvs error {rc}: {lib().uvs_status_string(rc).decode()} / {lib().uvs_last_error(self._h).decode()}")
+            raise RuntimeError(f"uvs error {rc}: {lib().uvs_status_string(rc).decode()} / {self.last_error()}")
         return rc
 
     # ---- single window (host buffers in / out, PCIe inclusive) -------------
@@ -450,27 +468,15 @@ class Solver:
                     cycles=dict(zip(['setup', 'obs', 'lmprep', 'gather', 'assemble', 'chol', 'trsv', 'backsub', 'cost', 'misc', 'chol_diag', 'chol_panel', 'chol_trail', 'asm_imu', 'asm_zero', 'asm_add'], scal[8:24])), sub_timers=dict(cost_phase=dict(zip(['stage_dx', 'prior_residual', 'observations', 'imu'], scal[24:28])), chol_busy_per_wave=scal[28:32].copy()))
 
 
-class PoseGraphSolver:
+class PoseGraphSolver(_Handle):
     """Owns one `uvs_pose_graph` handle: the 4-DoF pose-graph optimizer of loop closure (PoseGraph::optimize4DoF) on one GPU.
 
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
 
+    _UNIT = "uvs_pg"
+
     def __init__(self, device=0, max_keyframes=16384, max_loops=256):
-        self._h = C.c_void_p()
-        rc = lib().uvs_pg_create(device, max_keyframes, max_loops, C.byref(self._h))
-        if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_pg_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-
-    def close(self):
-        if self._h:
-            lib().uvs_pg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_keyframes, max_loops)
 
     def optimize_raw(self, t, q, sequence, constant, loops):
         """-> (return code, yaw_t [n, 4], report) without raising: for the tests of the argument checks."""
@@ -487,7 +493,7 @@ class PoseGraphSolver:
         -> (yaw_t [n, 4] = (yaw deg, tx, ty, tz), abi.PgReport)."""
         rc, out, rep = self.optimize_raw(t, q, sequence, constant, loops)
         if rc not in (abi.UVS_OK, abi.UVS_ERR_NUMERIC):
-            raise RuntimeError(f"uvs_pg_optimize: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
+            raise self._error("uvs_pg_optimize", rc)
         return out, rep
 
     def debug_step_raw(self, t, q, sequence, constant, loops, radius):
@@ -502,32 +508,20 @@ class PoseGraphSolver:
         -> (delta [4 n_free] = the unscaled step in free-keyframe order, dict(factor_fail, capacitance_fail, n_loop_columns, n_free))."""
         rc, delta, scal = self.debug_step_raw(t, q, sequence, constant, loops, radius)
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_pg_debug_step: {lib().uvs_status_string(rc).decode()} / {lib().uvs_pg_last_error(self._h).decode()}")
+            raise self._error("uvs_pg_debug_step", rc)
         return delta, dict(factor_fail=int(scal[0]), capacitance_fail=int(scal[1]), n_loop_columns=int(scal[2]), n_free=int(scal[3]))
 
 
-class LoopVerifier:
+class LoopVerifier(_Handle):
     """Owns one `uvs_loop_verifier` handle: loop verification of loop closure (KeyFrame::findConnection: BRIEF matching + PnP-RANSAC) on
     one GPU, a batch of candidate pairs per call.
 
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
 
+    _UNIT = "uvs_lc"
+
     def __init__(self, device=0, max_pairs=64, max_query=1024, max_old=4096):
-        self._h = C.c_void_p()
-        rc = lib().uvs_lc_create(device, max_pairs, max_query, max_old, C.byref(self._h))
-        if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_lc_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-
-    def close(self):
-        if self._h:
-            lib().uvs_lc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_pairs, max_query, max_old)
 
     def verify_raw(self, pairs, tic, qic, n_pairs=None, null=()):
         """-> (return code, [result dict], [match_old per pair], [inlier per pair]) without raising: for the tests of the argument checks.
@@ -556,7 +550,7 @@ class LoopVerifier:
         extrinsic.  -> (results: list of dicts with the uvs_lc_result fields, match_old: list of int32 [nq], inlier: list of uint8 [nq])."""
         rc, res, mo, inl = self.verify_raw(pairs, tic, qic)
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_lc_verify: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
+            raise self._error("uvs_lc_verify", rc)
         return res, mo, inl
 
     def debug_pair(self, pair, tic, qic):
@@ -571,34 +565,21 @@ class LoopVerifier:
         rc = lib().uvs_lc_debug_pair(self._h, C.cast(arr, C.POINTER(abi.LcPair)), abi._dp(tic), abi._dp(qic), mo.ctypes.data_as(C.POINTER(C.c_int32)),
                                      inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.cast(res, C.POINTER(abi.LcResult)), abi._dp(raw))
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_lc_debug_pair: {lib().uvs_status_string(rc).decode()} / {lib().uvs_lc_last_error(self._h).decode()}")
+            raise self._error("uvs_lc_debug_pair", rc)
         return res[0].as_dict(), mo[:nq].copy(), inl[:nq].copy(), abi.lc_trace(raw)
 
 
-class VanishingPointEstimator:
+class VanishingPointEstimator(_Handle):
     """Owns one `uvs_vp_estimator` handle: the vanishing points of the line front end (getVPHypVia2Lines, getSphereGrids, getBestVpsHyp,
     lines2Vps of the reference's line_feature_tracker.cpp) on one GPU, a batch of frames per call.
 
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
 
+    _UNIT = "uvs_vp"
     ONE_DEGREE = 1.0 / 180.0 * 3.1415926535897932384626433832795       # thAngle of the reference
 
     def __init__(self, device=0, max_frames=64, max_lines=1024):
-        self._h = C.c_void_p()
-        rc = lib().uvs_vp_create(device, max_frames, max_lines, C.byref(self._h))
-        if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_vp_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-
-    def close(self):
-        if self._h:
-            lib().uvs_vp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_frames, max_lines)
 
     def estimate_raw(self, frames, camera, th_angle=None, n_frames=None, null=()):
         """-> (return code, [result dict], [tag per frame], [line_vp per frame]) without raising: for the tests of the argument checks.
@@ -628,7 +609,7 @@ class VanishingPointEstimator:
         0..2 or 3 for "none", line_vp: list of [n, 3] with vps[tag] / vps[tag].z or zero)."""
         rc, res, tag, lvp = self.estimate_raw(frames, camera, th_angle)
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_vp_estimate: {lib().uvs_status_string(rc).decode()} / {lib().uvs_vp_last_error(self._h).decode()}")
+            raise self._error("uvs_vp_estimate", rc)
         return res, tag, lvp
 
     def debug_frame(self, frame, camera, th_angle=None):
@@ -645,40 +626,27 @@ class VanishingPointEstimator:
         rc = lib().uvs_vp_debug_frame(self._h, C.cast(arr, C.POINTER(abi.VpFrame)), C.byref(cam), self.ONE_DEGREE if th_angle is None else float(th_angle),
                                       abi._dp(hyp), ip(cells), abi._dp(scores), abi._dp(raw), abi._dp(smooth), ip(pc), C.byref(res))
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_vp_debug_frame: {lib().uvs_status_string(rc).decode()} / {lib().uvs_vp_last_error(self._h).decode()}")
+            raise self._error("uvs_vp_debug_frame", rc)
         out = res.as_dict()
         out.update(hyp=hyp, cells=cells, scores=scores, raw=raw, smooth=smooth, pair_cell=pc[:n * (n - 1) // 2])
         return out
 
 
-class KeyframeExtractor:
+class KeyframeExtractor(_Handle):
     """Owns one `uvs_kf_extractor` handle: the features of a pose-graph keyframe (computeWindowBRIEFPoint / computeBRIEFPoint of the reference's
     keyframe.cpp: FAST corners, BRIEF descriptors, normalized keypoints) on one GPU, a batch of images per call.
 
     `pattern` is the BRIEF pattern as int32 [4, 256] (x1, y1, x2, y2), e.g. abi.load_brief_pattern("brief_pattern.yml").
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
 
+    _UNIT = "uvs_kf"
+
     def __init__(self, pattern, device=0, max_frames=16, max_width=752, max_height=480, max_keypoints=4096, max_window=1024):
         pat = np.ascontiguousarray(pattern, dtype=np.int32)
         if pat.shape != (4, abi.KF_PATTERN_BITS):
             raise ValueError(f"pattern must be [4, {abi.KF_PATTERN_BITS}] (x1, y1, x2, y2)")
         self.max_keypoints = int(max_keypoints)
-        self._h = C.c_void_p()
-        rc = lib().uvs_kf_create(device, max_frames, max_width, max_height, max_keypoints, max_window,
-                                 *[pat[k].ctypes.data_as(abi.c_i32_p) for k in range(4)], C.byref(self._h))
-        if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_kf_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-
-    def close(self):
-        if self._h:
-            lib().uvs_kf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(device, max_frames, max_width, max_height, max_keypoints, max_window, *[pat[k].ctypes.data_as(abi.c_i32_p) for k in range(4)])
 
     def _outputs(self, n_frames, n_window):
         K = max(n_frames, 1) * self.max_keypoints
@@ -724,7 +692,7 @@ class KeyframeExtractor:
         of an old keyframe, window_desc as qdesc of the current one."""
         rc, out = self.extract_raw(frames, camera)
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_kf_extract: {lib().uvs_status_string(rc).decode()} / {lib().uvs_kf_last_error(self._h).decode()}")
+            raise self._error("uvs_kf_extract", rc)
         return out
 
     def debug_frame(self, frame, camera):
@@ -739,44 +707,26 @@ class KeyframeExtractor:
                                       smap.ctypes.data_as(abi.c_u8_p), o["xy"].ctypes.data_as(abi.c_i32_p), o["score"].ctypes.data_as(abi.c_u8_p),
                                       abi._dp(o["norm"]), o["desc"].ctypes.data_as(abi.c_u64_p), o["wdesc"].ctypes.data_as(abi.c_u64_p), C.byref(res))
         if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_kf_debug_frame: {lib().uvs_status_string(rc).decode()} / {lib().uvs_kf_last_error(self._h).decode()}")
+            raise self._error("uvs_kf_debug_frame", rc)
         out = self._split(o, [res], [nw])[0]
         out.update(blur=blur, score_map=smap)
         return out
 
 
-class FeatureTracker:
+class FeatureTracker(_Handle):
     """Owns one `uvs_ft_tracker` handle: the tracking step of the reference's point front end (FeatureTracker::readImage: pyramidal Lucas-Kanade
     with a 21 x 21 window, inBorder, liftProjective of the tracked points) on one GPU.  Each of the `max_streams` slots keeps the pyramid of its
     last image on the device; a call takes one new image per slot and the points to follow into it.
 
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
 
+    _UNIT = "uvs_ft"
+
     def __init__(self, device=0, max_streams=1, max_width=752, max_height=480, levels=4, max_points=1024):
         self.levels = int(levels)
         self.max_candidates = abi.FT_DEFAULT_CANDIDATES
         self._pyramid_capacity = 2 * int(max_width) * int(max_height)      # level 0 plus the levels above it, which add less than a third
-        self._h = C.c_void_p()
-        rc = lib().uvs_ft_create(device, max_streams, max_width, max_height, levels, max_points, C.byref(self._h))
-        if rc != abi.UVS_OK:
-            raise RuntimeError(f"uvs_ft_create failed: {lib().uvs_status_string(rc).decode()} (rc={rc}); the HIP path is the only path")
-
-    def close(self):
-        if self._h:
-            lib().uvs_ft_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _error(self, what, rc):
-        return RuntimeError(f"{what}: {lib().uvs_status_string(rc).decode()} / {lib().uvs_ft_last_error(self._h).decode()}")
-
-    def last_error(self):
-        return lib().uvs_ft_last_error(self._h).decode()
+        self._create(device, max_streams, max_width, max_height, levels, max_points)
 
     def track_raw(self, items, camera, n_items=None, null=()):
         """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  n_items overrides the count passed; `null`

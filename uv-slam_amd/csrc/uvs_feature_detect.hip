@@ -32,13 +32,10 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_camera_lift.h"
+#include "uvs_frontend_dev.h"
 #include "uvs_ft_handle.h"
-#include "uvs_hip_buf.h"
 
 namespace uvsfd {
-
-using uvsft::align_up;
-using uvsft::pitch_of;
 
 constexpr int kThreads = 256;
 constexpr int kTW = 32, kTH = 8;                              // a tile: a thread per pixel
@@ -65,12 +62,6 @@ struct FdItem {                        // device copy of one item
     long long cand_off;                // candidate keys before this item's (each item has a power of two >= cap of them)
     long long out_off;                 // output entries before this item's: the sum of max_new
 };
-
-__device__ __forceinline__ int reflect101(int i, int n) {     // exact for -n < i < 2 n - 1, clamped beyond
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - 2 - i : i;
-    return min(max(i, 0), n - 1);
-}
 
 // ---- score map, allowed map, the tiles' maxima
 __global__ void __launch_bounds__(kThreads) k_ft_detect_score(const FdItem* __restrict__ items, const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ mask,
@@ -139,7 +130,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_detect_score(const FdItem* __re
         int before = 0, total = 0;
 #pragma unroll
         for (int w = 0; w < kThreads / 64; ++w) { const int v = sCnt[w]; before += w < wave ? v : 0; total += v; }
-        if (hit) { const int k = before + __popcll(hm & ((1ull << lane) - 1ull)); sOcc[2 * k] = ox; sOcc[2 * k + 1] = oy; }
+        if (hit) { const int k = before + uvs_rank_below(hm, lane); sOcc[2 * k] = ox; sOcc[2 * k + 1] = oy; }
         __syncthreads();
         for (int k = 0; k < total; ++k) {
             const int dx = x - sOcc[2 * k], dy = y - sOcc[2 * k + 1];      // |dx| <= R + 31, |dy| <= R + 7
@@ -205,25 +196,8 @@ __global__ void __launch_bounds__(kThreads) k_ft_detect_scan(const FdItem* __res
                                                            uvs_ft_detect_result* __restrict__ results) {
     __shared__ int sPart[kThreads];
     const FdItem F = items[blockIdx.x];
-    const int tid = threadIdx.x;
-    const int chunk = (F.n_seg + kThreads - 1) / kThreads;
-    const int b = min(tid * chunk, F.n_seg), e = min(b + chunk, F.n_seg);
-    const int* cnt = seg_cnt + F.seg_off;
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += cnt[i];
-    sPart[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {            // inclusive scan of the chunk sums
-        const int v = tid >= off ? sPart[tid - off] : 0;
-        __syncthreads();
-        sPart[tid] += v;
-        __syncthreads();
-    }
-    int run = sPart[tid] - sum;
-    int* base = seg_base + F.seg_off;
-    for (int i = b; i < e; ++i) { base[i] = run; run += cnt[i]; }
-    if (tid == kThreads - 1) {
-        const int total = sPart[tid];
+    const int total = uvs_segment_scan<kThreads>(seg_cnt + F.seg_off, seg_base + F.seg_off, F.n_seg, sPart);
+    if (threadIdx.x == kThreads - 1) {
         results[blockIdx.x].status = total > F.cap ? UVS_FT_DETECT_OVERFLOW : UVS_FT_DETECT_OK;
         results[blockIdx.x].n_candidates = total;
     }
@@ -238,7 +212,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_detect_emit(const FdItem* __res
     if (seg >= F.n_seg) return;
     const unsigned long long m = seg_mask[F.seg_off + seg];
     if (!((m >> lane) & 1ull)) return;
-    const int idx = seg_base[F.seg_off + seg] + __popcll(m & ((1ull << lane) - 1ull));
+    const int idx = seg_base[F.seg_off + seg] + uvs_rank_below(m, lane);
     if (idx >= F.cap) return;
     const int y = seg / F.segs_per_row, x = (seg - y * F.segs_per_row) * kSeg + lane;
     cand_score[F.cand_off + idx] = score[F.pix_off + (size_t)y * F.W + x];
@@ -328,7 +302,7 @@ __global__ void __launch_bounds__(kSelThreads) k_ft_detect_select(const FdItem* 
         __syncthreads();
         int before = 0, total = 0;
         for (int w = 0; w < kSelWaves; ++w) { const int v = sWaveCnt[w]; before += w < wave ? v : 0; total += v; }
-        if (ok) { const int k = before + __popcll(m & ((1ull << lane) - 1ull)); sSurvXY[k] = xy; sSurvRank[k] = c; }
+        if (ok) { const int k = before + uvs_rank_below(m, lane); sSurvXY[k] = xy; sSurvRank[k] = c; }
         __syncthreads();
         if (wave == 0) {                                      // the survivors in rank order, 64 at a time
             int T = T0;
@@ -398,9 +372,7 @@ int fd_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_detect
     if (n_items > h->max_streams) { h->err = fn + ": more items than the slots given to uvs_ft_create"; return UVS_ERR_CAPACITY; }
     if (!(quality > 0.0 && quality <= 1.0)) { h->err = fn + ": quality_level must be in (0, 1]"; return UVS_ERR_INVALID_ARG; }
     if (min_distance < 1 || min_distance > UVS_FT_MAX_MIN_DISTANCE) { h->err = fn + ": min_distance must be 1 .. UVS_FT_MAX_MIN_DISTANCE"; return UVS_ERR_INVALID_ARG; }
-    const double cam_v[8] = {camera->fx, camera->fy, camera->cx, camera->cy, camera->k1, camera->k2, camera->p1, camera->p2};
-    for (double c : cam_v) if (!std::isfinite(c)) { h->err = fn + ": the camera must be finite"; return UVS_ERR_INVALID_ARG; }
-    if (!(camera->fx > 0.0) || !(camera->fy > 0.0)) { h->err = fn + ": fx and fy must be positive"; return UVS_ERR_INVALID_ARG; }
+    if (const int rc = check_camera(camera, fn, h->err)) return rc;
     std::vector<char> seen(h->max_streams, 0);
     for (int i = 0; i < n_items; ++i) {
         const uvs_ft_detect_item& it = items[i];
@@ -438,14 +410,13 @@ int fd_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_detect
         top_tx = std::max(top_tx, d.tiles_x); top_ty = std::max(top_ty, d.tiles_y); top_seg = std::max(top_seg, d.n_seg);
     }
     FdLayout L;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
-    L.items = take(n_items * sizeof(FdItem)); L.occ = take(n_occ * 8);
-    L.part = take(n_part * 8); L.seg_mask = take(n_seg * 8); L.seg_cnt = take(n_seg * 4); L.seg_base = take(n_seg * 4);
-    L.score = take(n_pix * 8); L.allowed = take(n_pix); L.cscore = take(n_key * 8); L.cindex = take(n_key * 4);
-    L.res = take(n_items * sizeof(uvs_ft_detect_result));
-    L.xy = take(n_out * 8); L.sc = take(n_out * 8); L.norm = take(n_out * 16);
-    L.end = o;
+    UvsArena A;
+    L.items = A.take(n_items * sizeof(FdItem)); L.occ = A.take(n_occ * 8);
+    L.part = A.take(n_part * 8); L.seg_mask = A.take(n_seg * 8); L.seg_cnt = A.take(n_seg * 4); L.seg_base = A.take(n_seg * 4);
+    L.score = A.take(n_pix * 8); L.allowed = A.take(n_pix); L.cscore = A.take(n_key * 8); L.cindex = A.take(n_key * 4);
+    L.res = A.take(n_items * sizeof(uvs_ft_detect_result));
+    L.xy = A.take(n_out * 8); L.sc = A.take(n_out * 8); L.norm = A.take(n_out * 16);
+    L.end = A.o;
     const size_t in_bytes = L.part, out_bytes = L.end - L.res;      // items | occupied points;  results | new_xy | new_score | new_norm
     UVS_HIP(h->err, hipSetDevice(h->device));
     int rc;

@@ -27,12 +27,10 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_frontend_dev.h"
 #include "uvs_ft_handle.h"
-#include "uvs_hip_buf.h"
 
 namespace uvsfr {
-
-using uvsft::align_up;
 
 constexpr int kThreads = 256;                                 // hypotheses of a round
 constexpr int kHyp = UVS_FT_REJECT_HYPOTHESES;
@@ -48,12 +46,6 @@ struct FrItem {                        // device copy of one item
     long long pts_off;                 // doubles before this item's prev[n][2] | next[n][2]
     long long keep_off;                // tracks before this item's
 };
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ double det3(double u0, double u1, double u2, double v0, double v1, double v2, double w0, double w1, double w2) {
     return (u0 * (v1 * w2 - v2 * w1) - u1 * (v0 * w2 - v2 * w0)) + u2 * (v0 * w1 - v1 * w0);
@@ -126,7 +118,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_reject_run(const FrItem* __rest
             int i0 = -1, i1 = -1, i2 = -1, i3 = -1, i4 = -1, i5 = -1, i6 = -1, cnt = 0;
             if (valid) {
                 for (int a = 0; a < kAttempts && cnt < kModel; ++a) {
-                    const unsigned long long z = mix64(it.seed + 0x9E3779B97F4A7C15ull * (1ull + ((unsigned long long)h << 20) + (unsigned long long)a));
+                    const unsigned long long z = uvs_draw(it.seed, h, a);
                     const int v = (int)(z % (unsigned long long)n);
                     if (v == i0 || v == i1 || v == i2 || v == i3 || v == i4 || v == i5 || v == i6) continue;
                     i0 = cnt == 0 ? v : i0; i1 = cnt == 1 ? v : i1; i2 = cnt == 2 ? v : i2; i3 = cnt == 3 ? v : i3;
@@ -343,17 +335,16 @@ int fr_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_reject
         n_pts += (size_t)it.n_points;
     }
     // the layout of the call: items | points, uploaded;  results | keep, downloaded;  the debug arrays
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
-    const size_t o_items = take(n_items * sizeof(FrItem)), o_pts = take(n_pts * 32);
-    const size_t in_bytes = o;
-    const size_t o_res = take(n_items * sizeof(uvs_ft_reject_result)), o_keep = take(n_pts);
-    const size_t out_bytes = o - o_res;
-    const size_t o_smp = take(dbg_samples ? (size_t)kHyp * kModel * 4 : 0), o_cnt = take(dbg_samples ? (size_t)kHyp * 3 * 4 : 0);
-    const size_t o_mod = take(dbg_samples ? (size_t)kHyp * 27 * 8 : 0);
+    UvsArena A;
+    const size_t o_items = A.take(n_items * sizeof(FrItem)), o_pts = A.take(n_pts * 32);
+    const size_t in_bytes = A.o;
+    const size_t o_res = A.take(n_items * sizeof(uvs_ft_reject_result)), o_keep = A.take(n_pts);
+    const size_t out_bytes = A.o - o_res;
+    const size_t o_smp = A.take(dbg_samples ? (size_t)kHyp * kModel * 4 : 0), o_cnt = A.take(dbg_samples ? (size_t)kHyp * 3 * 4 : 0);
+    const size_t o_mod = A.take(dbg_samples ? (size_t)kHyp * 27 * 8 : 0);
     UVS_HIP(h->err, hipSetDevice(h->device));
     int rc;
-    if ((rc = h->d_rej.ensure(o, h->err)) != UVS_OK || (rc = h->h_rej_in.ensure(in_bytes, h->err, grow_pinned)) != UVS_OK ||
+    if ((rc = h->d_rej.ensure(A.o, h->err)) != UVS_OK || (rc = h->h_rej_in.ensure(in_bytes, h->err, grow_pinned)) != UVS_OK ||
         (rc = h->h_rej_out.ensure(out_bytes, h->err, grow_pinned)) != UVS_OK) return rc;
     FrItem* F = reinterpret_cast<FrItem*>(h->h_rej_in + o_items);
     double* P = reinterpret_cast<double*>(h->h_rej_in + o_pts);

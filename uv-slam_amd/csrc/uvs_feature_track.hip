@@ -6,7 +6,7 @@
 //
 // The handle is csrc/uvs_ft_handle.h, shared with the detection unit (uvs_feature_detect.hip), which reads level 0 of a slot's stored pyramid.
 // A tracker keeps, for each of its slots, two pyramids in one device buffer: the stored one and the one the next image is built into; a call
-// swaps them.  Rows use the keyframe unit's pitch (the width rounded up to 16 bytes).  Kernels of one call, in stream order:
+// swaps them.  Rows use pitch_of (uvs_handle.h: the width rounded up to 16 bytes), as the keyframe unit's.  Kernels of one call, in stream order:
 //   k_ft_pyramid   one launch per level above 0, the item on the last grid axis, a thread per output pixel: five rows of five reads through
 //                  reflect-101 (the 5 x 5 footprints of neighbouring threads overlap in L1 / L2; no LDS stage).
 //   k_ft_track     ONE WAVE PER POINT, four waves per workgroup, the points of all items in one grid.  Per level the wave stages the 24 x 24
@@ -27,8 +27,8 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_camera_lift.h"
+#include "uvs_frontend_dev.h"
 #include "uvs_ft_handle.h"
-#include "uvs_hip_buf.h"
 
 namespace uvsft {
 
@@ -45,14 +45,6 @@ struct FtItem {                        // device copy of one item: the geometry 
     int W[kMaxLevels], H[kMaxLevels], pitch[kMaxLevels];
     long long prev_off[kMaxLevels], new_off[kMaxLevels];      // byte offsets of the levels of the stored / the new pyramid in the pyramid buffer
 };
-
-// reflect-101, exact for -n < i < 2 n - 1 (every index the kernels form, as a level is at least 24 wide and they reach at most 11 beyond it),
-// clamped beyond so that no lane reads outside the image whatever it is given
-__device__ __forceinline__ int reflect101(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - 2 - i : i;
-    return min(max(i, 0), n - 1);
-}
 
 // ---- one level of the pyramid from the level below it
 __global__ void __launch_bounds__(kThreads) k_ft_pyramid(const FtItem* __restrict__ items, uint8_t* __restrict__ pyr, int level) {
@@ -270,9 +262,7 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
         h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG;
     }
     if (n_items > h->max_streams) { h->err = fn + ": more items than the slots given to uvs_ft_create"; return UVS_ERR_CAPACITY; }
-    const double cam_v[8] = {camera->fx, camera->fy, camera->cx, camera->cy, camera->k1, camera->k2, camera->p1, camera->p2};
-    for (double c : cam_v) if (!std::isfinite(c)) { h->err = fn + ": the camera must be finite"; return UVS_ERR_INVALID_ARG; }
-    if (!(camera->fx > 0.0) || !(camera->fy > 0.0)) { h->err = fn + ": fx and fy must be positive"; return UVS_ERR_INVALID_ARG; }
+    if (const int rc = check_camera(camera, fn, h->err)) return rc;
     const int min_size = UVS_FT_MIN_SIZE << (h->levels - 1);
     std::vector<char> seen(h->max_streams, 0);
     size_t total = 0;
@@ -385,7 +375,7 @@ int uvs_ft_create(int device, int max_streams, int max_width, int max_height, in
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVS_ERR_NO_DEVICE;
     uvs_ft_tracker* h = new uvs_ft_tracker();
-    h->device = device; h->max_streams = max_streams; h->max_width = max_width; h->max_height = max_height; h->levels = levels; h->max_points = max_points;
+    h->max_streams = max_streams; h->max_width = max_width; h->max_height = max_height; h->levels = levels; h->max_points = max_points;
     h->slots.resize(max_streams);
     int W[kMaxLevels], H[kMaxLevels], P[kMaxLevels]; long long off[kMaxLevels];
     h->pyr_bytes = pyramid_layout(max_width, max_height, levels, W, H, P, off);      // every level of a smaller image is no larger than the level here
@@ -393,12 +383,9 @@ int uvs_ft_create(int device, int max_streams, int max_width, int max_height, in
     const size_t S = max_streams, N = S * max_points;
     h->in_meta = align_up(align_up(align_up(S * sizeof(FtItem), 16) + N * 4, 16) + N * 16, 256);
     const size_t out_bytes = out_layout(N).total;
-    hipError_t e; int rc = UVS_OK;
-    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(h->err, e, "hipSetDevice");
-    else if ((e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(h->err, e, "hipStreamCreate");
-    else if ((e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess) rc = hip_fail(h->err, e, "hipEventCreate");
-    else if ((rc = h->d_pyr.ensure(2 * S * h->pyr_bytes, h->err)) == UVS_OK && (rc = h->d_in.ensure(h->in_meta, h->err)) == UVS_OK &&
-             (rc = h->d_out.ensure(out_bytes, h->err)) == UVS_OK && (rc = h->h_in.ensure(h->in_meta + S * h->img_slot, h->err)) == UVS_OK) {
+    int rc = h->open(device);
+    if (rc == UVS_OK && (rc = h->d_pyr.ensure(2 * S * h->pyr_bytes, h->err)) == UVS_OK && (rc = h->d_in.ensure(h->in_meta, h->err)) == UVS_OK &&
+        (rc = h->d_out.ensure(out_bytes, h->err)) == UVS_OK && (rc = h->h_in.ensure(h->in_meta + S * h->img_slot, h->err)) == UVS_OK) {
         rc = h->h_out.ensure(out_bytes, h->err);
     }
     if (rc != UVS_OK) { uvs_ft_destroy(h); return rc; }
@@ -406,12 +393,7 @@ int uvs_ft_create(int device, int max_streams, int max_width, int max_height, in
     return UVS_OK;
 }
 
-void uvs_ft_destroy(uvs_ft_tracker* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    delete h;
-}
+void uvs_ft_destroy(uvs_ft_tracker* h) { if (h) { h->close(); delete h; } }
 
 const char* uvs_ft_last_error(const uvs_ft_tracker* h) { return h ? h->err.c_str() : "null feature tracker"; }
 

@@ -1,6 +1,7 @@
 // uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the three units of the point front end: csrc/uvs_feature_track.hip (creates
 // and destroys it, builds the pyramids, tracks), csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid) and
-// csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot).  Host only.
+// csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot).  Device, stream, events and error
+// text are the base's (uvs_handle.h, which also has align_up, pitch_of, the arena and the camera check the three units use).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -9,17 +10,14 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
-#include "uvs_hip_buf.h"
+#include "uvs_handle.h"
 
-struct uvs_ft_tracker {
+struct uvs_ft_tracker : UvsHandle {
     // cur: which of the slot's two pyramids is the stored one; has_mask: the slot's part of d_mask holds a mask (uvs_ft_set_mask)
     struct Slot { int W = 0, H = 0, cur = 0; bool holds = false, has_mask = false; };
-    int device = 0, max_streams = 0, max_width = 0, max_height = 0, levels = 0, max_points = 0;
+    int max_streams = 0, max_width = 0, max_height = 0, levels = 0, max_points = 0;
     int max_candidates = UVS_FT_DEFAULT_CANDIDATES;      // uvs_ft_set_max_candidates
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the device work of one call (uvs_ft_last_device_ms, uvs_ft_last_detect_device_ms)
-    float device_ms = 0.f, detect_ms = 0.f;
-    std::string err;
+    float device_ms = 0.f, detect_ms = 0.f;     // uvs_ft_last_device_ms, uvs_ft_last_detect_device_ms
     std::vector<Slot> slots;
     size_t pyr_bytes = 0;                       // bytes of one pyramid at the largest size, every level rounded up to 256
     size_t img_slot = 0;                        // bytes of one level-0 image at the largest size, rounded up to 256
@@ -35,17 +33,9 @@ struct uvs_ft_tracker {
     DevBuf<char> d_rej;                         // one call's item table and points, results and keep masks, and the debug arrays
     PinnedBuf<char> h_rej_in, h_rej_out;        // pinned staging of uvs_ft_reject
     float reject_ms = 0.f;                      // uvs_ft_last_reject_device_ms
-    ~uvs_ft_tracker() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 namespace uvsft {
-
-inline size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
-inline int pitch_of(int width) { return (width + 15) & ~15; }
 
 // sizes and byte offsets of the levels of one pyramid of a width x height image -> its bytes
 inline size_t pyramid_layout(int width, int height, int levels, int* W, int* H, int* P, long long* off) {

@@ -34,7 +34,8 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_camera_lift.h"
-#include "uvs_hip_buf.h"
+#include "uvs_frontend_dev.h"
+#include "uvs_handle.h"
 
 namespace uvskf {
 
@@ -57,14 +58,6 @@ struct KfFrame {                   // device copy of one uvs_kf_frame
     long long img_off;             // byte offset of the image / blurred image / score map in their buffers
 };
 using KfCam = UvsLiftCam;         // uvs_camera_lift.h: shared with the feature tracker
-
-// cv::BORDER_REFLECT_101; exact for -n < i < 2 n - 1 (every index an output needs, as n >= 9 and the halo is 4), clamped beyond so that the
-// lanes of a tile that hangs over the image still read inside it
-__device__ __forceinline__ int reflect101(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - 2 - i : i;
-    return min(max(i, 0), n - 1);
-}
 
 __device__ __forceinline__ unsigned byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 255u; }
 
@@ -219,25 +212,8 @@ __global__ void __launch_bounds__(kThreads) k_kf_select_scan(const KfFrame* __re
                                                            uvs_kf_result* __restrict__ results, int max_keypoints) {
     __shared__ int sPart[kThreads];
     const KfFrame F = frames[blockIdx.x];
-    const int tid = threadIdx.x;
-    const int chunk = (F.n_seg + kThreads - 1) / kThreads;
-    const int b = min(tid * chunk, F.n_seg), e = min(b + chunk, F.n_seg);
-    const int* cnt = seg_cnt + F.seg_off;
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += cnt[i];
-    sPart[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {            // inclusive scan of the chunk sums
-        const int v = tid >= off ? sPart[tid - off] : 0;
-        __syncthreads();
-        sPart[tid] += v;
-        __syncthreads();
-    }
-    int run = sPart[tid] - sum;
-    int* base = seg_base + F.seg_off;
-    for (int i = b; i < e; ++i) { base[i] = run; run += cnt[i]; }
-    if (tid == kThreads - 1) {
-        const int total = sPart[tid];
+    const int total = uvs_segment_scan<kThreads>(seg_cnt + F.seg_off, seg_base + F.seg_off, F.n_seg, sPart);
+    if (threadIdx.x == kThreads - 1) {
         uvs_kf_result* res = results + blockIdx.x;            // n_corners_before_nms: k_kf_score's
         res->status = total > max_keypoints ? UVS_KF_OVERFLOW : UVS_KF_OK;
         res->n_keypoints = total;
@@ -254,7 +230,7 @@ __global__ void __launch_bounds__(kThreads) k_kf_select_emit(const KfFrame* __re
     if (seg >= F.n_seg) return;
     const unsigned long long m = seg_mask[F.seg_off + seg];
     if (!((m >> lane) & 1ull)) return;
-    const int idx = seg_base[F.seg_off + seg] + __popcll(m & ((1ull << lane) - 1ull));
+    const int idx = seg_base[F.seg_off + seg] + uvs_rank_below(m, lane);
     if (idx >= max_keypoints) return;
     const int y = seg / F.segs_per_row, x = (seg % F.segs_per_row) * kSeg + lane;
     const size_t o = (size_t)blockIdx.y * max_keypoints + idx;
@@ -310,12 +286,9 @@ __global__ void __launch_bounds__(kThreads) k_kf_describe(const KfFrame* __restr
 
 using namespace uvskf;
 
-struct uvs_kf_extractor {
-    int device = 0, max_frames = 0, max_width = 0, max_height = 0, max_keypoints = 0, max_window = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the device work of one call (uvs_kf_last_device_ms)
-    float device_ms = 0.f;
-    std::string err;
+struct uvs_kf_extractor : UvsHandle {
+    int max_frames = 0, max_width = 0, max_height = 0, max_keypoints = 0, max_window = 0;
+    float device_ms = 0.f;                      // uvs_kf_last_device_ms
     size_t slot = 0;                            // bytes of one image at the largest pitch and height, rounded up to 256
     size_t in_meta = 0;                         // bytes of (frames | window points) at capacity, rounded up to 256: the images follow
     DevBuf<char> d_in, d_out;                   // packed inputs (frames | window points | images) / outputs (results | norm | desc | window desc | xy | score) of one call
@@ -324,17 +297,10 @@ struct uvs_kf_extractor {
     DevBuf<unsigned long long> d_seg_mask;      // keep mask of every row segment
     DevBuf<int> d_seg_cnt, d_seg_base;          // its count, its exclusive prefix
     DevBuf<int32_t> d_pattern;                  // x1 | y1 | x2 | y2
-    ~uvs_kf_extractor() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 namespace {
 
-inline size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
-inline int pitch_of(int width) { return (width + 15) & ~15; }
 inline int segs_of(int width) { return (width + kSeg - 1) / kSeg; }
 
 struct KfOutLayout { size_t norm, desc, wdesc, xy, score, total; };
@@ -358,9 +324,7 @@ int kf_run(uvs_kf_extractor* h, const char* who_, int n_frames, const uvs_kf_fra
         h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG;
     }
     if (n_frames > h->max_frames) { h->err = fn + ": more frames than the capacity given to uvs_kf_create"; return UVS_ERR_CAPACITY; }
-    const double cam_v[8] = {camera->fx, camera->fy, camera->cx, camera->cy, camera->k1, camera->k2, camera->p1, camera->p2};
-    for (double c : cam_v) if (!std::isfinite(c)) { h->err = fn + ": the camera must be finite"; return UVS_ERR_INVALID_ARG; }
-    if (!(camera->fx > 0.0) || !(camera->fy > 0.0)) { h->err = fn + ": fx and fy must be positive"; return UVS_ERR_INVALID_ARG; }
+    if (const int rc = check_camera(camera, fn, h->err)) return rc;
     size_t tw = 0, img_bytes = 0, n_seg = 0;
     int max_w = 0, max_h = 0, max_nw = 0;
     for (int f = 0; f < n_frames; ++f) {
@@ -461,35 +425,28 @@ int uvs_kf_create(int device, int max_frames, int max_width, int max_height, int
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVS_ERR_NO_DEVICE;
     uvs_kf_extractor* h = new uvs_kf_extractor();
-    h->device = device; h->max_frames = max_frames; h->max_width = max_width; h->max_height = max_height;
+    h->max_frames = max_frames; h->max_width = max_width; h->max_height = max_height;
     h->max_keypoints = max_keypoints; h->max_window = max_window;
     const size_t B = max_frames, Wt = B * max_window;
     h->slot = align_up((size_t)pitch_of(max_width) * max_height, 256);
     h->in_meta = align_up(align_up(B * sizeof(KfFrame), 16) + Wt * 8, 256);
     const size_t in_bytes = h->in_meta + B * h->slot, out_bytes = out_layout(B, max_keypoints, Wt).total;
     const size_t segs = B * (size_t)max_height * segs_of(max_width);
-    hipError_t e; int rc = UVS_OK;
-    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(h->err, e, "hipSetDevice");
-    else if ((e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(h->err, e, "hipStreamCreate");
-    else if ((e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess) rc = hip_fail(h->err, e, "hipEventCreate");
-    else if ((rc = h->d_in.ensure(in_bytes, h->err)) == UVS_OK && (rc = h->d_out.ensure(out_bytes, h->err)) == UVS_OK &&
-             (rc = h->h_in.ensure(in_bytes, h->err)) == UVS_OK && (rc = h->h_out.ensure(out_bytes, h->err)) == UVS_OK &&
-             (rc = h->d_blur.ensure(B * h->slot, h->err)) == UVS_OK && (rc = h->d_score.ensure(B * h->slot, h->err)) == UVS_OK &&
-             (rc = h->d_seg_mask.ensure(segs * 8, h->err)) == UVS_OK && (rc = h->d_seg_cnt.ensure(segs * 4, h->err)) == UVS_OK &&
-             (rc = h->d_seg_base.ensure(segs * 4, h->err)) == UVS_OK && (rc = h->d_pattern.ensure(pattern.size() * 4, h->err)) == UVS_OK) {
-        if ((e = hipMemcpy(h->d_pattern, pattern.data(), pattern.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(h->err, e, "hipMemcpy");
+    int rc = h->open(device);
+    if (rc == UVS_OK && (rc = h->d_in.ensure(in_bytes, h->err)) == UVS_OK && (rc = h->d_out.ensure(out_bytes, h->err)) == UVS_OK &&
+        (rc = h->h_in.ensure(in_bytes, h->err)) == UVS_OK && (rc = h->h_out.ensure(out_bytes, h->err)) == UVS_OK &&
+        (rc = h->d_blur.ensure(B * h->slot, h->err)) == UVS_OK && (rc = h->d_score.ensure(B * h->slot, h->err)) == UVS_OK &&
+        (rc = h->d_seg_mask.ensure(segs * 8, h->err)) == UVS_OK && (rc = h->d_seg_cnt.ensure(segs * 4, h->err)) == UVS_OK &&
+        (rc = h->d_seg_base.ensure(segs * 4, h->err)) == UVS_OK && (rc = h->d_pattern.ensure(pattern.size() * 4, h->err)) == UVS_OK) {
+        const hipError_t e = hipMemcpy(h->d_pattern, pattern.data(), pattern.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = hip_fail(h->err, e, "hipMemcpy");
     }
     if (rc != UVS_OK) { uvs_kf_destroy(h); return rc; }
     *out = h;
     return UVS_OK;
 }
 
-void uvs_kf_destroy(uvs_kf_extractor* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    delete h;
-}
+void uvs_kf_destroy(uvs_kf_extractor* h) { if (h) { h->close(); delete h; } }
 
 const char* uvs_kf_last_error(const uvs_kf_extractor* h) { return h ? h->err.c_str() : "null keyframe-feature extractor"; }
 

@@ -42,7 +42,8 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
-#include "uvs_hip_buf.h"
+#include "uvs_frontend_dev.h"
+#include "uvs_handle.h"
 
 namespace uvslc {
 
@@ -68,12 +69,6 @@ struct LcPair {                             // device copy of one uvs_lc_pair
     unsigned long long seed;
     double vio_t[3], vio_q[4];
 };
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // Eigen's Quaternion::toRotationMatrix, q = (x, y, z, w), row-major
 __device__ inline void quat_to_R(const double* q, double* R) {
@@ -394,7 +389,7 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
         const int h = tid;
         int s[kModel], got = 0;
         for (int a = 0; a < kMaxAttempts && got < kModel; ++a) {
-            const unsigned long long z = mix64(P.seed + 0x9E3779B97F4A7C15ull * (1ull + ((unsigned long long)h << 20) + (unsigned long long)a));
+            const unsigned long long z = uvs_draw(P.seed, h, a);
             const int v = (int)(z % (unsigned long long)n);
             bool dup = false;
 #pragma unroll
@@ -651,15 +646,12 @@ __global__ void __launch_bounds__(kThreads) k_lc_verify(const LcPair* __restrict
 
 using namespace uvslc;
 
-struct uvs_loop_verifier {
-    int device = 0, max_pairs = 0, max_query = 0, max_old = 0;
-    hipStream_t st = nullptr;
-    std::string err;
+struct uvs_loop_verifier : UvsHandle {       // no call is timed: opened without events
+    int max_pairs = 0, max_query = 0, max_old = 0;
     size_t in_bytes = 0, out_bytes = 0;
     DevBuf<char> d_in, d_out;                   // packed inputs / outputs of one call
     DevBuf<double> d_trace;                     // uvs_lc_debug_pair's trace, allocated by its first call
     PinnedBuf<char> h_in, h_out;                // pinned staging
-    ~uvs_loop_verifier() { if (st) (void)hipStreamDestroy(st); }
 };
 
 namespace {
@@ -682,26 +674,19 @@ int uvs_lc_create(int device, int max_pairs, int max_query, int max_old, uvs_loo
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVS_ERR_NO_DEVICE;
     uvs_loop_verifier* lc = new uvs_loop_verifier();
-    lc->device = device; lc->max_pairs = max_pairs; lc->max_query = max_query; lc->max_old = max_old;
+    lc->max_pairs = max_pairs; lc->max_query = max_query; lc->max_old = max_old;
     const size_t B = max_pairs, Q = B * max_query, O = B * max_old;
     lc->in_bytes = align8(B * sizeof(LcPair)) + 12 * 8 + Q * (3 * 8 + 4 * 8) + O * (2 * 8 + 4 * 8);
     lc->out_bytes = align8(B * sizeof(uvs_lc_result)) + align8(Q * 4) + align8(Q);
-    hipError_t e; int rc = UVS_OK;
-    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(lc->err, e, "hipSetDevice");
-    else if ((e = hipStreamCreateWithFlags(&lc->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(lc->err, e, "hipStreamCreate");
-    else if ((rc = lc->d_in.ensure(lc->in_bytes, lc->err)) == UVS_OK && (rc = lc->d_out.ensure(lc->out_bytes, lc->err)) == UVS_OK &&
-             (rc = lc->h_in.ensure(lc->in_bytes, lc->err)) == UVS_OK) rc = lc->h_out.ensure(lc->out_bytes, lc->err);
+    int rc = lc->open(device, false);
+    if (rc == UVS_OK && (rc = lc->d_in.ensure(lc->in_bytes, lc->err)) == UVS_OK && (rc = lc->d_out.ensure(lc->out_bytes, lc->err)) == UVS_OK &&
+        (rc = lc->h_in.ensure(lc->in_bytes, lc->err)) == UVS_OK) rc = lc->h_out.ensure(lc->out_bytes, lc->err);
     if (rc != UVS_OK) { uvs_lc_destroy(lc); return rc; }
     *out = lc;
     return UVS_OK;
 }
 
-void uvs_lc_destroy(uvs_loop_verifier* lc) {
-    if (!lc) return;
-    (void)hipSetDevice(lc->device);
-    if (lc->st) (void)hipStreamSynchronize(lc->st);
-    delete lc;
-}
+void uvs_lc_destroy(uvs_loop_verifier* lc) { if (lc) { lc->close(); delete lc; } }
 
 const char* uvs_lc_last_error(const uvs_loop_verifier* lc) { return lc ? lc->err.c_str() : "null loop verifier"; }
 

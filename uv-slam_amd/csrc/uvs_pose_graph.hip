@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
-#include "uvs_hip_buf.h"
+#include "uvs_handle.h"
 
 namespace uvspg {
 
@@ -699,10 +699,8 @@ __global__ void __launch_bounds__(1024) k_pg_reduce(RedArgs ra, double* __restri
 
 using namespace uvspg;
 
-struct uvs_pose_graph {
-    int device = 0, max_n = 0, max_l = 0, max_cols = 0;
-    hipStream_t st = nullptr;
-    std::string err;
+struct uvs_pose_graph : UvsHandle {          // no call is timed: opened without events
+    int max_n = 0, max_l = 0, max_cols = 0;
     // inputs
     DevBuf<double> t, q; DevBuf<int> seq, fidx, kf_of_free, ucol, wstart;
     DevBuf<uvs_pg_loop> loops;
@@ -715,7 +713,6 @@ struct uvs_pose_graph {
     DevBuf<double> res, wz;                     // refinement pass: residual, W_U^T L^-1 r
     DevBuf<double> scal; DevBuf<int> fail;      // device scalars
     PinnedBuf<double> h_scal;                   // pinned: 8 doubles + fail flags
-    ~uvs_pose_graph() { if (st) (void)hipStreamDestroy(st); }
 };
 
 namespace {
@@ -845,11 +842,9 @@ int uvs_pg_create(int device, int max_keyframes, int max_loops, uvs_pose_graph**
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVS_ERR_NO_DEVICE;
     uvs_pose_graph* pg = new uvs_pose_graph();
-    pg->device = device; pg->max_n = max_keyframes; pg->max_l = max_loops;
+    pg->max_n = max_keyframes; pg->max_l = max_loops;
     pg->max_cols = ((4 * max_loops + 1 + kTile - 1) / kTile) * kTile;
-    hipError_t e; int rc = UVS_OK;
-    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(pg->err, e, "hipSetDevice");
-    else if ((e = hipStreamCreateWithFlags(&pg->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(pg->err, e, "hipStreamCreate");
+    int rc = pg->open(device, false);
     const size_t N = max_keyframes, Lm = std::max(1, max_loops), ES = 4 * N + Lm, C = pg->max_cols, M = 4 * N;
     const auto al = [&](auto& buf, size_t bytes) { if (rc == UVS_OK) rc = buf.ensure(bytes, pg->err); };
     al(pg->t, N * 3 * 8); al(pg->q, N * 4 * 8); al(pg->seq, N * 4); al(pg->fidx, N * 4);
@@ -868,12 +863,7 @@ int uvs_pg_create(int device, int max_keyframes, int max_loops, uvs_pose_graph**
     return UVS_OK;
 }
 
-void uvs_pg_destroy(uvs_pose_graph* pg) {
-    if (!pg) return;
-    (void)hipSetDevice(pg->device);
-    if (pg->st) (void)hipStreamSynchronize(pg->st);
-    delete pg;
-}
+void uvs_pg_destroy(uvs_pose_graph* pg) { if (pg) { pg->close(); delete pg; } }
 
 const char* uvs_pg_last_error(const uvs_pose_graph* pg) { return pg ? pg->err.c_str() : "null pose graph"; }
 

@@ -9,7 +9,8 @@
 //                  of the frame's voting grid, and the UVS_VP_N_SAMPLES line pairs of the hypotheses:
 //                  UVS_VP_N_SAMPLES = int(log(1 - 0.9999) / log(1 - (1/3) * 0.5^2)) = 105  (:1981-1985).
 //                  Sample s, attempt t draws a = z(2t) % n, b = z(2t + 1) % n with z(c) = mix64(seed + 0x9E3779B97F4A7C15 * (1 + (s << 20) + c))
-//                  (the counter-based generator of uvs_loop_verify.hip); the attempt is redrawn when a == b or (para_a x para_b).z == 0 (:2016-2029).
+//                  (uvs_draw of uvs_frontend_dev.h, the generator of uvs_loop_verify.hip); the attempt is redrawn when a == b or
+//                  (para_a x para_b).z == 0 (:2016-2029).
 //                  The reference redraws forever; here a sample that finds no pair in kMaxAttempts attempts makes the frame UVS_VP_NO_HYPOTHESIS.
 //   k_vp_vote      thread per line pair i < j (:2104-2148).  The weight sqrt(len_i len_j) (sin(2 dev) + 0.2) goes into the pair's cell of the
 //                  90 x 360 grid.  Deterministic sum: the grid lives in global memory (259 200 B of doubles per frame do not fit the 160 KiB of
@@ -38,7 +39,8 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
-#include "uvs_hip_buf.h"
+#include "uvs_frontend_dev.h"
+#include "uvs_handle.h"
 
 namespace uvsvp {
 
@@ -69,12 +71,6 @@ struct VpCtl {                     // per frame, written by k_vp_prepare
 };
 struct VpBlockBest { double score; int idx, pad; double hyp[9]; };
 struct VpCam { double fx, fy, cx, cy, th; };
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // the cell rule of the header comment; q >= 0 for every caller, anything else (a NaN) goes to cell 0 so that no index leaves the grid
 __device__ __forceinline__ int snap_cell(double angle, int n) {
@@ -128,9 +124,8 @@ __global__ void __launch_bounds__(kPrepThreads) k_vp_prepare(const VpFrame* __re
         const int s = tid;
         int a = -1, b = -1;
         for (int t = 0; t < kMaxAttempts; ++t) {
-            const unsigned long long c = 1ull + ((unsigned long long)s << 20) + 2ull * (unsigned long long)t;
-            const int ia = (int)(mix64(F.seed + 0x9E3779B97F4A7C15ull * c) % (unsigned long long)n);
-            const int ib = (int)(mix64(F.seed + 0x9E3779B97F4A7C15ull * (c + 1ull)) % (unsigned long long)n);
+            const int ia = (int)(uvs_draw(F.seed, s, 2 * t) % (unsigned long long)n);
+            const int ib = (int)(uvs_draw(F.seed, s, 2 * t + 1) % (unsigned long long)n);
             if (ia == ib) continue;
             const double z = sPara[3 * ia] * sPara[3 * ib + 1] - sPara[3 * ia + 1] * sPara[3 * ib];
             if (z == 0) continue;
@@ -363,12 +358,9 @@ __global__ void __launch_bounds__(kSelThreads) k_vp_select(const VpFrame* __rest
 
 using namespace uvsvp;
 
-struct uvs_vp_estimator {
-    int device = 0, max_frames = 0, max_lines = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the device work of one call (uvs_vp_last_device_ms)
-    float device_ms = 0.f;
-    std::string err;
+struct uvs_vp_estimator : UvsHandle {
+    int max_frames = 0, max_lines = 0;
+    float device_ms = 0.f;                      // uvs_vp_last_device_ms
     size_t in_bytes = 0, out_bytes = 0;
     DevBuf<char> d_in, d_out;                   // packed inputs (frames | segments) / outputs (results | tags | line_vp) of one call
     PinnedBuf<char> h_in, h_out;                // pinned staging
@@ -378,11 +370,6 @@ struct uvs_vp_estimator {
     DevBuf<unsigned long long> d_limbs;         // voting grids, two integers per cell
     DevBuf<VpBlockBest> d_best;                 // [frames][105]
     DevBuf<char> d_dbg;                         // uvs_vp_debug_frame only (allocated by its first call)
-    ~uvs_vp_estimator() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 namespace {
@@ -468,30 +455,22 @@ int uvs_vp_create(int device, int max_frames, int max_lines, uvs_vp_estimator** 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return UVS_ERR_NO_DEVICE;
     uvs_vp_estimator* h = new uvs_vp_estimator();
-    h->device = device; h->max_frames = max_frames; h->max_lines = max_lines;
+    h->max_frames = max_frames; h->max_lines = max_lines;
     const size_t B = max_frames, Lt = B * max_lines;
     h->in_bytes = align8(B * sizeof(VpFrame)) + Lt * 32;
     h->out_bytes = align8(B * sizeof(uvs_vp_result)) + align8(Lt * 4) + Lt * 24;
-    hipError_t e; int rc = UVS_OK;
-    if ((e = hipSetDevice(device)) != hipSuccess) rc = hip_fail(h->err, e, "hipSetDevice");
-    else if ((e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)) != hipSuccess) rc = hip_fail(h->err, e, "hipStreamCreate");
-    else if ((e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess) rc = hip_fail(h->err, e, "hipEventCreate");
-    else if ((rc = h->d_in.ensure(h->in_bytes, h->err)) == UVS_OK && (rc = h->d_out.ensure(h->out_bytes, h->err)) == UVS_OK &&
-             (rc = h->h_in.ensure(h->in_bytes, h->err)) == UVS_OK && (rc = h->h_out.ensure(h->out_bytes, h->err)) == UVS_OK &&
-             (rc = h->d_lp.ensure(Lt * 40, h->err)) == UVS_OK && (rc = h->d_smooth.ensure(B * kCells * 8, h->err)) == UVS_OK &&
-             (rc = h->d_ctl.ensure(B * sizeof(VpCtl), h->err)) == UVS_OK && (rc = h->d_samples.ensure(B * kSamples * 8, h->err)) == UVS_OK &&
-             (rc = h->d_limbs.ensure(B * kCells * 16, h->err)) == UVS_OK) rc = h->d_best.ensure(B * kSamples * sizeof(VpBlockBest), h->err);
+    int rc = h->open(device);
+    if (rc == UVS_OK && (rc = h->d_in.ensure(h->in_bytes, h->err)) == UVS_OK && (rc = h->d_out.ensure(h->out_bytes, h->err)) == UVS_OK &&
+        (rc = h->h_in.ensure(h->in_bytes, h->err)) == UVS_OK && (rc = h->h_out.ensure(h->out_bytes, h->err)) == UVS_OK &&
+        (rc = h->d_lp.ensure(Lt * 40, h->err)) == UVS_OK && (rc = h->d_smooth.ensure(B * kCells * 8, h->err)) == UVS_OK &&
+        (rc = h->d_ctl.ensure(B * sizeof(VpCtl), h->err)) == UVS_OK && (rc = h->d_samples.ensure(B * kSamples * 8, h->err)) == UVS_OK &&
+        (rc = h->d_limbs.ensure(B * kCells * 16, h->err)) == UVS_OK) rc = h->d_best.ensure(B * kSamples * sizeof(VpBlockBest), h->err);
     if (rc != UVS_OK) { uvs_vp_destroy(h); return rc; }
     *out = h;
     return UVS_OK;
 }
 
-void uvs_vp_destroy(uvs_vp_estimator* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    delete h;
-}
+void uvs_vp_destroy(uvs_vp_estimator* h) { if (h) { h->close(); delete h; } }
 
 const char* uvs_vp_last_error(const uvs_vp_estimator* h) { return h ? h->err.c_str() : "null vanishing-point estimator"; }
 
