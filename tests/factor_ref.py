@@ -38,6 +38,13 @@ is written down here, with the exceptions that are not derivatives in the refere
                point  J = reduce * jaco keeps POINT_G x 2^-53 of the absolute sum of the two terms of a row (far points, no parallax);
                IMU    the analytic blocks are derivatives for unit frame quaternions only: IMU_Q (| |Qi|^2 - 1 | + | |Qj|^2 - 1 |) |W| |J_raw|.
 The metric and the bound of DESIGN.md section 4 (`check`) are computed from these alone: neither the oracle nor the device enters a number.
+
+Residual-only mode (`jacobians=False` of tasks_of / block_task / evaluate; what tests/lm_accept_ref.py evaluates candidate costs with): no central differences; r, cost,
+the level of r and the residual models are those of the full mode bit for bit (the +-1 ulp draws consume the generator identically), the Jacobians are zero, and
+the blocks' costs are also summed at 60 digits (Ref.cost_mp).  `relo=True` adds the relocalization blocks (family 'relo': a point block on Pose[start frame of the
+landmark], relo_Pose, Ex_Pose and the landmark, never a td factor), which uvs_evaluate and the default mode skip.  Measured on the canonical window with a
+prior (750 point, 280 line / VP and 10 IMU blocks, n = 75): 1.5 s serially without levels, 2.5 s on 8 workers with four draws per block; the full mode takes 2.1 s
+serially for a tenth of the blocks without levels.
 """
 import os
 from concurrent.futures import ProcessPoolExecutor
@@ -166,7 +173,7 @@ def _point_res(pi_, pj_, ex, lam, a, b, vi, vj, tdi, tdj, td, sq, use_td):
     return [sq * (pcj[0] / pcj[2] - b[0]), sq * (pcj[1] / pcj[2] - b[1])], pcj
 
 
-def _point_once(d, h):
+def _point_once(d, h, jac=True):
     pi_, pj_, ex = _v(d["pose_i"]), _v(d["pose_j"]), _v(d["ex"])
     lam = mpf(float(d["lam"])); a, b = _v(d["pi"]), _v(d["pj"])
     vi, vj = _v(d["vi"]), _v(d["vj"]); tdi, tdj, td = mpf(float(d["tdi"])), mpf(float(d["tdj"])), mpf(float(d["td"]))
@@ -184,6 +191,11 @@ def _point_once(d, h):
         else: o = _point_res(pi_, pj_, ex, lam, a, b, vi, vj, tdi, tdj, td + s, sq, use_td)
         return o[0] + o[1]
     r, pc = _point_res(pi_, pj_, ex, lam, a, b, vi, vj, tdi, tdj, td, sq, use_td)
+    if not jac:      # residual-only: what the Jacobian does not enter (r, the loss, the cost) as in the full mode; J and its model stay zero
+        rho, rr, _, ks = _cauchy(mpf(d["loss"]), r, [])
+        z20 = np.zeros((2, 20))
+        return dict(r=[_f(r), _f(rr)], J=[z20, z20], mJ=[z20, z20], cost=[float(sum(x * x for x in r)) / 2, float(rho) / 2], cost_mp=[sum(x * x for x in r) / 2, rho / 2],
+                    aux=dict(depth_j=float(pc[2]), lam=float(lam)))
     J5 = _central(f, 20 if use_td else 19, h)
     if not use_td: J5 = [row + [mpf(0)] for row in J5]
     J = J5[:2]
@@ -227,7 +239,7 @@ def _line_vp_res(x, qw, ex, sp, ep, vp, lf, vf, has_vp):
     return out, s2
 
 
-def _line_once(d, h):
+def _line_once(d, h, jac=True):
     x = _v(d["pose"][:6]) + _v(d["line"]); qw = mpf(float(d["pose"][6])); ex = _v(d["ex"])
     sp, ep, vp = _v(d["sp"]), _v(d["ep"]), _v(d["vp"])
     lf, vf, hv = mpf(d["line_factor"]), mpf(d["vp_factor"]), bool(d["has_vp"])
@@ -236,9 +248,10 @@ def _line_once(d, h):
         y = list(x); y[k] = y[k] + s
         return _line_vp_res(y, qw, ex, sp, ep, vp, lf, vf, hv)[0]
     r, s2 = _line_vp_res(x, qw, ex, sp, ep, vp, lf, vf, hv)
-    J = _central(f, 10, h)
+    J = _central(f, 10, h) if jac else [[mpf(0)] * 10 for _ in r]      # residual-only: zero Jacobians, everything else as in the full mode
     rho, rr, Jr, _ = _cauchy(mpf(d["loss_line"]), r[:2], J[:2])
     out = dict(r=[_f(r[:2]), _f(rr)], J=[_f(J[:2]), _f(Jr)], cost=[float(r[0] * r[0] + r[1] * r[1]) / 2, float(rho) / 2])
+    if not jac: out["cost_mp"] = [(r[0] * r[0] + r[1] * r[1]) / 2, rho / 2]
     z1, z10 = np.zeros(1), np.zeros((1, 10))
     if hv:
         guarded = s2 <= mpf(VP_GUARD)
@@ -249,6 +262,7 @@ def _line_once(d, h):
         mJ = np.zeros((1, 10)) if guarded else np.abs(_f(Jv)) * (VP_DC / s2f)
         out.update(vr=[_f([r[2]]), _f(rv)], vJ=[_f(Jv), _f(Jvr)], vcost=[float(r[2] * r[2]) / 2, float(rho) / 2],
                    vmr=[np.array([mr]), np.array([mr * k])], vmJ=[mJ, mJ * k], aux=dict(s2=s2f, guarded=bool(guarded)))
+        if not jac: out["vcost_mp"] = [r[2] * r[2] / 2, rho / 2]
     else:
         out.update(vr=[z1, z1], vJ=[z10, z10], vcost=[0.0, 0.0], vmr=[z1, z1], vmJ=[z10, z10], aux=dict(s2=float("nan"), guarded=False))
     return out
@@ -290,7 +304,7 @@ def _imu_raw(B, G, pi_, sbi, pj_, sbj):
     return rp + [2 * qe[0], 2 * qe[1], 2 * qe[2]] + rv + _sub(sbj[3:6], sbi[3:6]) + _sub(sbj[6:9], sbi[6:9]), cq, qe
 
 
-def _imu_once(d, h):
+def _imu_once(d, h, jac=True):
     B = dict(sum_dt=mpf(float(d["sum_dt"])), dp=_v(d["delta_p"]), dq=_v(d["delta_q"]), dv=_v(d["delta_v"]), lin_ba=_v(d["linearized_ba"]),
              lin_bg=_v(d["linearized_bg"]), jac=[_v(row) for row in np.asarray(d["jacobian"], np.float64).reshape(15, 15)])
     G = [mpf(float(g)) for g in d["G"]]
@@ -305,6 +319,11 @@ def _imu_once(d, h):
         y = list(sbj); y[k - 21] = y[k - 21] + s
         return _imu_raw(B, G, pi_, sbi, pj_, y)[0]
     raw, cq, qe = _imu_raw(B, G, pi_, sbi, pj_, sbj)
+    if not jac:      # residual-only: the whitened residual alone
+        W = _whiten(np.asarray(d["covariance"], np.float64).reshape(15, 15))
+        r = [sum(W[i][k] * raw[k] for k in range(i, 15)) for i in range(15)]
+        z = np.zeros((15, 30)); c = sum(x * x for x in r) / 2
+        return dict(r=[_f(r)] * 2, J=[z] * 2, mJ=[z] * 2, cost=[float(sum(x * x for x in r)) / 2] * 2, cost_mp=[c, c], aux=dict(sum_dt=float(B["sum_dt"])), W=_f(W))
     J = _central(f, 30, h)
     # (O_R, O_R) of pose i: the reference's expression is |Q_j^-1 Q_i corrected_delta_q|^2 = 1 / |q_e|^2 times the derivative (module docstring;
     # |corrected_delta_q|^2 when the frame quaternions are unit)
@@ -333,7 +352,7 @@ def _imu_once(d, h):
 
 
 # ---------------------------------------------------------------- prior
-def _prior_once(d, h):
+def _prior_once(d, h, jac=True):
     n = int(d["n"]); x0 = _v(d["x0"]); r0 = _v(d["r0"]); J0 = np.asarray(d["J0"], np.float64).reshape(n, n)
     dx = [mpf(0)] * n
     neg = []
@@ -350,34 +369,45 @@ def _prior_once(d, h):
             for k in range(3): dx[idx + 3 + k] = sg * e[k]
     nz = [k for k in range(n) if dx[k] != 0]
     r = [r0[i] + sum(mpf(float(J0[i, k])) * dx[k] for k in nz) for i in range(n)]
-    return dict(r=[_f(r)] * 2, cost=[float(sum(x * x for x in r)) / 2] * 2, aux=dict(negative_w=neg))
+    out = dict(r=[_f(r)] * 2, cost=[float(sum(x * x for x in r)) / 2] * 2, aux=dict(negative_w=neg))
+    if not jac:
+        # the absolute terms of the quadratic form c0 + g0 . dx + dx . (H0 dx) / 2 the solve evaluates the prior in (`quad`):
+        # A = 1/2 sum_k (|r0_k| + sum_j |J0_kj| |dx_j|)^2; and dx itself, for the tests that look at its size
+        A = sum((abs(r0[i]) + sum(abs(mpf(float(J0[i, k])) * dx[k]) for k in nz)) ** 2 for i in range(n)) / 2
+        c = sum(x * x for x in r) / 2
+        out["cost_mp"] = [c, c]; out["aux"] = dict(negative_w=neg, quad_A=float(A), dx=_f(dx), c0=float(sum(x * x for x in r0) / 2))
+    return out
 
 
-_ONCE = dict(pt=_point_once, ln=_line_once, imu=_imu_once, prior=_prior_once)
-_INPUTS = dict(pt=("pose_i", "pose_j", "ex", "lam", "pi", "pj", "vi", "vj", "tdi", "tdj", "td"),
+_ONCE = dict(pt=_point_once, ln=_line_once, imu=_imu_once, prior=_prior_once, relo=_point_once)
+_INPUTS = dict(pt=("pose_i", "pose_j", "ex", "lam", "pi", "pj", "vi", "vj", "tdi", "tdj", "td"), relo=("pose_i", "pose_j", "ex", "lam", "pi", "pj"),
                ln=("pose", "line", "ex", "sp", "ep", "vp"),
                imu=("sum_dt", "delta_p", "delta_q", "delta_v", "linearized_ba", "linearized_bg", "jacobian", "covariance", "pose_i", "sb_i", "pose_j", "sb_j"),
                prior=("x0", "r0", "J0", "x"))
-_ARRAYS = dict(pt=("r", "J"), ln=("r", "J", "vr", "vJ"), imu=("r", "J"), prior=("r",))
+_ARRAYS = dict(pt=("r", "J"), ln=("r", "J", "vr", "vJ"), imu=("r", "J"), prior=("r",), relo=("r", "J"))
+_FAMILY_STREAM = {"pt": 1, "ln": 2, "imu": 3, "prior": 4, "relo": 5}
 
 
 def block_task(task):
     """One residual block: the reference at the inputs as given and, with task['draws'] > 0, the largest deviation over that many +-1 ulp
-    re-evaluations.  Runs in a worker process (mpmath + numpy only).  Step task['h'], precision task['dps']."""
+    re-evaluations.  Runs in a worker process (mpmath + numpy only).  Step task['h'], precision task['dps'].  task['jacobians'] = False: the
+    residual-only mode (no central differences: r, cost, the level of r and the residual models as in the full mode, Jacobians zero)."""
     fam, d = task["family"], task["data"]
     mp.mp.dps = task.get("dps", DPS)
     h = mpf(task.get("h", H))
-    base = _ONCE[fam](d, h)
+    jac = task.get("jacobians", True)
+    base = _ONCE[fam](d, h) if jac else _ONCE[fam](d, h, False)
+    names = _ARRAYS[fam] if jac else tuple(nm for nm in _ARRAYS[fam] if nm.endswith("r"))
     if task.get("draws", 0) > 0:
-        rng = np.random.default_rng([task["seed"], task["index"], {"pt": 1, "ln": 2, "imu": 3, "prior": 4}[fam]])
+        rng = np.random.default_rng([task["seed"], task["index"], _FAMILY_STREAM[fam]])
         lvl = {nm: [np.zeros_like(base[nm][0]), np.zeros_like(base[nm][1])] for nm in _ARRAYS[fam]}
         for _ in range(task["draws"]):
             if fam == "prior":
                 dd = _perturb(d, ("x0", "r0", "J0"), rng); dd["x"] = [_ulp(x, rng) for x in d["x"]]
             else:
                 dd = _perturb(d, _INPUTS[fam], rng)
-            o = _ONCE[fam](dd, h)
-            for nm in _ARRAYS[fam]:
+            o = _ONCE[fam](dd, h) if jac else _ONCE[fam](dd, h, False)
+            for nm in names:
                 for v in range(2): lvl[nm][v] = np.maximum(lvl[nm][v], np.abs(o[nm][v] - base[nm][v]))
         base["level"] = lvl
     mp.mp.dps = DPS
@@ -430,13 +460,16 @@ def _opts(o):
                 loss_line=float(o.loss_line), loss_vp=float(o.loss_vp), G=[float(o.gravity[k]) for k in range(3)], use_td=bool(o.estimate_td))
 
 
-def tasks_of(w, opts, subset=None, draws=4, level_stride=1, seed=0, dps=DPS, h=H):
+def tasks_of(w, opts, subset=None, draws=4, level_stride=1, seed=0, dps=DPS, h=H, jacobians=True, relo=False):
     """The block tasks of window `w`.  subset: None (all) or dict(pt=[...], ln=[...], imu=[...], prior=bool).  Every level_stride-th block of a
-    family gets its level; blocks named in subset['level'] (dict family -> indices) always do."""
+    family gets its level; blocks named in subset['level'] (dict family -> indices) always do.  jacobians=False: the residual-only mode of
+    block_task.  relo=True: the relocalization blocks of the window too (family 'relo'; solve-only blocks, estimator.cpp:944-978: the point block
+    between Pose[frame of the landmark's first observation] and relo_Pose, the extrinsic and the landmark, never a td factor)."""
     o = _opts(opts); out = []
     want = lambda fam, n: range(n) if subset is None else subset.get(fam, [])
     force = (subset or {}).get("level", {})
     common = dict(seed=seed, dps=dps, h=h)
+    if not jacobians: common["jacobians"] = False
     td_on = o["use_td"] and w.pt_vel_i is not None
     z2 = np.zeros(2)
     for k in want("pt", len(w.pt_lm)):
@@ -457,6 +490,14 @@ def tasks_of(w, opts, subset=None, draws=4, level_stride=1, seed=0, dps=DPS, h=H
         d = {k: np.asarray(blk[k], np.float64) for k in ("sum_dt", "delta_p", "delta_q", "delta_v", "linearized_ba", "linearized_bg", "jacobian", "covariance")}
         d.update(pose_i=w.pose[i], sb_i=w.speedbias[i], pose_j=w.pose[i + 1], sb_j=w.speedbias[i + 1], G=o["G"])
         out.append(dict(family="imu", index=b, data=d, draws=draws, **common))
+    if relo and len(w.relo_lm):
+        first = {}
+        for k in range(len(w.pt_lm)): first.setdefault(int(w.pt_lm[k]), int(w.pt_fi[k]))
+        for k in want("relo", len(w.relo_lm)):
+            lm = int(w.relo_lm[k])
+            d = dict(pose_i=w.pose[first[lm]], pose_j=w.relo_pose, ex=w.ex_pose, lam=w.inv_depth[lm], pi=w.relo_pi[k], pj=w.relo_pj[k], vi=z2, vj=z2, tdi=0.0, tdj=0.0,
+                     td=0.0, sqrt_info=o["sqrt_info"], loss=o["loss"], use_td=False)
+            out.append(dict(family="relo", index=k, data=d, draws=draws if (k % level_stride == 0 or k in force.get("relo", ())) else 0, **common))
     if w.prior is not None and w.prior.n > 0 and (subset is None or subset.get("prior", False)):
         p = w.prior; nb = p.n_blocks
         xs = []
@@ -481,8 +522,9 @@ def evaluate_cached(key, w, opts, **kw):
     import pickle
     d = os.environ.get("UVS_FACTOR_REF_CACHE")
     if not d: return evaluate(w, opts, **kw)
-    tasks = tasks_of(w, opts, kw.get("subset"), kw.get("draws", 4), kw.get("level_stride", 1), kw.get("seed", 0), kw.get("dps", DPS), kw.get("h", H))
-    tag = hashlib.sha1(pickle.dumps([(t["family"], t["index"], t["draws"], sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else pickle.dumps([np.asarray(x).tobytes() for x in v])) for k, v in t["data"].items())) for t in tasks])).hexdigest()[:16]
+    tasks = tasks_of(w, opts, kw.get("subset"), kw.get("draws", 4), kw.get("level_stride", 1), kw.get("seed", 0), kw.get("dps", DPS), kw.get("h", H),
+                     kw.get("jacobians", True), kw.get("relo", False))
+    tag = hashlib.sha1(pickle.dumps([(t["family"], t["index"], t["draws"]) + (() if t.get("jacobians", True) else ("r",)) + (sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else pickle.dumps([np.asarray(x).tobytes() for x in v])) for k, v in t["data"].items()),) for t in tasks])).hexdigest()[:16]
     path = os.path.join(d, f"{key}-{tag}.pkl")
     if os.path.exists(path):
         with open(path, "rb") as f: return pickle.load(f)
@@ -493,15 +535,26 @@ def evaluate_cached(key, w, opts, **kw):
     return out
 
 
-def evaluate(w, opts, subset=None, draws=4, level_stride=1, seed=0, parallel=True, dps=DPS, h=H):
-    """-> {False: Ref, True: Ref}: the reference of window `w` without and with the loss correction."""
-    res = run(tasks_of(w, opts, subset, draws, level_stride, seed, dps, h), parallel)
+def evaluate(w, opts, subset=None, draws=4, level_stride=1, seed=0, parallel=True, dps=DPS, h=H, jacobians=True, relo=False):
+    """-> {False: Ref, True: Ref}: the reference of window `w` without and with the loss correction.  jacobians=False (residual-only mode): r,
+    cost, the level of r and the residual models are those of the full mode, the Jacobians are zero, and the Ref also carries cost_mp, the sum of
+    the blocks' costs taken at 60 digits (rounded by whoever uses it, once).  relo=True: the relocalization blocks too, as relo_r / cost_terms['relo'] /
+    level['relo_r']; they enter cost_mp and NOT cost (uvs_evaluate does not evaluate them)."""
+    res = run(tasks_of(w, opts, subset, draws, level_stride, seed, dps, h, jacobians, relo), parallel)
     out = {}
     for v, robust in enumerate((False, True)):
         R = Ref(w)
+        cmp_ = mpf(0)
+        if relo:
+            nr = len(w.relo_lm)
+            R.relo_r = np.zeros((nr, 2)); R.cost_terms["relo"] = np.zeros(nr); R.level["relo_r"] = np.full((nr, 2), np.nan); R.have["relo"] = np.zeros(nr, bool); R.aux["relo"] = {}
         for fam, k, b in res:
             lv = b.get("level")
-            if fam == "pt":
+            if "cost_mp" in b: cmp_ += b["cost_mp"][v] + (b["vcost_mp"][v] if "vcost_mp" in b else 0)
+            if fam == "relo":
+                R.relo_r[k] = b["r"][v]; R.cost_terms["relo"][k] = b["cost"][v]
+                if lv: R.level["relo_r"][k] = lv["r"][v]
+            elif fam == "pt":
                 R.pt_r[k] = b["r"][v]; R.pt_J[k] = b["J"][v][:, :19]; R.pt_Jtd[k] = b["J"][v][:, 19]; R.cost_terms["pt"][k] = b["cost"][v]
                 R.model["pt_J"][k] = b["mJ"][v][:, :19]; R.model["pt_Jtd"][k] = b["mJ"][v][:, 19]
                 if lv: R.level["pt_r"][k] = lv["r"][v]; R.level["pt_J"][k] = lv["J"][v][:, :19]; R.level["pt_Jtd"][k] = lv["J"][v][:, 19]
@@ -526,6 +579,7 @@ def evaluate(w, opts, subset=None, draws=4, level_stride=1, seed=0, parallel=Tru
                 for nm in ("imu_r", "imu_J"): R.level[nm][b] = 0.0
         ct = R.cost_terms
         R.cost = float(ct["prior"] + ct["imu"].sum() + ct["pt"].sum() + ct["ln"].sum() + ct["vp"].sum())
+        if not jacobians: R.cost_mp = cmp_
         out[robust] = R
     return out
 

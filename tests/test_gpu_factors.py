@@ -14,6 +14,7 @@ import pytest
 from helpers import abi
 import factor_cases as cases
 import factor_ref as fr
+import lm_accept_ref
 import lm_step_ref
 from lm_step_check import _Env
 
@@ -95,11 +96,9 @@ def _prior_columns(w, L):
     return cols, src
 
 
-def _first_iteration_reference(w, o, ref):
-    """(g_reduced, diag H, their entrywise first-order bounds) over the frame columns of lm_step_ref.layout, from the reference's evaluation.
-    g_reduced = g_f - H_fl H_ll^-1 g_l of the damped system in unscaled coordinates (helpers.lm_reduced_system), in longdouble; the bound carries
-    dg_f + |H_fl H_ll^-1| dg_l + dH_fl |H_ll^-1 g_l| + |H_fl H_ll^-1| dH_ll |H_ll^-1 g_l|, the damping's share of dH_ll included."""
-    L = lm_step_ref.layout(w, o); F, P = L["frames"], L["n"]
+def _normal_equations_reference(w, o, ref):
+    """(H, g, their entrywise first-order bounds dH, dg, layout) over the whole parameter vector, from the reference's evaluation."""
+    L = lm_step_ref.layout(w, o)
     H, g = lm_step_ref.normal_equations(w, ref, o)
     B = fr.entry_bounds(ref, C)
     Ha, ga = lm_step_ref.normal_equations(w, _abs_eval(w, ref, B, False), o)
@@ -108,6 +107,14 @@ def _first_iteration_reference(w, o, ref):
     if w.prior is not None and w.prior.n > 0:
         cols, src = _prior_columns(w, L)
         dg[cols] += np.abs(w.prior.J0()[:, src]).T @ B["prior_r"][:w.prior.n]
+    return H, g, dH, dg, L
+
+
+def _first_iteration_reference(w, o, ref):
+    """(g_reduced, diag H, their entrywise first-order bounds) over the frame columns of lm_step_ref.layout, from the reference's evaluation.
+    g_reduced = g_f - H_fl H_ll^-1 g_l of the damped system in unscaled coordinates (helpers.lm_reduced_system), in longdouble; the bound carries
+    dg_f + |H_fl H_ll^-1| dg_l + dH_fl |H_ll^-1 g_l| + |H_fl H_ll^-1| dH_ll |H_ll^-1 g_l|, the damping's share of dH_ll included."""
+    H, g, dH, dg, L = _normal_equations_reference(w, o, ref); F, P = L["frames"], L["n"]
     hd = np.diag(H).copy(); dhd = np.diag(dH).copy()
     s = LD(1) / (LD(1) + np.sqrt(hd)) if o.jacobi_scaling else np.ones(P, LD)
     radius = LD(o.initial_trust_region_radius)
@@ -173,22 +180,27 @@ def test_first_iteration_matches_the_reference(gpu_api, name, nt):
 
 @pytest.mark.parametrize("name", cases.SOLVE_NAMES)
 def test_initial_cost_of_every_solver_matches_the_reference(gpu_api, name):
-    """initial_cost of solve (both k_solve instantiations), large_solve and large_solve_fused against the reference's cost, bound sum |r| B_r."""
+    """initial_cost of solve (both k_solve instantiations), large_solve and large_solve_fused against the reference's cost, bound sum |r| B_r; and their
+    gradient_max_norm[0] against || x - Plus(x, -g*) ||_inf of the reference's gradient (lm_accept_ref.gradient_max_norm), bound: the largest entry bound
+    propagated for g, plus 1e-13 of the value."""
     w, o, R = _case(gpu_api, name)
     ref = R[True]; cb = fr.cost_bound(ref, C)
-    got = {}
+    _, g, _, dg, _ = _normal_equations_reference(w, o, ref)
+    gmax = lm_accept_ref.gradient_max_norm(w, o, g); gb = float(dg.max()) + 1e-13 * gmax
+    got = {}; grad = {}
     for nt in (512, 256):
         with _Env({"UVS_KSOLVE_NT": str(nt)}):
             s = gpu_api.Solver(opts=o, max_batch=2)
         try:
-            got[f"solve{nt}"] = s.solve(w)[1].initial_cost
-            if nt == 512:
-                got["large_solve"] = s.large_solve(w)[1].initial_cost
-                got["large_solve_fused"] = s.large_solve_fused(w)[1].initial_cost
+            reps = {f"solve{nt}": s.solve(w)[1]}
+            if nt == 512: reps.update(large_solve=s.large_solve(w)[1], large_solve_fused=s.large_solve_fused(w)[1])
+            for nm, r in reps.items(): got[nm], grad[nm] = r.initial_cost, r.gradient_max_norm[0]
         finally:
             s.close()
     bad = []
     for nm, c0 in got.items():
         fr.log(f"{nm} {name}: initial_cost {c0:.17g} reference {ref.cost:.17g} |diff| {abs(c0 - ref.cost):.2e} bound {cb:.2e}")
         if not abs(c0 - ref.cost) <= cb: bad.append((nm, c0, ref.cost, cb))
+        fr.log(f"{nm} {name}: gradient_max_norm[0] {grad[nm]:.17g} reference {gmax:.17g} |diff| {abs(grad[nm] - gmax):.2e} bound {gb:.2e}")
+        if not abs(grad[nm] - gmax) <= gb: bad.append((nm, "gradient_max_norm", grad[nm], gmax, gb))
     assert not bad, (name, bad)
