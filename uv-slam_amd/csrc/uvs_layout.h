@@ -74,6 +74,8 @@
 #define UVS_GT UVS_NT
 #endif
 #define UVS_NGRP (UVS_GT / UVS_GLANES)      // gather groups; each owns one 6x6 pose block or one part of a split one
+#define UVS_GRP_PER_WAVE (64 / UVS_GLANES)  // ... of one wave; the host packing deals the groups to the waves by it (uvs_pack.cpp: assign_groups)
+#define UVS_GWAVES (UVS_GT / 64)            // waves that hold gather accumulators: all four of the 256-thread library build (the kernel's NW there), waves 4..7 of the 512-thread one
 
 #define UVS_CHUNK_INTS 8
 struct DevWin {
@@ -103,7 +105,7 @@ struct DevWin {
     int32_t i_chunks;                 // [n_chunks][UVS_CHUNK_INTS] : type(0 pt,1 ln), lm_begin, lm_end, offset of the chunk's gather lists in i_lists, their length, 0, first observation, observations
                                       // (the last two save the kernel two dependent loads from the CSR arrays at the head of every chunk: the whole descriptor is ONE 32-byte scalar load)
     int32_t i_wblk;                   // [UVS_NGRP] gather group -> pose block id | 256 (diagonal block) | part << 9 (4 bits, split blocks) | fa << 13 | fb << 17 | (parts - 1) << 21 (the parts of a block are consecutive groups); -1 = idle
-    int32_t i_lists;                  // per chunk: schur_off[81] direct_off[81] entries[...]  (group-major, see pack_window in uvs_solver.hip)
+    int32_t i_lists;                  // per chunk: schur_off[81] direct_off[81] entries[...]  (group-major: schur_off and direct_off have UVS_NGRP + 1 ints each; written by write_lists of uvs_pack.cpp)
     // workspace
     int32_t w_invd0, w_invd1, w_line0, w_line1;       // landmark parameters, two buffers (current / candidate)
     int32_t w_ltrig0, w_ltrig1;                        // sin/cos of the four orthonormal line angles, [n_lines][8], one per parameter buffer (k_solve only)

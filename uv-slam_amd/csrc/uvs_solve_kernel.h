@@ -1203,7 +1203,8 @@ UVS_DEV void chol_solve(const Ctx& c) { if (c.hdr->chol_half_ok) chol_solve_call
 //   direct entry: points: offset of the first Jacobian block | offset of the second << 16 ; lines: record offset
 // Gradient entries need no Schur list: pass B stores the Schur-CORRECTED residual rc = r - J_l H_ll^-1 g_l in every record,
 // and sum_o J_p^T rc IS the reduced gradient.
-static constexpr int GRP_PER_WAVE = 64 / UVS_GLANES;
+static constexpr int GRP_PER_WAVE = UVS_GRP_PER_WAVE;
+static_assert(NW == (ROLES ? 2 : 1) * UVS_GWAVES && UVS_GWAVES * GRP_PER_WAVE == UVS_NGRP, "the host packing deals UVS_NGRP gather groups to UVS_GWAVES waves (uvs_layout.h)");
 static constexpr int GR = UVS_GROWS;      // block rows per lane
 static constexpr int LIST_HDR = 2 * (UVS_NGRP + 1);
 typedef double d2_t __attribute__((ext_vector_type(2)));
