@@ -25,8 +25,8 @@ __global__ __launch_bounds__(NT) void k_evaluate(char* blob, double* ws, KOpts o
     extern __shared__ __attribute__((aligned(16))) double sh[];   // same LDS map as the solver (launched with LDS_BYTES)
     const int tid = threadIdx.x;
     Ctx c;
-    c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o;
-    const DevWin& h = *c.hdr;
+    c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o;
+    DevWinK& h = *c.hdr;
     if (tid < UVS_XDIM) sh[L_X + tid] = c.bd[h.d_frames + tid];
     setup_window(c, (double*)blob, false, marg0 ? 0 : -1);
     __syncthreads();

@@ -77,8 +77,8 @@ __global__ __launch_bounds__(NT) void k_large_chunks(char* blob, double* ws, KOp
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int tid = threadIdx.x;
     if (lc.ctl) { if (lc.ctl[LC_DONE] != 0.0) return; sel = (int)lc.ctl[LC_SEL]; first = (int)lc.ctl[LC_FIRST]; radius = lc.ctl[LC_RADIUS]; }
-    Ctx c; c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
-    const DevWin& h = *c.hdr;
+    Ctx c; c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
+    DevWinK& h = *c.hdr;
     UVS_LPROF(0);
     // after a rejected step (fused loop): same point, new radius -- the landmark partials are UPDATED by the change of their Schur terms
     // (redamp_chunk), the frame image (undamped) stays as it is
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(NT) void k_large_solve(char* blob, double* ws, KOpt
         gmax_lm = 0.0;
         for (int r = 0; r < LG_MAXRANKS; ++r) gmax_lm = fmax(gmax_lm, reduced[LX_GMAX + r]);
     }
-    Ctx c; c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
+    Ctx c; c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
     if (tid < UVS_XDIM) sh[L_X + tid] = state[LS_X + tid];
     if (tid < UVS_RD && !first) sh[L_SC + tid] = state[LS_SC + tid];
     // the frame image (k_large_chunks' extra workgroup): 147 KB, 16-byte loads, everything in flight before the first store
@@ -276,8 +276,8 @@ __device__ __forceinline__ void large_backsub_body(char* blob, double* ws, KOpts
     extern __shared__ __attribute__((aligned(16))) double sh[];
     const int tid = threadIdx.x;
     if (lc.ctl) { if (lc.ctl[LC_DONE] != 0.0) return; sel = (int)lc.ctl[LC_SEL]; }
-    Ctx c; c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
-    const DevWin& h = *c.hdr;
+    Ctx c; c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
+    DevWinK& h = *c.hdr;
     if (tid < UVS_XDIM) sh[L_XC + tid] = state[LS_XC + tid];
     if (tid < UVS_RD) sh[L_DLT + tid] = state[LS_DLT + tid];
     __syncthreads();
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256) void k_large_decide(double* ctl, double* state
 // small host-side copies / memsets (each a separate stream operation) by one launch.
 __global__ __launch_bounds__(256) void k_large_init(const char* blob, double* ws, double* state, double* ctl, uvs_report* rep, double* reduced,
                                                     double radius0, double frame_x2, double local_x2) {
-    const DevWin& h = *(const DevWin*)blob; const double* bd = (const double*)blob;
+    DevWinK& h = *(DevWinK*)blob; const double* bd = (const double*)blob;
     const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
     for (int i = t; i < LG_STATE; i += nt) state[i] = (i >= LS_X && i < LS_X + UVS_XDIM) ? bd[h.d_frames + (i - LS_X)] : 0.0;
     for (int i = t; i < h.n_points; i += nt) ws[h.w_invd0 + i] = bd[h.d_invd + i];
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void k_large_init(const char* blob, double* ws
 // End of a fused solve: everything the host reads back, gathered into one buffer [ctl 64 | report | frames 192 | inverse depths | line parameters]
 // (the landmark buffer that holds the accepted values is only known on the device: ctl[LC_SEL])
 __global__ __launch_bounds__(256) void k_large_pack(const char* blob, const double* ws, const double* state, const double* ctl, const uvs_report* rep, double* out) {
-    const DevWin& h = *(const DevWin*)blob;
+    DevWinK& h = *(DevWinK*)blob;
     constexpr int RD = (int)(sizeof(uvs_report) / 8);
     const int sel = (int)ctl[LC_SEL];
     const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;

@@ -78,6 +78,17 @@
 #define UVS_GWAVES (UVS_GT / 64)            // waves that hold gather accumulators: all four of the 256-thread library build (the kernel's NW there), waves 4..7 of the 512-thread one
 
 #define UVS_CHUNK_INTS 8
+// What a kernel may read through the SCALAR cache (uvs_solve_kernel.h: DevWinK / IntK, the constant address space).  That cache is coherent with nothing a launch
+// itself writes: it is invalidated when a kernel starts and never sees the vector stores of the running one.  So only bytes that NO kernel writes during a launch go
+// that way -- today
+//   * this header, all of it: the only device store into it is cur_sel, written once by one lane at the very end of k_solve and never read on the device
+//     (out_host is patched by the host, in the staged copy, before the upload);
+//   * the chunk table (i_chunks), indexed by a workgroup-uniform chunk number;
+//   * the IMU block table (i_imu), where a wave indexes it by its own block (lin_imu_tiles).
+// Everything a kernel generates stays on vector loads or LDS, however constant it looks from the next phase: the whole workspace (w_*: w_cimg, w_prior_h0, w_imu_w, the
+// landmark buffers, ...).  The per-lane tables of the blob (i_wblk, the prior's column map, the CSR and observation arrays, the gather lists) are written by
+// no kernel either, but a per-lane index makes their loads vector loads anyway; they keep the plain pointer.  No kernel stores through `blob` beside cur_sel
+// (setup_window's blob_rw is read only); a store added there has to take its target off the list above first.
 struct DevWin {
     int32_t n_points, n_pt_obs, n_lines, n_ln_obs, n_imu, prior_n, prior_nb, n_chunks;
     int32_t pt_stride, ln_stride;     // SoA strides of the measurement arrays
@@ -103,7 +114,9 @@ struct DevWin {
     int32_t i_imu;                    // [n_imu][2] : frame_i, skip
     int32_t i_prior;                  // kind[16] frame[16] size[16] idx[16] x0off[16] colmap[96] inverse colmap[176] touched S blocks[66]
     int32_t i_chunks;                 // [n_chunks][UVS_CHUNK_INTS] : type(0 pt,1 ln), lm_begin, lm_end, offset of the chunk's gather lists in i_lists, their length, 0, first observation, observations
-                                      // (the last two save the kernel two dependent loads from the CSR arrays at the head of every chunk: the whole descriptor is ONE 32-byte scalar load)
+                                      // (the last two save the kernel two dependent loads from the CSR arrays at the head of every chunk.  chunk_desc reads the descriptor through the
+                                      // scalar cache, the words a call site uses: s_load_dwordx4 of words 0..3, s_load_dwordx2 of words 6..7, a dword for word 4 where the list length is
+                                      // needed -- two or three scalar loads issued back to back behind one wait, not the single 32-byte load this comment used to promise)
     int32_t i_wblk;                   // [UVS_NGRP] gather group -> pose block id | 256 (diagonal block) | part << 9 (4 bits, split blocks) | fa << 13 | fb << 17 | (parts - 1) << 21 (the parts of a block are consecutive groups); -1 = idle
     int32_t i_lists;                  // per chunk: schur_off[81] direct_off[81] entries[...]  (group-major: schur_off and direct_off have UVS_NGRP + 1 ints each; written by write_lists of uvs_pack.cpp)
     // workspace

@@ -202,8 +202,31 @@ UVS_DEV void lacc_add(double* sh, double cost, double gmax) {
 UVS_DEV double lacc_cost(const double* sh) { const int tid = lane_tid(); return tid < ET ? sh[L_LCOST + tid] : 0.0; }
 UVS_DEV double lacc_gmax(const double* sh) { return sh[L_LGMAX + (lane_tid() >> 6)]; }
 
+// The launch-invariant words of the blob (uvs_layout.h, "What a kernel may read through the scalar cache": the header, the chunk table, the IMU block table) are
+// read through the CONSTANT address space.  Behind the plain blob pointer the compiler can prove neither that they are invariant nor that a scalar load is safe
+// (the kernels store through other plain pointers), so every h.field was a vector global load, repeated at every phase entry and queued in the same in-order
+// vmcnt as the data loads it precedes; in the constant address space it is an s_load that the scalar cache serves and that may be hoisted.  The wave-uniform
+// index of a table word goes through wave_uniform() / readfirstlane, so that the load itself is scalar.  -DUVS_X_VECTOR_HEADER (A/B builds only,
+// tools/ab/build_variant.sh) gives the plain pointers back.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(UVS_X_VECTOR_HEADER)
+#define UVS_KSPACE __attribute__((address_space(4)))
+#define UVS_KIDX(i) __builtin_amdgcn_readfirstlane(i)      // an index that is the same in every lane of the wave
+#define UVS_KWAVE(tid) wave_uniform()                      // the wave of lane `tid`
+// a header word that a pipelined loop uses, loaded BEFORE the loop and held in its SGPR: an s_load shares lgkmcnt with the LDS reads and returns out of order, so one
+// inside the loop turns the loop's counted waits into lgkmcnt(0) -- and the spill-avoiding sinking of uvs_solve512.hip moves a plain invariant load back in
+static __device__ __forceinline__ int kpin(int v) { asm volatile("" : "+s"(v)); return v; }
+#define UVS_KPIN(v) kpin(v)
+#else
+#define UVS_KSPACE
+#define UVS_KIDX(i) (i)
+#define UVS_KWAVE(tid) ((tid) >> 6)
+#define UVS_KPIN(v) (v)
+#endif
+typedef const UVS_KSPACE DevWin DevWinK;
+typedef const UVS_KSPACE int IntK;
+
 struct Ctx {
-    const DevWin* hdr;
+    DevWinK* hdr;
     const double* bd;      // blob as doubles
     const int* bi;         // blob as ints
     double* ws;            // workspace of this window
@@ -215,7 +238,7 @@ struct Ctx {
 
 // sin/cos cache that belongs to the line-parameter buffer `line` (nullptr: compute on the fly)
 UVS_DEV const double* line_trig_of(const Ctx& c, const double* line) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     if (!c.ltrig_ok) return nullptr;
     return line == c.ws + h.w_line0 ? c.ws + h.w_ltrig0 : (line == c.ws + h.w_line1 ? c.ws + h.w_ltrig1 : nullptr);
 }
@@ -233,7 +256,7 @@ UVS_DEV const double* pose_of(const double* x, int f) { return x + (f > UVS_NF ?
 // measurements of point residual block `o`; with ESTIMATE_TD the time-shifted ones of ProjectionTdFactor (projection_td_factor.cpp:51-52):
 //   pts_i_td = pts_i - (td - td_i) * (vel_i, 0), same for j  (rolling-shutter term folded into td_i / td_j by the caller).  vij = vel_i.xy, vel_j.xy
 UVS_DEV void load_point_obs(const Ctx& c, int o, double td, double* pi, double* pj, double* vij) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const double* m = c.bd + h.d_ptmeas + o; const int st = h.pt_stride;
     pi[0] = m[0]; pi[1] = m[st]; pi[2] = m[2 * st]; pj[0] = m[3 * st]; pj[1] = m[4 * st]; pj[2] = m[5 * st];
     if (h.td_on) {
@@ -247,7 +270,7 @@ UVS_DEV void load_point_obs(const Ctx& c, int o, double td, double* pi, double* 
 // ------------------------------------------------------------------ residual-only cost at `x` (LDS) / landmark buffer `sel`
 UVS_DEV void stage_prior_tables(const Ctx& c) {      // once per solve; the caller's next barrier precedes the first prior_dx
     const int tid = lane_tid();
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     if (h.prior_n <= 0) return;
     int* tab = (int*)(c.sh + L_PTAB);
     if (tid < 4 * UVS_MAX_PRIOR_BLOCKS) tab[tid] = c.bi[h.i_prior + tid];      // kind[16] frame[16] size[16] idx[16]
@@ -255,7 +278,7 @@ UVS_DEV void stage_prior_tables(const Ctx& c) {      // once per solve; the call
 }
 UVS_DEV void prior_dx(const Ctx& c, const double* x) {
     const int tid = lane_tid() - 64;      // the lanes of the SECOND wave: its callers stage the rotations on the first lanes of wave 0 in the same breath, and one wave would run the two one after the other
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     if (h.prior_n > 0 && tid >= 0 && tid < h.prior_nb) {
         int kind, frame, size, idx;
         double x0[9];
@@ -292,7 +315,7 @@ UVS_DEV void prior_dx(const Ctx& c, const double* x) {
 // L2 / HBM on every evaluation; a 75-deep dependent chain would pay the memory latency 75 times).  Partials meet in the (dead) S region;
 // contains one workgroup barrier, so all threads must call it.
 UVS_DEV double prior_quad(const Ctx& c, int dst = L_PR) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int n = h.prior_n, tid = lane_tid();
     double cost = 0.0;
     if (n <= 0) return cost;
@@ -325,7 +348,7 @@ UVS_DEV double prior_quad(const Ctx& c, int dst = L_PR) {
 }
 // this thread's share of the prior cost at the point whose dx is staged in L_PDX and whose y = H0 dx sits in sh[src ..)
 UVS_DEV double prior_cost_share(const Ctx& c, int src) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int n = h.prior_n, tid = lane_tid();
     double cost = 0.0;
     if (tid < n) {
@@ -337,7 +360,7 @@ UVS_DEV double prior_cost_share(const Ctx& c, int src) {
 // The residual vector itself, r = r0 + J0 dx (marginalization_factor.cpp:364), for uvs_evaluate / the host marginalization path: one lane per row,
 // J0 read row-wise (not a hot path).  After prior_dx + barrier; fills L_PR, returns this thread's 0.5 r^2.
 UVS_DEV double prior_residual_rows(const Ctx& c) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int n = h.prior_n, tid = lane_tid();
     double cost = 0.0;
     if (tid < n) {
@@ -355,7 +378,7 @@ UVS_DEV double prior_residual_rows(const Ctx& c) {
 // several workgroups per compute unit passes smaller ones (its other waves hide the latency, its register budget is smaller)
 // raw IMU residual of block (lane - lane0) -> scratch in the S region (cost_pass whitens them after its barrier)
 UVS_DEV void cost_imu_raw(const Ctx& c, const double* x, int lane0) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int b = lane_tid() - lane0;
     double* rs = c.sh + L_S + 1024;
     if (b >= 0 && b < h.n_imu) {
@@ -371,7 +394,7 @@ UVS_DEV void cost_imu_raw(const Ctx& c, const double* x, int lane0) {
 }
 template <int PB = CP_PB, int LB = CP_LB>
 UVS_DEV double cost_pass(const Ctx& c, const double* x, const double* invd, const double* line, int po0, int po1, int lo0, int lo1, bool with_imu) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int tid = lane_tid();
     const double* RF = c.sh + L_RF; const double* ric = c.sh + L_EX; const double* tic = c.sh + L_EX + 9;
     const double* ltrig = line_trig_of(c, line);
@@ -1474,7 +1497,7 @@ UVS_DEV double lin_prep(const Ctx& c, const double* x, int mode = 0) {
 // lin_imu_stage: W + raw residuals / Jacobians -> the operand tiles in LDS (evaluator waves; THREE workgroup barriers, the last one at its end);
 // lin_imu_tiles: the MFMA stages of this wave's blocks (every wave), returns this lane's cost share
 UVS_DEV void lin_imu_stage(const Ctx& c, const double* x) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid(), lane = tid & 63, wv = tid >> 6;
     __syncthreads();      // previous users of the S region are done
@@ -1517,18 +1540,19 @@ UVS_DEV void lin_imu_stage(const Ctx& c, const double* x) {
     UVS_TLOG(c, 43);
 }
 UVS_DEV double lin_imu_tiles(const Ctx& c, ImuN& N) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
-    const int tid = lane_tid(), lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int tid = lane_tid(), lane = tid & 63, wv = UVS_KWAVE(tid), li = lane & 15, lk = lane >> 4;
     double cost = 0.0;
     double* IM = sh + L_S;
+    IntK* itab = (IntK*)c.bi + h.i_imu;      // (frame_i, skip) of this wave's blocks: wave-uniform words, scalar loads
     // stage 1 for all of this wave's blocks, ONE wave-level hand-over, then stage 2: the LDS round trips and MFMA drains of the slots overlap
     bool act[IMU_SLOTS];
 #pragma unroll
     for (int s = 0; s < IMU_SLOTS; ++s) {
         const int b = imu_block_of(wv, s);
-        act[s] = b < h.n_imu && !c.bi[h.i_imu + 2 * (b < h.n_imu ? b : 0) + 1];
-        N.act[s] = act[s]; N.fi[s] = c.bi[h.i_imu + 2 * (b < h.n_imu ? b : 0)];
+        act[s] = b < h.n_imu && !itab[2 * (b < h.n_imu ? b : 0) + 1];
+        N.act[s] = act[s]; N.fi[s] = itab[2 * (b < h.n_imu ? b : 0)];
         if (act[s]) {
             double* Jb = IM + IMU_BLK * b; const double* Wb = Jb + IMU_WOFF;
             d4_t t0 = {0.0, 0.0, 0.0, 0.0}, t1 = t0;
@@ -1610,19 +1634,20 @@ static constexpr bool LISTS_BY_GATHERERS = false;
 #endif
 struct ChunkDesc { int type, k0, k1, o0, nob, nlm, nlist; const int* glists; };
 UVS_DEV ChunkDesc chunk_desc(const Ctx& c, int ch) {
-    const DevWin& h = *c.hdr;
-    const int* chunks = c.bi + h.i_chunks;
+    DevWinK& h = *c.hdr;
+    // `ch` is the same in every lane of the workgroup (a loop counter, or derived from blockIdx): the descriptor arrives through the scalar cache
+    IntK* chunks = (IntK*)c.bi + h.i_chunks + UVS_CHUNK_INTS * UVS_KIDX(ch);
     ChunkDesc d;
-    d.type = chunks[UVS_CHUNK_INTS * ch]; d.k0 = chunks[UVS_CHUNK_INTS * ch + 1]; d.k1 = chunks[UVS_CHUNK_INTS * ch + 2];
-    d.glists = c.bi + h.i_lists + chunks[UVS_CHUNK_INTS * ch + 3];      // gather lists of this chunk (HBM)
-    d.nlist = chunks[UVS_CHUNK_INTS * ch + 4];
+    d.type = chunks[0]; d.k0 = chunks[1]; d.k1 = chunks[2];
+    d.glists = c.bi + h.i_lists + chunks[3];      // gather lists of this chunk (HBM)
+    d.nlist = chunks[4];
     d.nlm = d.k1 - d.k0;
-    d.o0 = chunks[UVS_CHUNK_INTS * ch + 6]; d.nob = chunks[UVS_CHUNK_INTS * ch + 7];
+    d.o0 = chunks[6]; d.nob = chunks[7];
     return d;
 }
 // where the gather lists of a staged chunk sit (after the records and the Schur factors)
 UVS_DEV int* chunk_lists(const Ctx& c, const ChunkDesc& d) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* rec = c.sh + L_S;
     if (d.type == 0) return (int*)(rec + (size_t)d.nob * h.pt_rec + (size_t)(d.nob + h.pt_xslots * d.nlm) * 12);
     return (int*)(rec + (size_t)d.nob * (UVS_LN_REC + 2 * UVS_LN_EY) + 20 * d.nlm);
@@ -1631,7 +1656,7 @@ UVS_DEV int* chunk_lists(const Ctx& c, const ChunkDesc& d) {
 // slot E_0 = sum_o c_o A_o (and the time-offset / extrinsic slots).  One lane per landmark: the lane of its first observation in the 256-thread build, a lane of
 // the otherwise idle gatherer waves in the 512-thread build (pt_anchor_pass).
 UVS_DEV void pt_landmark_slots(const Ctx& c, const ChunkDesc& d, int k, int b0, int b1, double hd, double gl, double dd, double hinv, double ginv, double* gmax_lm) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int PREC = h.pt_rec, XS = h.pt_xslots, li = k - d.k0;
     double* rec = c.sh + L_S;
     double* Eb = rec + (size_t)d.nob * PREC;
@@ -1682,7 +1707,7 @@ static constexpr bool ANCHOR_BY_GATHERERS = false;
 // still running (pt_anchor_pre, before the barrier that ends pass A), so the pass itself starts on LDS data
 struct AnchorPre { int b0, b1; double sc; };
 UVS_DEV void pt_anchor_pre(const Ctx& c, const ChunkDesc& d, bool first, AnchorPre& ap) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int li = lane_tid() - GT0;
     ap.b0 = 0; ap.b1 = 0; ap.sc = 1.0;
     if (li >= 0 && li < d.nlm) {
@@ -1692,7 +1717,7 @@ UVS_DEV void pt_anchor_pre(const Ctx& c, const ChunkDesc& d, bool first, AnchorP
     }
 }
 UVS_DEV void pt_anchor_pass(const Ctx& c, const ChunkDesc& d, bool first, double radius, const AnchorPre& ap) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int* beg = c.bi + h.i_pt_beg;
     const double* rec = c.sh + L_S;
     double gmax_lm = 0.0;
@@ -1754,7 +1779,7 @@ UVS_DEV void pt_anchor_pass(const Ctx& c, const ChunkDesc& d, bool first, double
 // observation (index words, measurements, the landmark's parameters, CSR range and scale) and throws it away: the lines then sit in the compute unit's vector
 // L1, which nothing else uses during a gather walk (LDS traffic only), and the dependent loads at the head of the next passes hit there instead of in L2.
 UVS_DEV void chunk_touch(const Ctx& c, const ChunkDesc& d, const double* invd, const double* line) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int tid = lane_tid();
     if (tid >= d.nob) return;
     const int o = d.o0 + tid;
@@ -1801,7 +1826,7 @@ UVS_DEV void copy_lists_gatherers(const Ctx& c, const ChunkDesc& d) {
     }
 }
 UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const double* invd, const double* line, bool first, double radius) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
     const double* RF = sh + L_RF; const double* ric = sh + L_EX; const double* tic = sh + L_EX + 9;
@@ -2006,7 +2031,7 @@ UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const
 }
 UVS_DEV int chunk_eval_barriers(const ChunkDesc& d) { return d.type == 0 ? 3 : 4; }      // workgroup barriers inside chunk_eval
 UVS_DEV void chunk_gather(const Ctx& c, const ChunkDesc& d, int grp, GAcc& acc) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const double* rec = c.sh + L_S;
     const int* lists = chunk_lists(c, d);
     UVS_TLOG(c, 8);
@@ -2035,7 +2060,7 @@ UVS_DEV void lin_chunk(const Ctx& c, int ch, const double* x, const double* invd
 // redamp_prep: the staging half (2 workgroup barriers for a point chunk, 3 for a line chunk: redamp_barriers); redamp_gather: the Schur walk.
 UVS_DEV int redamp_barriers(const ChunkDesc& d) { return d.type == 0 ? 2 : 3; }
 UVS_DEV void redamp_prep(const Ctx& c, const ChunkDesc& d, double radius) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
     const int type = d.type, k0 = d.k0;
@@ -2169,7 +2194,7 @@ static constexpr int R2_R = 0, R2_RR = 1056, R2_G = 1092, R2_HD = 1098, R2_SC = 
 static_assert(R2_DR + 6 <= UVS_RELO2_DOUBLES, "side buffer");
 UVS_DEV int relo2_index(int p) { return p < 66 ? 16 * (p / 6) + p % 6 : (p < 72 ? UVS_EX_INDEX(p - 66) : UVS_TD_INDEX); }      // the 73 S indices R can touch
 UVS_DEV void relo2_eliminate(const Ctx& c, const double* x, bool first, double radius, double& gmax) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh; double* W = c.ws + h.w_relo2;
     const int tid = lane_tid();
     __syncthreads();      // the block rows written by the assembly are visible
@@ -2246,7 +2271,7 @@ UVS_DEV void relo2_eliminate(const Ctx& c, const double* x, bool first, double r
 }
 // the step of relo_Pose after the reduced solve (d_f in L_DLT): d_r = -(M^-1 g_r + Z d_f); mirrored to where an observation of pseudo frame 12 looks for it
 UVS_DEV void relo2_backsub(const Ctx& c) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh; double* W = c.ws + h.w_relo2;
     const int tid = lane_tid();
     if (tid < 6) {
@@ -2266,14 +2291,14 @@ UVS_DEV void relo2_backsub(const Ctx& c) {
 // ---- pieces of the assembly (shared by lin_assemble and the role-split linearization of the 512-thread build)
 // zero the image: S, G, HD (and the side buffer of a second-level relo_Pose)
 UVS_DEV void asm_zero(const Ctx& c) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     { const d2_t z2 = {0.0, 0.0}; for (int i = tid; i < UVS_S_DOUBLES / 2; i += NT) *(d2_t*)(sh + L_S + 2 * i) = z2; }      // ds_write_b128
     if (tid < UVS_RD) { sh[L_G + tid] = 0.0; sh[L_HD + tid] = 0.0; }
     if (h.relo2) for (int t = tid; t < R2_SC; t += NT) c.ws[h.w_relo2 + t] = 0.0;
 }
 // the part-0 group of every pose block adds its rows (one writer per block: a single round)
 UVS_DEV void asm_part0(const Ctx& c, int grp, const GAcc& A) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     if (grp >= 0 && ((grp >> 9) & 15) == 0) {
         const int r0 = GR * (tid % UVS_GLANES);
         const int fa = (grp >> 13) & 15, fb = (grp >> 17) & 15;
@@ -2344,7 +2369,7 @@ UVS_DEV void asm_part0(const Ctx& c, int grp, const GAcc& A) {
 }
 // IMU normal-equation tiles from the registers of lin_imu (even blocks, then odd: consecutive blocks share a diagonal frame block); TWO workgroup barriers
 UVS_DEV void asm_imu(const Ctx& c, const ImuN& N) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     const int lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
     int fis[IMU_SLOTS]; bool act[IMU_SLOTS];
 #pragma unroll
@@ -2392,7 +2417,7 @@ UVS_DEV void asm_imu(const Ctx& c, const ImuN& N) {
 }
 // prior: H0 = J0^T J0 and g = g0 + H0 dx (y = H0 dx came with the cost of this point: prior_quad)
 UVS_DEV void asm_prior(const Ctx& c) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     if (h.prior_n > 0) {
         const int n = h.prior_n;
         const int* cm = c.bi + h.i_prior + 80;
@@ -2421,7 +2446,7 @@ UVS_DEV void asm_prior(const Ctx& c) {
 static constexpr int PA_UN = 8;      // entries per lane held ahead (the 10-frame prior has ~2.6 k structural entries: 6 per lane)
 struct PriorAdd { int idx[PA_UN]; double v[PA_UN]; double hd, g; int cmi; };
 UVS_DEV void asm_prior_load(const Ctx& c, PriorAdd& pa) {
-    const DevWin& h = *c.hdr; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; const int tid = lane_tid();
     pa.hd = 0.0; pa.g = 0.0; pa.cmi = -1;
 #pragma unroll
     for (int u = 0; u < PA_UN; ++u) { pa.idx[u] = -1; pa.v[u] = 0.0; }
@@ -2438,7 +2463,7 @@ UVS_DEV void asm_prior_load(const Ctx& c, PriorAdd& pa) {
     if (tid < n) { pa.cmi = c.bi[h.i_prior + 80 + tid]; pa.g = c.ws[h.w_prior_h0 + UVS_PH_G0(n) + tid]; }
 }
 UVS_DEV void asm_prior_add(const Ctx& c, const PriorAdd& pa) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     if (h.prior_n <= 0) return;
     double cur[PA_UN];
 #pragma unroll
@@ -2456,7 +2481,7 @@ UVS_DEV void asm_prior_add(const Ctx& c, const PriorAdd& pa) {
 }
 // frame damping, Jacobi scaling (first linearization only), dummy pivots, projected-gradient max norm, the linearization's cost -> control words
 UVS_DEV void asm_finish(const Ctx& c, const double* x, bool first, double radius, double cost, double gmax_lm, int mode) {
-    const DevWin& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
+    DevWinK& h = *c.hdr; double* sh = c.sh; const int tid = lane_tid();
     double gmax = gmax_lm;
     if (tid < UVS_RD) {
         const int k = tid & 15;
@@ -2495,7 +2520,7 @@ UVS_DEV void asm_finish(const Ctx& c, const double* x, bool first, double radius
     __syncthreads();
 }
 UVS_DEV void lin_assemble(const Ctx& c, const double* x, bool first, double radius, int grp, const GAcc& Ain, const ImuN& N, double cost, double gmax_lm, int mode = 0) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
     __syncthreads();
@@ -2559,7 +2584,7 @@ UVS_DEV void gacc_load(const Ctx& c, GAcc& A) {
     for (int q = 0; q < GR; ++q) { A.g[q] = W[(6 * GR + q) * UVS_GT]; A.hd[q] = W[(7 * GR + q) * UVS_GT]; }
 }
 UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, const double* line, bool first, double radius, int prep_mode, bool redamp) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const bool ev = role_eval();
     { const double pc = lin_prep(c, x, redamp ? 2 : prep_mode); if (!redamp) lacc_set(c.sh, pc, 0.0); }
     double ic = 0.0;
@@ -2643,7 +2668,7 @@ UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, 
 // `A`: the gather accumulators, owned by the caller (k_solve keeps them in registers between a linearization and a possible re-damping)
 UVS_DEV void linearize(const Ctx& c, const double* x, const double* invd, const double* line, bool first, double radius, int prep_mode, GAcc& A) {
     if (ROLES) { linearize_roles(c, x, invd, line, first, radius, prep_mode, false); return; }
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int grp = gather_group(c);       // this lane's gather group: pose block | flags (uvs_layout.h: i_wblk)
     gacc_zero(A);
     { const double pc = lin_prep(c, x, prep_mode); lacc_set(c.sh, pc, 0.0); }
@@ -2664,7 +2689,7 @@ UVS_DEV void linearize(const Ctx& c, const double* x, const double* invd, const 
 // (L_LCOST / L_LGMAX) still hold their values.
 UVS_DEV void relinearize_damping(const Ctx& c, const double* x, double radius, GAcc& A) {
     if (ROLES) { linearize_roles(c, x, nullptr, nullptr, false, radius, 2, true); return; }
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int grp = gather_group(c);
     (void)lin_prep(c, x, 2);
     {
@@ -2691,15 +2716,16 @@ template <int LNBT = BS_LNB, int PSB = 4, bool STREAM = false>
 // lstep (uvs_debug_step only; nullptr, i.e. no code, everywhere else): the landmark steps themselves, [points | 4 x lines]
 UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* line, double* invd_c, double* line_c,
                                   int pk0, int pk1, int lk0, int lk1, bool with_frames, double* sums_out, double* lstep = nullptr) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
     const double* d = sh + L_DLT;
     double gd = 0.0, dd2 = 0.0, step2 = 0.0, xc2 = 0.0;
-    const bool td_on = h.td_on != 0;
-    const bool ex_on = h.ex_on != 0, relo_on = h.relo_on != 0;
+    const bool td_on = UVS_KPIN(h.td_on) != 0;
+    const bool ex_on = UVS_KPIN(h.ex_on) != 0, relo_on = h.relo_on != 0;
     double* ltrig_c = const_cast<double*>(line_trig_of(c, line_c));
     const bool relo2 = h.relo2 != 0;
+    const int i_pt_fi = UVS_KPIN(h.i_pt_fi), i_pt_fj = UVS_KPIN(h.i_pt_fj), i_ln_fj = UVS_KPIN(h.i_ln_fj), pt_xslots = UVS_KPIN(h.pt_xslots);      // (used inside the landmark loops below)
     if (relo2) relo2_backsub(c);
     else if (relo_on) {      // the step of relo_Pose where an observation of pseudo frame 12 looks for it: d[16 * 12 + a]
         if (tid < 6) sh[L_DLT + 16 * UVS_RELO_FRAME + tid] = d[UVS_EX_INDEX(tid)];
@@ -2748,7 +2774,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
     for (int k = pk0 + tid; k < pk1; k += NT) {
         const int b0 = pbeg[k], b1 = pbeg[k + 1];
         const double* px = c.ws + h.w_pt_x + 4 * (size_t)k;
-        const double* Eg = c.ws + h.w_pt_E + 6 * (size_t)(b0 + h.pt_xslots * k);
+        const double* Eg = c.ws + h.w_pt_E + 6 * (size_t)(b0 + pt_xslots * k);
         double px0 = 0.0, px1 = 0.0, px2 = 0.0, iv0 = 0.0;
         if (STREAM) { px0 = px[0]; px1 = px[1]; px2 = px[2]; iv0 = invd[k]; }
         double t = 0.0;      // Einv . delta_pose  (the landmark's share of the frame step)
@@ -2761,7 +2787,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
 #pragma unroll
                 for (int u = 0; u < PSB; ++u) {
                     const int sl = s0 + u, slc = sl < ns ? sl : 0;
-                    fr[u] = slc == 0 ? c.bi[h.i_pt_fi + b0] : c.bi[h.i_pt_fj + b0 + slc - 1];
+                    fr[u] = slc == 0 ? c.bi[i_pt_fi + b0] : c.bi[i_pt_fj + b0 + slc - 1];
 #pragma unroll
                     for (int a = 0; a < 6; ++a) ev[u][a] = Eg[6 * slc + a];
                 }
@@ -2806,7 +2832,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
 #pragma unroll
                 for (int u = 0; u < QB; ++u) {
                     const int oc = o + u < b1 ? o + u : o;
-                    fr[u] = c.bi[h.i_ln_fj + oc];
+                    fr[u] = c.bi[i_ln_fj + oc];
                     const double* Y = c.ws + h.w_ln_Y + 24 * (size_t)oc + 6 * q;
 #pragma unroll
                     for (int a = 0; a < 6; ++a) yv[u][a] = Y[a];
@@ -2836,7 +2862,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
 #pragma unroll
             for (int u = 0; u < LNB; ++u) {
                 const int oc = o + u < b1 ? o + u : o;
-                fr[u] = c.bi[h.i_ln_fj + oc];
+                fr[u] = c.bi[i_ln_fj + oc];
                 const double* Y = c.ws + h.w_ln_Y + 24 * (size_t)oc;
 #pragma unroll
                 for (int q = 0; q < 24; ++q) yv[u][q] = Y[q];
@@ -2874,7 +2900,7 @@ UVS_DEV void backsub_candidate(const Ctx& c, const double* invd, const double* l
 }
 
 UVS_DEV double ambient_sqnorm(const Ctx& c, const double* x, const double* invd, const double* line) {
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int tid = lane_tid();
     double s = 0.0;
     if (tid < 176) s += x[tid] * x[tid];
@@ -2951,7 +2977,7 @@ UVS_DEV void imu_whiten_block(const double* cov, double* W, double* scr /* LDS, 
 }
 
 UVS_DEV void setup_window(const Ctx& c, double* blob_rw, bool with_prior_image = true, int only_imu_frame = -1) {      // k_evaluate needs the IMU whitening only
-    const DevWin& h = *c.hdr;
+    DevWinK& h = *c.hdr;
     const int tid = lane_tid(), lane = tid & 63, wv = tid >> 6;
     for (int b = wv; b < h.n_imu; b += NW) {
         if (only_imu_frame >= 0 && c.bi[h.i_imu + 2 * b] != only_imu_frame) continue;      // marginalization: the one block that touches the departing frame
@@ -3062,8 +3088,8 @@ UVS_DEV void k_solve_body(char* blobs, const long long* blob_off, double* ws_all
     const int tid = lane_tid(), wdx = blockIdx.x;
     char* blob = blobs + blob_off[wdx];
     Ctx c;
-    c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws_all + ws_off[wdx]; c.sh = sh; c.o = o;
-    const DevWin& h = *c.hdr;
+    c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws_all + ws_off[wdx]; c.sh = sh; c.o = o;
+    DevWinK& h = *c.hdr;
     uvs_report* rep = reports + wdx;
     // ---- init: frames -> LDS, landmark parameters -> workspace buffer 0
     if (tid < UVS_XDIM) sh[L_X + tid] = c.bd[h.d_frames + tid];      // pose[77] sb[99] ex[7] td relo[7]
@@ -3263,8 +3289,8 @@ static constexpr int MARG_OUT = UVS_RD * (UVS_RD + 1) / 2 + UVS_RD + 8;
 UVS_DEV void marg_linearize_body(char* blob, double* ws, KOpts o, double* out, double* sh) {
     const int tid = lane_tid();
     Ctx c;
-    c.hdr = (const DevWin*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
-    const DevWin& h = *c.hdr;
+    c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
+    DevWinK& h = *c.hdr;
     if (tid < UVS_XDIM) sh[L_X + tid] = c.bd[h.d_frames + tid];
     for (int k = tid; k < h.n_points; k += NT) c.ws[h.w_invd0 + k] = c.bd[h.d_invd + k];
     for (int k = tid; k < 4 * h.n_lines; k += NT) c.ws[h.w_line0 + k] = c.bd[h.d_line + k];
