@@ -773,7 +773,7 @@ enum {
 };
 
 typedef struct uvs_ft_item {
-    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width: the slot's NEW image */
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width: the slot's NEW image (raw, if the slot is equalized) */
     int32_t stream;                    /* the slot, 0 .. max_streams - 1; at most once per call */
     int32_t width;                     /* 24 << (levels - 1) .. max_width; fixed by the slot's first image until uvs_ft_reset */
     int32_t height;                    /* 24 << (levels - 1) .. max_height */
@@ -786,7 +786,7 @@ typedef struct uvs_ft_item {
 int uvs_ft_create(int device, int max_streams, int max_width, int max_height, int levels, int max_points, uvs_ft_tracker **out);
 void uvs_ft_destroy(uvs_ft_tracker *ft);
 const char *uvs_ft_last_error(const uvs_ft_tracker *ft);
-/* Empties a slot: its next image may have another size and must come without points. */
+/* Empties a slot: its next image may have another size and must come without points.  Its mask and its equalization are cleared. */
 int uvs_ft_reset(uvs_ft_tracker *ft, int stream);
 /* The outputs are PACKED over the items in order (as window_desc of uvs_kf_extract is): next_xy[][2], status[] (UVS_FT_*), iterations[] (the
  * iterations run at level 0), next_norm[][2] (liftProjective of next_xy through `camera`, the uvs_kf_camera of uvs_kf_extract, for TRACKED
@@ -959,6 +959,58 @@ double uvs_ft_last_reject_device_ms(const uvs_ft_tracker *ft);
  * keep[n_points] and the result as uvs_ft_reject gives them. */
 int uvs_ft_debug_reject(uvs_ft_tracker *ft, const uvs_ft_reject_item *item, double threshold, double confidence, int32_t *samples, double *models,
                         int32_t *counts, uint8_t *keep, uvs_ft_reject_result *result);
+
+/* ---- equalization of the front ends' images (reference feature_tracker/src/feature_tracker.cpp:60-66: cv::createCLAHE(3.0, cv::Size(8, 8))
+ * ->apply(_img, img) under EQUALIZE; line_feature_tracker.cpp:24-31 has it always on) ----
+ * Contrast-limited adaptive histogram equalization of an 8-bit image W x H with clip_limit (FP64, >= 0) and tiles_x x tiles_y tiles (the
+ * reference: 3.0, 8, 8).  uvs_ft_set_equalize switches it on for a slot: uvs_ft_track then takes the item's image as the RAW image, equalizes
+ * it on the device into level 0 of the slot's new pyramid and builds the levels above from that, so that the tracker, uvs_ft_detect and the
+ * next call see the equalized image and nothing else changes.  uvs_ft_equalize equalizes loose images (the line front end's, whose segments the
+ * caller still extracts).  Histograms, clipping and the running sums are integers (exact in any order); the float32 operations are the few
+ * below, each rounded once, in the order written (no fused multiply-add).  An image gives the same bits alone or in a batch, from run to run
+ * and on any machine.  Conventions as above: refl is reflect-101, rint rounds half to even, sat_u8 clamps to 0 .. 255.
+ *   padding     if W % tiles_x == 0 and H % tiles_y == 0: Wp = W, Hp = H.  Otherwise Wp = W + tiles_x - W % tiles_x and Hp = H + tiles_y -
+ *               H % tiles_y: BOTH are padded, and a dimension that did divide gains a FULL extra tiles_x columns (tiles_y rows).  That is
+ *               OpenCV's behaviour (its copyMakeBorder call) and is kept.  The padded image is ext(x, y) = img(refl(x, W), refl(y, H)); it is
+ *               never materialized
+ *   tile        tw = Wp / tiles_x, th = Hp / tiles_y, N = tw th;  lutScale = 255.0f / (float)N (float32);
+ *               clip = 0 if clip_limit == 0, otherwise max((int)(clip_limit N / 256), 1): product and quotient in FP64, then truncated
+ *   per tile    h[0 .. 255] = the histogram of ext over the tile.  If clip > 0: clipped = sum max(h[i] - clip, 0); h[i] = min(h[i], clip);
+ *               batch = clipped / 256, residual = clipped - 256 batch; batch is added to every bin; if residual > 0, step =
+ *               max(256 / residual, 1) and 1 is added to the bins 0, step, 2 step, .. until `residual` of them are done.  The bins still sum
+ *               to N.  lut[i] = sat_u8(rint((float)(h[0] + .. + h[i]) lutScale)): the conversion rounds to nearest even, one float32 multiply
+ *   per pixel   (x, y) of the original W x H:  txf = (float)x (1.0f / (float)tw) - 0.5f;  tx1 = floor(txf), xa = txf - (float)tx1,
+ *               xa1 = 1.0f - xa;  then tx2 = min(tx1 + 1, tiles_x - 1) and tx1 = max(tx1, 0);  the same in y.  With v = img(x, y) and
+ *               L(ty, tx) = (float)lut[ty][tx][v]:
+ *               res = (L(ty1, tx1) xa1 + L(ty1, tx2) xa) ya1 + (L(ty2, tx1) xa1 + L(ty2, tx2) xa) ya;  out = sat_u8(rint(res)).
+ * The numerics are restated in tests/cl_ref.py, which the device is held to bit for bit; DESIGN.md 3.13 has the kernel plan.  OpenCV's own
+ * output could not be compared where this was written.  No CPU path. */
+#define UVS_FT_CLAHE_MAX_TILES 16             /* largest tiles_x and tiles_y */
+
+typedef struct uvs_ft_image {
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width */
+    int32_t width;                     /* 24 .. max_width: the reflection of up to 16 padding pixels always fits */
+    int32_t height;                    /* 24 .. max_height */
+} uvs_ft_image;
+
+/* The equalization state of a slot, like its resident mask: it holds until it is changed or uvs_ft_reset empties the slot (which switches it
+ * off).  tiles_x == 0 switches it off (the other arguments are not looked at).  While it is on, uvs_ft_track and uvs_ft_debug_point take the
+ * item's image as the raw image.  A call that mixes equalized and plain slots gives every item the bits it gives alone; a call without an
+ * equalized slot issues exactly the operations it issued before this existed.
+ * UVS_ERR_INVALID_ARG: a stream outside the handle's slots, clip_limit not finite or outside 0 .. 256, tiles_x or tiles_y outside
+ * 1 .. UVS_FT_CLAHE_MAX_TILES.  A rejected call changes nothing. */
+int uvs_ft_set_equalize(uvs_ft_tracker *ft, int stream, double clip_limit, int tiles_x, int tiles_y);
+/* Stateless: equalizes n_images images (1 .. max_streams) with one setting; it touches no slot.  out receives the images PACKED in order, each
+ * [height][width] with stride = width.
+ * UVS_ERR_INVALID_ARG: null pointer, n_images < 1, a width or height below 24, clip_limit or tiles as above;
+ * UVS_ERR_CAPACITY: n_images, a width or a height above the handle's capacity.  A rejected call changes nothing, and the handle stays usable. */
+int uvs_ft_equalize(uvs_ft_tracker *ft, int n_images, const uvs_ft_image *images, double clip_limit, int tiles_x, int tiles_y, uint8_t *out);
+/* HIP-event time of the last successful uvs_ft_equalize: upload, the kernels, download, on the handle's stream (milliseconds). */
+double uvs_ft_last_equalize_device_ms(const uvs_ft_tracker *ft);
+/* Diagnostic (tests only): ONE image through the same kernels with every intermediate value: bins[tiles_y][tiles_x][256] (after clipping and
+ * redistribution), luts[tiles_y][tiles_x][256], out[height][width] and info[4] = {Wp, Hp, N, clip}. */
+int uvs_ft_debug_equalize(uvs_ft_tracker *ft, const uvs_ft_image *image, double clip_limit, int tiles_x, int tiles_y, int32_t *bins,
+                          uint8_t *luts, uint8_t *out, int32_t *info);
 
 #ifdef __cplusplus
 }

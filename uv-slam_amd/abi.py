@@ -720,3 +720,23 @@ def ft_reject_items(items):
         arr[b].prev_norm = prev.ctypes.data_as(c_double_p) if len(prev) else None
         arr[b].next_norm = nxt.ctypes.data_as(c_double_p) if len(nxt) else None
     return arr, keep
+
+
+# ---- equalization of the front ends' images (uvs_ft_set_equalize, uvs_ft_equalize, include/uvs_solver.h) ------------------
+FT_CLAHE_MAX_TILES = 16
+
+
+class FtImage(C.Structure):
+    _fields_ = [("image", c_u8_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+def ft_images(images):
+    """(FtImage array, keepalive) from [H, W] uint8 arrays."""
+    arr = (FtImage * max(len(images), 1))()
+    keep = []
+    for b, im in enumerate(images):
+        im = np.ascontiguousarray(im, dtype=np.uint8)
+        keep.append(im)
+        arr[b].image = im.ctypes.data_as(c_u8_p)
+        arr[b].height, arr[b].width = im.shape
+    return arr, keep

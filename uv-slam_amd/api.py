@@ -26,6 +26,7 @@ EXPORTS = [
     "uvs_ft_create", "uvs_ft_destroy", "uvs_ft_last_error", "uvs_ft_reset", "uvs_ft_track", "uvs_ft_last_device_ms", "uvs_ft_debug_pyramid", "uvs_ft_debug_point",
     "uvs_ft_set_max_candidates", "uvs_ft_set_mask", "uvs_ft_detect", "uvs_ft_last_detect_device_ms", "uvs_ft_debug_detect",
     "uvs_ft_reject", "uvs_ft_last_reject_device_ms", "uvs_ft_debug_reject",
+    "uvs_ft_set_equalize", "uvs_ft_equalize", "uvs_ft_last_equalize_device_ms", "uvs_ft_debug_equalize",
 ]
 
 
@@ -145,6 +146,11 @@ def lib():
         L.uvs_ft_debug_reject.argtypes = [C.c_void_p, C.POINTER(abi.FtRejectItem), C.c_double, C.c_double, abi.c_i32_p, abi.c_double_p, abi.c_i32_p,
                                           abi.c_u8_p, C.POINTER(abi.FtRejectResult)]
         L.uvs_ft_debug_reject.restype = C.c_int
+        L.uvs_ft_set_equalize.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]; L.uvs_ft_set_equalize.restype = C.c_int
+        L.uvs_ft_equalize.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.FtImage), C.c_double, C.c_int, C.c_int, abi.c_u8_p]; L.uvs_ft_equalize.restype = C.c_int
+        L.uvs_ft_last_equalize_device_ms.argtypes = [C.c_void_p]; L.uvs_ft_last_equalize_device_ms.restype = C.c_double
+        L.uvs_ft_debug_equalize.argtypes = [C.c_void_p, C.POINTER(abi.FtImage), C.c_double, C.c_int, C.c_int, abi.c_i32_p, abi.c_u8_p, abi.c_u8_p, abi.c_i32_p]
+        L.uvs_ft_debug_equalize.restype = C.c_int
         _lib = L
     return _lib
 
@@ -936,3 +942,56 @@ class FeatureTracker(_Handle):
         out = self._reject_dict(res, keep[:n])
         out.update(samples=smp, models=mod, counts=cnt)
         return out
+
+    # ---- equalization: CLAHE of a slot's raw images (uvs_ft_set_equalize) and of loose images (uvs_ft_equalize)
+    def set_equalize_raw(self, stream, clip_limit=3.0, tiles_x=8, tiles_y=8):
+        return lib().uvs_ft_set_equalize(self._h, int(stream), float(clip_limit), int(tiles_x), int(tiles_y))
+
+    def set_equalize(self, stream, clip_limit=3.0, tiles_x=8, tiles_y=None):
+        """Switches the equalization of a slot on: track() then takes the slot's images raw.  tiles_x = 0 switches it off; reset() does too."""
+        rc = self.set_equalize_raw(stream, clip_limit, tiles_x, tiles_x if tiles_y is None else tiles_y)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_set_equalize", rc)
+
+    def equalize_raw(self, images, clip_limit=3.0, tiles_x=8, tiles_y=8, n_images=None, null=()):
+        """-> (return code, [equalized image]) without raising: for the tests of the argument checks.  n_images overrides the count passed; `null`
+        names arguments passed as NULL ("images", "out")."""
+        arr, keep = abi.ft_images(images)
+        out = np.zeros(max(sum(im.size for im in keep), 1), np.uint8)
+        args = dict(images=C.cast(arr, C.POINTER(abi.FtImage)), out=out.ctypes.data_as(abi.c_u8_p))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_ft_equalize(self._h, len(images) if n_images is None else int(n_images), args["images"], float(clip_limit), int(tiles_x),
+                                   int(tiles_y), args["out"])
+        self.last_equalize_ms = (time.perf_counter() - t0) * 1e3
+        if rc != abi.UVS_OK:
+            return rc, []
+        res, o = [], 0
+        for im in keep:
+            res.append(out[o:o + im.size].reshape(im.shape).copy()); o += im.size
+        return rc, res
+
+    def equalize(self, images, clip_limit=3.0, tiles_x=8, tiles_y=None):
+        """images: list of [H, W] uint8 (at most max_streams) -> the equalized images.  Stateless: no slot is touched."""
+        rc, out = self.equalize_raw(images, clip_limit, tiles_x, tiles_x if tiles_y is None else tiles_y)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_equalize", rc)
+        return out
+
+    def last_equalize_device_ms(self):
+        return float(lib().uvs_ft_last_equalize_device_ms(self._h))
+
+    def debug_equalize(self, image, clip_limit=3.0, tiles_x=8, tiles_y=None):
+        """ONE image (tests only) -> dict(out [H, W] uint8, bins [tiles_y, tiles_x, 256] int32, luts [tiles_y, tiles_x, 256] uint8, info int32
+        (Wp, Hp, N, clip))."""
+        tiles_y = tiles_x if tiles_y is None else tiles_y
+        arr, keep = abi.ft_images([image])
+        n = max(int(tiles_x) * int(tiles_y), 1)
+        bins = np.zeros((n, 256), np.int32); luts = np.zeros((n, 256), np.uint8); out = np.zeros(keep[0].shape, np.uint8); info = np.zeros(4, np.int32)
+        rc = lib().uvs_ft_debug_equalize(self._h, C.cast(arr, C.POINTER(abi.FtImage)), float(clip_limit), int(tiles_x), int(tiles_y),
+                                         bins.ctypes.data_as(abi.c_i32_p), luts.ctypes.data_as(abi.c_u8_p), out.ctypes.data_as(abi.c_u8_p),
+                                         info.ctypes.data_as(abi.c_i32_p))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_debug_equalize", rc)
+        return dict(out=out, bins=bins.reshape(tiles_y, tiles_x, 256), luts=luts.reshape(tiles_y, tiles_x, 256), info=info)

@@ -16,6 +16,8 @@
 //                  accumulates (J - I) Dx and (J - I) Dy per lane and reduces them across the wave in 64 bits by a butterfly of shuffles, which
 //                  leaves the totals in every lane; every lane then does the same FP64 step, so the loop's branches are wave-uniform.
 //                  Lane 0 writes the point's outputs, its liftProjective (uvs_camera_lift.h) and, for uvs_ft_debug_point, the trace.
+// The item of a slot that uvs_ft_set_equalize has switched on brings a raw image: it is not copied into level 0 but handed to
+// uvsft::equalize_enqueue (uvs_feature_equalize.hip), which writes level 0 on the same stream before k_ft_pyramid runs.
 // No kernel uses scratch (build() checks it), none indexes a register array at run time, and no atomic is used.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -292,6 +294,7 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
     int* h_pi = reinterpret_cast<int*>(h->h_in + o_pi);
     size_t po = 0;
     int top_w[kMaxLevels] = {0, 0, 0, 0}, top_h[kMaxLevels] = {0, 0, 0, 0};
+    std::vector<EqJob> eq_jobs;                               // the items of equalized slots (uvs_ft_set_equalize); empty: the call is what it was without them
     for (int i = 0; i < n_items; ++i) {
         const uvs_ft_item& it = items[i];
         const uvs_ft_tracker::Slot& s = h->slots[it.stream];
@@ -307,10 +310,14 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
         hf[i] = d;
         for (int k = 0; k < it.n_points; ++k) h_pi[po + k] = i;
         if (it.n_points) std::memcpy(h->h_in + o_pts + po * 16, it.points_xy, (size_t)it.n_points * 16);
+        po += it.n_points;
+        if (s.equalize) {                                     // the image is raw: uvs_feature_equalize.hip stages it and writes level 0
+            eq_jobs.push_back(EqJob{it.image, it.width, it.height, s.eq_clip, s.eq_tiles_x, s.eq_tiles_y, h->d_pyr + d.new_off[0], d.pitch[0]});
+            continue;
+        }
         char* dst = h->h_in + h->in_meta + (size_t)i * h->img_slot;
         if (d.pitch[0] == d.W[0]) std::memcpy(dst, it.image, (size_t)d.W[0] * d.H[0]);
         else for (int y = 0; y < d.H[0]; ++y) { std::memcpy(dst + (size_t)y * d.pitch[0], it.image + (size_t)y * d.W[0], d.W[0]); }
-        po += it.n_points;
     }
     const FtOutLayout L = out_layout(total);
     const FtItem* dF = reinterpret_cast<const FtItem*>(h->d_in.get());
@@ -326,9 +333,12 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
     UVS_HIP(h->err, hipSetDevice(h->device));
     UVS_HIP(h->err, hipEventRecord(h->ev0, st));
     UVS_HIP(h->err, hipMemcpyAsync(h->d_in, h->h_in, meta, hipMemcpyHostToDevice, st));
-    for (int i = 0; i < n_items; ++i)                         // level 0 of the new pyramid is the repacked image
-        UVS_HIP(h->err, hipMemcpyAsync(h->d_pyr + hf[i].new_off[0], h->h_in + h->in_meta + (size_t)i * h->img_slot, (size_t)hf[i].pitch[0] * hf[i].H[0],
-                                       hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n_items; ++i)                         // level 0 of the new pyramid is the repacked image ...
+        if (!h->slots[items[i].stream].equalize)
+            UVS_HIP(h->err, hipMemcpyAsync(h->d_pyr + hf[i].new_off[0], h->h_in + h->in_meta + (size_t)i * h->img_slot, (size_t)hf[i].pitch[0] * hf[i].H[0],
+                                           hipMemcpyHostToDevice, st));
+    if (!eq_jobs.empty())                                     // ... or, of an equalized slot, the raw image through CLAHE
+        if (const int rc = equalize_enqueue(h, (int)eq_jobs.size(), eq_jobs.data(), nullptr)) return rc;
     for (int l = 1; l < h->levels; ++l)
         k_ft_pyramid<<<dim3((top_w[l] + kPyrTW - 1) / kPyrTW, (top_h[l] + kPyrTH - 1) / kPyrTH, n_items), kThreads, 0, st>>>(dF, h->d_pyr, l);
     if (total) {

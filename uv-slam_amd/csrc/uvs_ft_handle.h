@@ -1,7 +1,8 @@
-// uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the three units of the point front end: csrc/uvs_feature_track.hip (creates
-// and destroys it, builds the pyramids, tracks), csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid) and
-// csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot).  Device, stream, events and error
-// text are the base's (uvs_handle.h, which also has align_up, pitch_of, the arena and the camera check the three units use).  Host only.
+// uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the four units of the point front end: csrc/uvs_feature_track.hip (creates
+// and destroys it, builds the pyramids, tracks), csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid),
+// csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot) and csrc/uvs_feature_equalize.hip (CLAHE:
+// of an equalized slot's raw image into level 0 of its new pyramid, on the tracking unit's behalf, and of loose images).  Device, stream, events
+// and error text are the base's (uvs_handle.h, which also has align_up, pitch_of, the arena and the camera check the units use).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -13,8 +14,12 @@
 #include "uvs_handle.h"
 
 struct uvs_ft_tracker : UvsHandle {
-    // cur: which of the slot's two pyramids is the stored one; has_mask: the slot's part of d_mask holds a mask (uvs_ft_set_mask)
-    struct Slot { int W = 0, H = 0, cur = 0; bool holds = false, has_mask = false; };
+    // cur: which of the slot's two pyramids is the stored one; has_mask: the slot's part of d_mask holds a mask (uvs_ft_set_mask);
+    // equalize: the slot's images come raw and are equalized on the device with eq_* (uvs_ft_set_equalize).  uvs_ft_reset clears all of it
+    struct Slot {
+        int W = 0, H = 0, cur = 0; bool holds = false, has_mask = false;
+        bool equalize = false; double eq_clip = 0.0; int eq_tiles_x = 0, eq_tiles_y = 0;
+    };
     int max_streams = 0, max_width = 0, max_height = 0, levels = 0, max_points = 0;
     int max_candidates = UVS_FT_DEFAULT_CANDIDATES;      // uvs_ft_set_max_candidates
     float device_ms = 0.f, detect_ms = 0.f;     // uvs_ft_last_device_ms, uvs_ft_last_detect_device_ms
@@ -33,6 +38,13 @@ struct uvs_ft_tracker : UvsHandle {
     DevBuf<char> d_rej;                         // one call's item table and points, results and keep masks, and the debug arrays
     PinnedBuf<char> h_rej_in, h_rej_out;        // pinned staging of uvs_ft_reject
     float reject_ms = 0.f;                      // uvs_ft_last_reject_device_ms
+    // equalization (uvs_feature_equalize.hip): allocated by the first call that needs them
+    PinnedBuf<char> h_eq_in;                    // one call's job descriptors, then the raw images, each repacked to pitch_of rows
+    DevBuf<char> d_eq_in;                       // ... on the device: the staging the kernels read
+    DevBuf<uint8_t> d_eq_lut;                   // [job][tiles_y * tiles_x][256] LUTs of one call
+    DevBuf<char> d_eq_out;                      // uvs_ft_equalize: the equalized images (pitch_of rows), then the debug call's bins
+    PinnedBuf<char> h_eq_out;
+    float equalize_ms = 0.f;                    // uvs_ft_last_equalize_device_ms
 };
 
 namespace uvsft {
@@ -48,6 +60,27 @@ inline size_t pyramid_layout(int width, int height, int levels, int* W, int* H, 
         } else { W[l] = H[l] = P[l] = 0; off[l] = 0; }
     }
     return bytes;
+}
+
+// ---- equalization: what uvs_feature_track.hip needs of uvs_feature_equalize.hip
+// one image to equalize: the raw image on the host (stride = width) and where the result goes on the device (rows of dst_pitch bytes, dst and
+// dst_pitch multiples of 4)
+struct EqJob {
+    const uint8_t* image; int width, height;
+    double clip_limit; int tiles_x, tiles_y;
+    uint8_t* dst; int dst_pitch;
+};
+
+// uploads the jobs' images in one copy and launches k_ft_clahe_lut and k_ft_clahe_apply on the handle's stream, without waiting; the caller has
+// checked the arguments and set the device.  dbg_bins_dev: device memory for the bins of job 0 (uvs_ft_debug_equalize), or null
+int equalize_enqueue(uvs_ft_tracker* h, int n, const EqJob* jobs, int32_t* dbg_bins_dev);
+
+inline int check_equalize(double clip_limit, int tiles_x, int tiles_y, const std::string& fn, std::string& err) {
+    if (!std::isfinite(clip_limit) || clip_limit < 0.0 || clip_limit > 256.0) { err = fn + ": clip_limit must be finite and in 0 .. 256"; return UVS_ERR_INVALID_ARG; }
+    if (tiles_x < 1 || tiles_x > UVS_FT_CLAHE_MAX_TILES || tiles_y < 1 || tiles_y > UVS_FT_CLAHE_MAX_TILES) {
+        err = fn + ": tiles_x and tiles_y must be 1 .. UVS_FT_CLAHE_MAX_TILES"; return UVS_ERR_INVALID_ARG;
+    }
+    return UVS_OK;
 }
 
 }  // namespace uvsft

@@ -5,8 +5,8 @@
 // csrc/uvs_feature_detect.hip); what is here is the bookkeeping around them.  Differences from the reference, all from the C ABI below:
 // positions are FP64 (cv::Point2f there), setMask orders with a stable sort and keeps no image (the occupied points go to uvs_ft_detect, whose
 // disc is Euclidean), rejectWithF works on the normalized points with F_THRESHOLD / FOCAL_LENGTH (the same test as on the reference's virtual
-// image) and is off unless f_threshold > 0, CLAHE is not here, and n_id is a member, not a static, so that two trackers of one process number
-// their points apart.  With max_cnt = 0 (the default) new points are the caller's, through a Detector.
+// image) and is off unless f_threshold > 0, CLAHE (EQUALIZE, :60-66) runs on the device inside uvs_ft_track when `equalize` is set, and n_id is
+// a member, not a static, so that two trackers of one process number their points apart.  With max_cnt = 0 (the default) new points are the caller's, through a Detector.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -140,6 +140,18 @@ public:
         prev_un_pts_map = cur_un_pts_map;
     }
 
+    // :60-66, EQUALIZE.  The setting lives on the device, in the tracker's slot (uvs_ft_set_equalize), and is sent when it differs from what the
+    // slot was last told; a fresh slot, and a slot after a reset, is plain.  FeatureTracker::readImage asks equalizePending() before every frame.
+    bool equalizePending() const {
+        if (!eq_told_) return equalize;
+        return told_equalize_ != equalize || (equalize && (told_clip_ != clahe_clip || told_tiles_ != clahe_tiles));
+    }
+    void equalizeTold() { eq_told_ = true; told_equalize_ = equalize; told_clip_ = clahe_clip; told_tiles_ = clahe_tiles; }
+    void equalizeForgotten() { eq_told_ = false; }      // the slot was reset
+
+    bool equalize = false;            // EQUALIZE: readImage's images are raw and go through CLAHE on the device
+    double clahe_clip = 3.0;          // cv::createCLAHE(3.0, cv::Size(8, 8))
+    int clahe_tiles = 8;
     std::vector<Point2d> n_pts, prev_pts, cur_pts, forw_pts, prev_un_pts, cur_un_pts, pts_velocity;
     std::vector<int> ids, track_cnt;
     std::map<int, Point2d> cur_un_pts_map, prev_un_pts_map;
@@ -150,6 +162,11 @@ protected:
     uvs_kf_camera camera_;
     UvsLiftCam lift_;
     std::vector<Point2d> forw_norm_;
+
+private:
+    bool eq_told_ = false, told_equalize_ = false;      // what the slot was last told
+    double told_clip_ = 0.0;
+    int told_tiles_ = 0;
 };
 
 class FeatureTracker : public FeatureTrackerBook {
@@ -174,13 +191,15 @@ public:
         mask_w_ = width; mask_h_ = height; mask_pending_ = true;
     }
 
-    // :54-147 with PUB_THIS_FRAME set.  image: [height][width] grey levels (after CLAHE, if the caller wants it).  Returns UVS_OK or the error
+    // :54-147 with PUB_THIS_FRAME set.  image: [height][width] grey levels, the raw frame as in the reference: with `equalize` set the device
+    // runs CLAHE (clahe_clip, clahe_tiles x clahe_tiles) on it before anything else sees it (:60-66).  Returns UVS_OK or the error
     // of uvs_ft_track (its text in last_error; the vectors are unchanged then).  Without a Detector and with max_cnt > 0 the frame goes on as
     // :109-139 does: setMask, uvs_ft_detect of max_cnt - forw_pts.size() points with the kept points occupied, addPoints; an error of the
     // detection is returned after the frame has been finished without new points.  With f_threshold > 0 rejectWithF (:111) runs between the
     // flow and setMask / the Detector, on frames that carry at least 8 tracks; an error of it is returned after the frame has been finished
     // with every track kept.
     int readImage(const uint8_t* image, int width, int height, double time, const Detector& detect = nullptr) {
+        if (const int rc = pushEqualize()) return rc;
         const size_t n = cur_pts.size();
         xy_.resize(2 * n + 2); nxt_.resize(2 * n + 2); nrm_.resize(2 * n + 2); st_.resize(n + 1); it_.resize(n + 1);
         for (size_t i = 0; i < n; ++i) { xy_[2 * i] = cur_pts[i].x; xy_[2 * i + 1] = cur_pts[i].y; }
@@ -215,7 +234,28 @@ public:
     uvs_ft_reject_result last_reject = {};      // of the last frame that ran rejectWithF
     std::string last_error;
 
+    // empties the device slot (the next image may have another size; it must find no points here, so the vectors are emptied too); the slot's
+    // equalization and mask are cleared with it and pushed again by the next frame
+    int reset() {
+        const int rc = uvs_ft_reset(ft_, 0);
+        if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
+        prev_pts.clear(); cur_pts.clear(); forw_pts.clear(); prev_un_pts.clear(); cur_un_pts.clear(); pts_velocity.clear(); ids.clear(); track_cnt.clear();
+        forw_norm_.clear();
+        equalizeForgotten();
+        if (!image_mask_.empty()) mask_pending_ = true;
+        return UVS_OK;
+    }
+
 private:
+    // the equalization setting to the slot when it changed or the slot was reset (the way mask_pending_ works for the mask)
+    int pushEqualize() {
+        if (!equalizePending()) return UVS_OK;
+        const int rc = uvs_ft_set_equalize(ft_, 0, clahe_clip, equalize ? clahe_tiles : 0, equalize ? clahe_tiles : 0);
+        if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
+        equalizeTold();
+        return UVS_OK;
+    }
+
     // :149-182: cur_un_pts and the device's normalized forward points through uvs_ft_reject, then the reduceVector calls
     int rejectWithF() {
         const size_t n = forw_pts.size();

@@ -6,6 +6,7 @@
 // Detector, and uvs_host_ft_apply_set_mask a frame of the bookkeeping with setMask between the flow and addPoints.
 // uvs_host_ft_set_rejection turns rejectWithF on (f_threshold > 0) for the frames that follow, and uvs_host_ft_apply_reject is a frame of the
 // bookkeeping with a given keep mask between the flow and addPoints.
+// uvs_host_ft_set_equalize sets EQUALIZE and its CLAHE parameters for the frames that follow; uvs_host_ft_reset empties the tracker.
 #include <cstdio>
 #include <memory>
 #include "feature_tracker.h"
@@ -136,6 +137,36 @@ int uvs_host_ft_apply_reject(void* hv, double time, int n, const double* next_xy
     b.addPoints();
     b.rotate();
     return ok ? UVS_OK : UVS_ERR_INVALID_ARG;
+}
+
+// EQUALIZE: the frames that follow are raw and go through CLAHE on the device (clip, tiles x tiles); equalize = 0: off.  Any handle: on one
+// without a device only the bookkeeping of the setting runs (uvs_host_ft_equalize_pending, _told, _forgotten)
+int uvs_host_ft_set_equalize(void* hv, int equalize, double clip, int tiles) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h) return UVS_ERR_INVALID_ARG;
+    h->b().equalize = equalize != 0; h->b().clahe_clip = clip; h->b().clahe_tiles = tiles;
+    return UVS_OK;
+}
+
+// 1 when readImage would send the setting to the slot before its next frame, 0 when the slot has it
+int uvs_host_ft_equalize_pending(void* hv) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    return h ? (h->b().equalizePending() ? 1 : 0) : -1;
+}
+
+// what readImage does after it sent the setting (told != 0), and what reset does (told == 0), by hand
+int uvs_host_ft_equalize_told(void* hv, int told) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h) return UVS_ERR_INVALID_ARG;
+    if (told) h->b().equalizeTold(); else h->b().equalizeForgotten();
+    return UVS_OK;
+}
+
+// empties a device handle's slot and its vectors (uvs::FeatureTracker::reset)
+int uvs_host_ft_reset(void* hv) {
+    HostFt* h = static_cast<HostFt*>(hv);
+    if (!h || !h->dev) return UVS_ERR_INVALID_ARG;
+    return h->dev->reset();
 }
 
 // updateID(i) for i = 0, 1, .. as the node does after readImage (feature_tracker_node.cpp); returns the number of points
