@@ -1012,6 +1012,109 @@ double uvs_ft_last_equalize_device_ms(const uvs_ft_tracker *ft);
 int uvs_ft_debug_equalize(uvs_ft_tracker *ft, const uvs_ft_image *image, double clip_limit, int tiles_x, int tiles_y, int32_t *bins,
                           uint8_t *luts, uint8_t *out, int32_t *info);
 
+/* ---- line tracking of the line front end (reference feature_tracker/src/line_feature_tracker.cpp: lineExtraction's lineBiDes->compute,
+ * lineMatching, and the matches that readImage4Line :351-433 turns into ids) ----
+ * A handle is a line tracker with max_streams slots.  The caller detects the segments of a frame (ELSED is a sequential edge walk and stays
+ * the caller's) and passes them with the image they were found in.  One call takes a batch of items, at most one per slot: it computes one
+ * 256-bit LBD descriptor per segment, matches the slot's previous lines (the queries) against the new ones (the train set), and makes the new
+ * lines the slot's previous ones: descriptors and gate points stay resident on the device.  A slot that holds nothing (fresh, after
+ * uvs_lt_reset, or after a frame without lines) matches nothing.  An item gives the same bits alone or in a batch, from run to run and on any
+ * machine: positions, projections and row sums are integers (exact in any order), and the FP64 operations are the few below, each rounded
+ * once, in the order written (no fused multiply-add).
+ *
+ * The rule is this project's own statement of LBD with the default parameters of OpenCV's BinaryDescriptor (9 bands of width 7, one octave);
+ * OpenCV's own descriptors could not be compared where this was written.  Two deliberate deviations, both for order-independence and bit
+ * equality: sample positions and gradient projections are fixed-point (Q10) where OpenCV keeps float32 running sums, and the direction comes
+ * from dx / len, dy / len, not from cos / sin(atan2).  Conventions as above: refl, rint, >> arithmetic; (int) truncates towards zero.
+ *   segment     (sx, sy, ex, ey); if sx > ex the ends are swapped (a tie keeps them).  dx = ex - sx, dy = ey - sy, len = sqrt(dx dx + dy dy),
+ *               L = (int)len.  Status UVS_LT_SHORT if L < 2, UVS_LT_LONG if L > max_length: the descriptor is all zero, the line is never
+ *               matched, and cq = sq = halfWidth = 0; otherwise UVS_LT_OK and cq = rint(1024 dx / len), sq = rint(1024 dy / len),
+ *               halfWidth = (L - 1) / 2.  MX = rint(512 (sx + ex)), MY = rint(512 (sy + ey)).  The gate points are ((int)sx, (int)sy) and
+ *               ((int)ex, (int)ey) of the ordered ends (the reference stores the truncated values, and getStartPoint() returns them)
+ *   gradient    the Sobel gx, gy of uvs_ft_detect's rule over the item's image W x H, reflect-101, |g| <= 1020
+ *   support     63 rows h, L columns w:  X = MX + (w - halfWidth) cq - (h - 31) sq,  Y = MY + (w - halfWidth) sq + (h - 31) cq  (int32);
+ *               the pixel is x = clamp((X + 512) >> 10, 0, W - 1), y = clamp((Y + 512) >> 10, 0, H - 1)
+ *   projections gDL = gx cq + gy sq,  gDO = -gx sq + gy cq  (int32, |.| < 1.5e6)
+ *   row sums    S[h][0] = sum_w max(gDL, 0), S[h][1] = sum_w max(-gDL, 0), S[h][2] = sum_w max(gDO, 0), S[h][3] = sum_w max(-gDO, 0): 64-bit
+ *               integers (below 2^32 for L <= 2048)
+ *   tables      G[h] = exp(-(h - 31)^2 / (2 31^2)), h = 0 .. 62;  Lc[i] = exp(-(i - 10)^2 / (2 7^2)), i = 0 .. 20 (the local sigma is OpenCV's
+ *               integer (2 7 + 1) / 2 = 7); computed once on the host with exp in FP64 (uvs_lt_gauss_tables)
+ *   bands       for h = 0 .. 62 ascending and each k: r = G[h] (double)S[h][k], r2 = r r, b = h / 7, j = h % 7;
+ *               BS[b][k] += Lc[7 + j] r, B2[b][k] += (Lc[7 + j] Lc[7 + j]) r2; if b >= 1 the same into band b - 1 with Lc[14 + j]; if b <= 7 the
+ *               same into band b + 1 with Lc[j].  (An accumulator of band b so receives the rows 7 (b - 1) .. 7 (b + 1) + 6 that exist,
+ *               ascending, row h with Lc[h - 7 b + 7].)  inv = 1.0 / 14 for the bands 0 and 8, 1.0 / 21 otherwise;  m = BS inv,
+ *               sd = sqrt(max(B2 inv - m m, 0));  d[8 b + 2 k] = m, d[8 b + 2 k + 1] = sd
+ *   normalise   tm = sum m^2, ts = sum sd^2, each from 0 with b ascending and k ascending within it.  If tm > 0 every m is multiplied by
+ *               1 / sqrt(tm); likewise sd with ts.  Every entry above 0.4 becomes 0.4.  desc_float = d (1 / sqrt(sum d^2)), the sum from 0 in
+ *               index order; all zero if the sum is 0
+ *   bits        byte p = 0 .. 31 takes the p-th pair (a, b) of the lexicographic list (0, 1), (0, 2), .., (0, 8), (1, 2), ..; its bit 7 - i is
+ *               d[8 a + i] > d[8 b + i] on the clamped values (the final scale changes no comparison; a tie gives 0)
+ *   match       for each previous line q with status OK, t* is the OK current line with the smallest Hamming distance, ties to the lowest
+ *               t.  The match is dropped iff the squared distance of the start gate points, or of the end gate points, is > 900 (integers:
+ *               exactly 30 px apart passes).  match_of_prev[q] = t* or -1; distance[q] = the Hamming distance to t*, dropped or not, or -1
+ *               if q is not OK or there is no OK current line;  prev_of_cur[t] = the LARGEST accepted q that chose t, else -1 (the
+ *               reference walks the matches in query order and overwrites).
+ * The numerics are restated in tests/lt_ref.py, which the device is held to bit for bit; DESIGN.md 3.14 has the kernel plan.  No CPU path:
+ * uvs_lt_create fails with UVS_ERR_NO_DEVICE without a GPU (uvs_lt_gauss_tables needs none). */
+#define UVS_LT_MAX_STREAMS 64                 /* largest max_streams uvs_lt_create takes */
+#define UVS_LT_MAX_LINES 1024                 /* largest max_lines (segments of one item) = UVS_VP_MAX_LINES */
+#define UVS_LT_MAX_LENGTH 2048                /* largest max_length (L of a described segment) */
+#define UVS_LT_MIN_SIZE 8                     /* smallest width and height of an image */
+#define UVS_LT_ROWS 63                        /* rows of the support region: 9 bands of width 7 */
+#define UVS_LT_DESC_FLOATS 72                 /* desc_float: (mean, deviation) of 4 sums in 9 bands */
+#define UVS_LT_DESC_BYTES 32
+#define UVS_LT_GATE2 900                      /* squared gate of lineMatching: 30 px */
+typedef struct uvs_lt_tracker uvs_lt_tracker;      /* opaque: the slots' previous lines, device buffers, pinned staging, stream */
+
+enum { UVS_LT_OK = 0, UVS_LT_SHORT = 1, UVS_LT_LONG = 2 };
+
+typedef struct uvs_lt_item {
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width: the (undistorted) image of the segments */
+    int32_t stream;                    /* the slot, 0 .. max_streams - 1; at most once per call */
+    int32_t width;                     /* UVS_LT_MIN_SIZE .. max_width; it may differ from the slot's last frame */
+    int32_t height;                    /* UVS_LT_MIN_SIZE .. max_height */
+    int32_t n_lines;                   /* 0 .. max_lines; 0 empties the slot's previous set */
+    const double *segments;            /* [n_lines][4]: sx, sy, ex, ey in pixels, finite and within UVS_KF_MAX_COORD; they may leave the image */
+} uvs_lt_item;
+
+typedef struct uvs_lt_result {
+    int32_t n_described;               /* lines of the item with status UVS_LT_OK */
+    int32_t n_matched;                 /* previous lines of the slot with an accepted match */
+    int32_t status;                    /* 0 */
+} uvs_lt_result;
+
+/* UVS_ERR_INVALID_ARG: null out, a capacity < 1, max_width or max_height below UVS_LT_MIN_SIZE, max_length < 2;
+ * UVS_ERR_CAPACITY: max_streams > UVS_LT_MAX_STREAMS, max_width > UVS_KF_MAX_WIDTH, max_height > UVS_KF_MAX_HEIGHT, max_lines >
+ * UVS_LT_MAX_LINES, max_length > UVS_LT_MAX_LENGTH. */
+int uvs_lt_create(int device, int max_streams, int max_width, int max_height, int max_lines, int max_length, uvs_lt_tracker **out);
+void uvs_lt_destroy(uvs_lt_tracker *lt);
+const char *uvs_lt_last_error(const uvs_lt_tracker *lt);
+/* Empties a slot: its next frame matches nothing. */
+int uvs_lt_reset(uvs_lt_tracker *lt, int stream);
+/* The outputs are PACKED over the items' lines in order: desc[][32], line_status[] (UVS_LT_*), prev_index[] (prev_of_cur: the index, in the
+ * slot's previous frame, of the line this one continues, or -1) and distance[] (the Hamming distance of that match, or -1);
+ * results[n_items].
+ * UVS_ERR_INVALID_ARG: null pointer, n_items < 1, a negative count, a null array behind a positive count, a null image, a stream outside the
+ * handle's slots or given twice, a width or height below UVS_LT_MIN_SIZE, a coordinate that is not finite or beyond UVS_KF_MAX_COORD;
+ * UVS_ERR_CAPACITY: n_items, a width, a height or n_lines above the handle's capacity.  A rejected call changes no slot, and the handle stays
+ * usable after it. */
+int uvs_lt_track(uvs_lt_tracker *lt, int n_items, const uvs_lt_item *items, uint8_t *desc, int32_t *line_status, int32_t *prev_index,
+                 int32_t *distance, uvs_lt_result *results);
+/* Stateless: the match kernel on the caller's descriptors prev_desc[n_prev][32], cur_desc[n_cur][32] and gate points prev_ends[n_prev][4],
+ * cur_ends[n_cur][4] (int32: start x, y, end x, y); every line counts as UVS_LT_OK.  match_of_prev[n_prev], distance[n_prev],
+ * prev_of_cur[n_cur].  It touches no slot.
+ * UVS_ERR_INVALID_ARG: null pointer behind a positive count, a negative count; UVS_ERR_CAPACITY: n_prev or n_cur above max_lines. */
+int uvs_lt_match(uvs_lt_tracker *lt, int n_prev, const uint8_t *prev_desc, const int32_t *prev_ends, int n_cur, const uint8_t *cur_desc,
+                 const int32_t *cur_ends, int32_t *match_of_prev, int32_t *distance, int32_t *prev_of_cur);
+/* HIP-event time of the last successful uvs_lt_track: upload, the kernels, download, on the handle's stream (milliseconds). */
+double uvs_lt_last_device_ms(const uvs_lt_tracker *lt);
+/* Diagnostic (tests only): ONE segment[4] of ONE image through the same kernels, with every intermediate value:
+ * geom[8] = {L, cq, sq, MX, MY, halfWidth, status, 0}, row_sums[63][4], desc_float[72], desc[32].  It touches no slot. */
+int uvs_lt_debug_line(uvs_lt_tracker *lt, const uint8_t *image, int width, int height, const double *segment, int32_t *geom,
+                      int64_t *row_sums, double *desc_float, uint8_t *desc);
+/* Host only, no GPU needed: the two coefficient tables a handle uploads, G[63] and Lc[21]. */
+void uvs_lt_gauss_tables(double *G, double *Lc);
+
 #ifdef __cplusplus
 }
 #endif

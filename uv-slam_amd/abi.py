@@ -740,3 +740,41 @@ def ft_images(images):
         arr[b].image = im.ctypes.data_as(c_u8_p)
         arr[b].height, arr[b].width = im.shape
     return arr, keep
+
+
+# ---- line tracking of the line front end (uvs_lt_*, include/uvs_solver.h) ------------------------------------------------
+LT_MAX_STREAMS = 64
+LT_MAX_LINES = 1024
+LT_MAX_LENGTH = 2048
+LT_MIN_SIZE = 8
+LT_ROWS = 63
+LT_DESC_FLOATS = 72
+LT_DESC_BYTES = 32
+LT_GATE2 = 900
+LT_STATUS = ["OK", "SHORT", "LONG"]      # line_status[] of uvs_lt_track
+LT_OK, LT_SHORT, LT_LONG = 0, 1, 2
+
+
+class LtItem(C.Structure):
+    _fields_ = [("image", c_u8_p), ("stream", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_lines", C.c_int32),
+                ("segments", c_double_p)]
+
+
+class LtResult(C.Structure):
+    _fields_ = [("n_described", C.c_int32), ("n_matched", C.c_int32), ("status", C.c_int32)]
+
+
+def lt_items(items):
+    """(LtItem array, keepalive) from dicts with stream, image [H, W] uint8 and segs [n, 4] float64 pixels (sx, sy, ex, ey; optional)."""
+    arr = (LtItem * max(len(items), 1))()
+    keep = []
+    for b, d in enumerate(items):
+        im = np.ascontiguousarray(d["image"], dtype=np.uint8)
+        segs = np.ascontiguousarray(d.get("segs", np.zeros((0, 4))), dtype=np.float64).reshape(-1, 4)
+        keep += [im, segs]
+        arr[b].image = im.ctypes.data_as(c_u8_p)
+        arr[b].stream = int(d.get("stream", 0))
+        arr[b].height, arr[b].width = im.shape
+        arr[b].n_lines = int(d.get("n_lines", len(segs)))            # n_lines: for the tests of the argument checks
+        arr[b].segments = segs.ctypes.data_as(c_double_p) if len(segs) else None
+    return arr, keep

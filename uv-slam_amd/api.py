@@ -27,6 +27,8 @@ EXPORTS = [
     "uvs_ft_set_max_candidates", "uvs_ft_set_mask", "uvs_ft_detect", "uvs_ft_last_detect_device_ms", "uvs_ft_debug_detect",
     "uvs_ft_reject", "uvs_ft_last_reject_device_ms", "uvs_ft_debug_reject",
     "uvs_ft_set_equalize", "uvs_ft_equalize", "uvs_ft_last_equalize_device_ms", "uvs_ft_debug_equalize",
+    "uvs_lt_create", "uvs_lt_destroy", "uvs_lt_last_error", "uvs_lt_reset", "uvs_lt_track", "uvs_lt_match", "uvs_lt_last_device_ms", "uvs_lt_debug_line",
+    "uvs_lt_gauss_tables",
 ]
 
 
@@ -151,6 +153,18 @@ def lib():
         L.uvs_ft_last_equalize_device_ms.argtypes = [C.c_void_p]; L.uvs_ft_last_equalize_device_ms.restype = C.c_double
         L.uvs_ft_debug_equalize.argtypes = [C.c_void_p, C.POINTER(abi.FtImage), C.c_double, C.c_int, C.c_int, abi.c_i32_p, abi.c_u8_p, abi.c_u8_p, abi.c_i32_p]
         L.uvs_ft_debug_equalize.restype = C.c_int
+        L.uvs_lt_create.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_void_p)]; L.uvs_lt_create.restype = C.c_int
+        L.uvs_lt_destroy.argtypes = [C.c_void_p]; L.uvs_lt_destroy.restype = None
+        L.uvs_lt_last_error.argtypes = [C.c_void_p]; L.uvs_lt_last_error.restype = C.c_char_p
+        L.uvs_lt_reset.argtypes = [C.c_void_p, C.c_int]; L.uvs_lt_reset.restype = C.c_int
+        L.uvs_lt_track.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LtItem), abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, C.POINTER(abi.LtResult)]
+        L.uvs_lt_track.restype = C.c_int
+        L.uvs_lt_match.argtypes = [C.c_void_p, C.c_int, abi.c_u8_p, abi.c_i32_p, C.c_int, abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p]
+        L.uvs_lt_match.restype = C.c_int
+        L.uvs_lt_last_device_ms.argtypes = [C.c_void_p]; L.uvs_lt_last_device_ms.restype = C.c_double
+        L.uvs_lt_debug_line.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, abi.c_double_p, abi.c_i32_p, C.POINTER(C.c_int64), abi.c_double_p, abi.c_u8_p]
+        L.uvs_lt_debug_line.restype = C.c_int
+        L.uvs_lt_gauss_tables.argtypes = [abi.c_double_p, abi.c_double_p]; L.uvs_lt_gauss_tables.restype = None
         _lib = L
     return _lib
 
@@ -995,3 +1009,96 @@ class FeatureTracker(_Handle):
         if rc != abi.UVS_OK:
             raise self._error("uvs_ft_debug_equalize", rc)
         return dict(out=out, bins=bins.reshape(tiles_y, tiles_x, 256), luts=luts.reshape(tiles_y, tiles_x, 256), info=info)
+
+
+class LineTracker(_Handle):
+    """Owns one `uvs_lt_tracker` handle: the line tracking of the line front end (lineBiDes->compute and lineMatching of the reference's
+    line_feature_tracker.cpp) on one GPU.  The caller supplies a frame's segments with the image they were detected in; each slot keeps its
+    previous lines' descriptors and gate points on the device, and a call describes a batch of new frames, one per slot, and says which
+    previous line each new line continues.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path (gauss_tables needs none)."""
+
+    _UNIT = "uvs_lt"
+
+    def __init__(self, device=0, max_streams=1, max_width=752, max_height=480, max_lines=256, max_length=abi.LT_MAX_LENGTH):
+        self._create(device, max_streams, max_width, max_height, max_lines, max_length)
+
+    @staticmethod
+    def gauss_tables():
+        """-> (G [63], Lc [21]): the coefficient tables a handle uploads (host only)."""
+        G = np.zeros(abi.LT_ROWS); Lc = np.zeros(21)
+        lib().uvs_lt_gauss_tables(abi._dp(G), abi._dp(Lc))
+        return G, Lc
+
+    def track_raw(self, items, n_items=None, null=()):
+        """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  n_items overrides the count passed;
+        `null` names arguments passed as NULL ("items", "desc", "line_status", "prev_index", "distance", "results")."""
+        arr, keep = abi.lt_items(items)
+        nl = [len(k) for k in keep[1::2]]
+        tl = max(sum(nl), 1)
+        desc = np.zeros((tl, abi.LT_DESC_BYTES), np.uint8); status = np.zeros(tl, np.int32); prev = np.full(tl, -1, np.int32); dist = np.full(tl, -1, np.int32)
+        res = (abi.LtResult * max(len(items), 1))()
+        args = dict(items=C.cast(arr, C.POINTER(abi.LtItem)), desc=desc.ctypes.data_as(abi.c_u8_p), line_status=abi._ip(status),
+                    prev_index=abi._ip(prev), distance=abi._ip(dist), results=C.cast(res, C.POINTER(abi.LtResult)))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_lt_track(self._h, len(items) if n_items is None else int(n_items), args["items"], args["desc"], args["line_status"],
+                                args["prev_index"], args["distance"], args["results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernels, download
+        self.last_device_ms = float(lib().uvs_lt_last_device_ms(self._h))      # HIP events around upload, kernels, download
+        off = np.r_[0, np.cumsum(nl)].astype(int)
+        return rc, [dict(desc=desc[off[b]:off[b + 1]].copy(), status=status[off[b]:off[b + 1]].copy(), prev_index=prev[off[b]:off[b + 1]].copy(),
+                         distance=dist[off[b]:off[b + 1]].copy(), n_described=int(res[b].n_described), n_matched=int(res[b].n_matched))
+                    for b in range(len(items))]
+
+    def track(self, items):
+        """items: list of dicts (stream, image [H, W] uint8, segs [n, 4]: sx, sy, ex, ey in pixels of that image) -> list of dicts: desc
+        [n, 32] uint8, status [n] (abi.LT_STATUS), prev_index [n] (the slot's previous line this one continues, or -1), distance [n] (the
+        Hamming distance of that match, or -1), n_described, n_matched."""
+        rc, out = self.track_raw(items)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_track", rc)
+        return out
+
+    def reset(self, stream):
+        rc = lib().uvs_lt_reset(self._h, int(stream))
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_reset", rc)
+
+    def match_raw(self, prev_desc, prev_ends, cur_desc, cur_ends, n_prev=None, n_cur=None):
+        """-> (return code, match_of_prev, distance, prev_of_cur) without raising."""
+        pd = np.ascontiguousarray(prev_desc, np.uint8).reshape(-1, abi.LT_DESC_BYTES); pe = np.ascontiguousarray(prev_ends, np.int32).reshape(-1, 4)
+        cd = np.ascontiguousarray(cur_desc, np.uint8).reshape(-1, abi.LT_DESC_BYTES); ce = np.ascontiguousarray(cur_ends, np.int32).reshape(-1, 4)
+        mop = np.full(max(len(pd), 1), -1, np.int32); dist = np.full(max(len(pd), 1), -1, np.int32); poc = np.full(max(len(cd), 1), -1, np.int32)
+        u8 = lambda a: a.ctypes.data_as(abi.c_u8_p) if len(a) else None
+        i32 = lambda a: abi._ip(a) if len(a) else None
+        rc = lib().uvs_lt_match(self._h, len(pd) if n_prev is None else int(n_prev), u8(pd), i32(pe), len(cd) if n_cur is None else int(n_cur),
+                                u8(cd), i32(ce), abi._ip(mop), abi._ip(dist), abi._ip(poc))
+        return rc, mop[:len(pd)], dist[:len(pd)], poc[:len(cd)]
+
+    def match(self, prev_desc, prev_ends, cur_desc, cur_ends):
+        """Stateless: descriptors [., 32] uint8 and gate points [., 4] int32 -> (match_of_prev, distance, prev_of_cur); every line counts as OK."""
+        rc, mop, dist, poc = self.match_raw(prev_desc, prev_ends, cur_desc, cur_ends)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_match", rc)
+        return mop, dist, poc
+
+    def debug_line_raw(self, image, segment, null=()):
+        im = np.ascontiguousarray(image, np.uint8); seg = np.ascontiguousarray(segment, np.float64).reshape(4)
+        geom = np.zeros(8, np.int32); S = np.zeros((abi.LT_ROWS, 4), np.int64); df = np.zeros(abi.LT_DESC_FLOATS); desc = np.zeros(abi.LT_DESC_BYTES, np.uint8)
+        args = dict(image=im.ctypes.data_as(abi.c_u8_p), segment=abi._dp(seg), geom=abi._ip(geom), row_sums=S.ctypes.data_as(C.POINTER(C.c_int64)),
+                    desc_float=abi._dp(df), desc=desc.ctypes.data_as(abi.c_u8_p))
+        for k in null:
+            args[k] = None
+        rc = lib().uvs_lt_debug_line(self._h, args["image"], im.shape[1], im.shape[0], args["segment"], args["geom"], args["row_sums"],
+                                     args["desc_float"], args["desc"])
+        return rc, dict(geom=geom, row_sums=S, desc_float=df, desc=desc)
+
+    def debug_line(self, image, segment):
+        """ONE segment with the intermediate results (tests only) -> dict: geom [8], row_sums [63, 4] int64, desc_float [72], desc [32]."""
+        rc, out = self.debug_line_raw(image, segment)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_debug_line", rc)
+        return out
