@@ -1014,8 +1014,8 @@ int uvs_ft_debug_equalize(uvs_ft_tracker *ft, const uvs_ft_image *image, double 
 
 /* ---- line tracking of the line front end (reference feature_tracker/src/line_feature_tracker.cpp: lineExtraction's lineBiDes->compute,
  * lineMatching, and the matches that readImage4Line :351-433 turns into ids) ----
- * A handle is a line tracker with max_streams slots.  The caller detects the segments of a frame (ELSED is a sequential edge walk and stays
- * the caller's) and passes them with the image they were found in.  One call takes a batch of items, at most one per slot: it computes one
+ * A handle is a line tracker with max_streams slots.  The caller passes the segments of a frame (its own detector's, or uvs_lt_detect's
+ * below; uvs_lt_detect_track does both steps) with the image they were found in.  One call takes a batch of items, at most one per slot: it computes one
  * 256-bit LBD descriptor per segment, matches the slot's previous lines (the queries) against the new ones (the train set), and makes the new
  * lines the slot's previous ones: descriptors and gate points stay resident on the device.  A slot that holds nothing (fresh, after
  * uvs_lt_reset, or after a frame without lines) matches nothing.  An item gives the same bits alone or in a batch, from run to run and on any
@@ -1114,6 +1114,88 @@ int uvs_lt_debug_line(uvs_lt_tracker *lt, const uint8_t *image, int width, int h
                       int64_t *row_sums, double *desc_float, uint8_t *desc);
 /* Host only, no GPU needed: the two coefficient tables a handle uploads, G[63] and Lc[21]. */
 void uvs_lt_gauss_tables(double *G, double *Lc);
+
+/* ---- segment detection of the line front end (the place of elsed.detect(forw_img) in the reference's lineExtraction) ----
+ * Calls on the line tracker's handle.  ELSED's source is not in the reference tree, and a sequential edge walk is the wrong shape for a GPU;
+ * this is the project's own statement of a detector, chosen so that every stage is order-independent and the device is held to a numpy
+ * restatement (tests/ld_ref.py) bit for bit: Burns-style line-support regions, i.e. connected regions of like gradient orientation in two
+ * overlapping orientation partitions, a vote between the partitions, and a weighted moment fit.  No comparison with ELSED or OpenCV output was
+ * possible where this was written.  Out of scope: splitting curved regions, a straightness gate (width2 is returned so that a caller can
+ * filter), sub-pixel refinement, merging collinear pieces.
+ *
+ * For one 8-bit image I[H][W] and the parameters grad_threshold T >= 1, min_pixels >= 2, min_length > 0 (conventions as above: refl is
+ * reflect-101, >> arithmetic):
+ *   1 blur      separable, taps {1, 4, 6, 4, 1}, reflect-101, rows then columns in integers, out = (sum + 128) >> 8
+ *   2 gradient  the Sobel gx, gy of the tracking rule above (k_lt_gradient's, reflect-101) on the BLURRED image;  M = |gx| + |gy|;  a pixel is
+ *               a support pixel iff M >= T
+ *   3 sectors   integers only.  Quadrant q: (gx > 0, gy >= 0) -> 0, (gx <= 0, gy > 0) -> 1, (gx < 0, gy <= 0) -> 2, (gx >= 0, gy < 0) -> 3.  The
+ *               vector turned back by q 90 degrees is (px, py) with px > 0, py >= 0: (gx, gy), (gy, -gx), (-gx, -gy), (-gy, gx).
+ *               Partition A, boundaries at multiples of 45 degrees:  A = 2 q + (py >= px).
+ *               Partition B, boundaries at 22.5 + 45 k degrees:      B = (2 q + (985 py >= 408 px) + (408 py >= 985 px)) mod 8.
+ *   4 regions   in each partition two support pixels are linked iff they are 8-neighbours with the same sector; a region is a connected
+ *               component, its NAME the smallest linear index y W + x among its pixels, its size n
+ *   5 vote      a support pixel votes A iff n_A(its A region) >= n_B(its B region), else B.  A region's support s = the number of its pixels
+ *               that voted for its partition.  A region is a candidate iff n >= min_pixels and 2 s > n
+ *   6 fit       over ALL pixels of a candidate, relative to its name pixel (x0, y0):  dx = x - x0, dy = y - y0, w = M;  the int64 sums S0, Sx, Sy,
+ *               Sxx, Sxy, Syy of w, w dx, w dy, w dx^2, w dx dy, w dy^2 (exact in any order), each converted to FP64 once.  Then, every FP64
+ *               operation rounding as written (+ - x / sqrt only, no fused multiply-add):
+ *                 mx = Sx / S0, my = Sy / S0;  a = Sxx / S0 - mx mx, c = Syy / S0 - my my, b = Sxy / S0 - mx my;
+ *                 h = (a - c) 0.5, r = sqrt(h h + b b);  (ux, uy) = a >= c ? (h + r, b) : (b, r - h);  nrm = sqrt(ux ux + uy uy);
+ *                 the region is rejected if nrm == 0;  ux /= nrm, uy /= nrm;  width2 = (a + c) 0.5 - r
+ *   7 extent    per pixel t = (dx - mx) ux + (dy - my) uy;  tmin, tmax over the region's pixels (exact in any order);  length = tmax - tmin;
+ *               the region is kept iff length >= min_length.  Start = ((x0 + mx) + tmin ux, (y0 + my) + tmin uy), end likewise with tmax
+ *   8 output    the kept segments ranked by (length descending, name ascending, partition A before B); the first max_lines (of the handle)
+ *               are returned.  Per segment: seg[4] = start x, y, end x, y; width2; info[4] = name, partition (0 = A, 1 = B), n, s.
+ * The device equals tests/ld_ref.py bit for bit; DESIGN.md 3.15 has the kernel plan.  No CPU path. */
+#define UVS_LT_DET_MAX_THRESHOLD 2040         /* largest grad_threshold: M never exceeds it */
+enum { UVS_LT_DET_OK = 0, UVS_LT_DET_OVERFLOW = 1 };      /* OVERFLOW: n_found > max_lines; the first max_lines of the ranking are returned */
+
+typedef struct uvs_lt_det_item {
+    const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width */
+    int32_t stream;                    /* uvs_lt_detect_track: the slot, at most once per call; uvs_lt_detect ignores it */
+    int32_t width;                     /* UVS_LT_MIN_SIZE .. max_width */
+    int32_t height;                    /* UVS_LT_MIN_SIZE .. max_height */
+    int32_t reserved;                  /* 0 */
+} uvs_lt_det_item;
+
+typedef struct uvs_lt_det_params {
+    int32_t grad_threshold;            /* T: 1 .. UVS_LT_DET_MAX_THRESHOLD */
+    int32_t min_pixels;                /* >= 2 */
+    double min_length;                 /* > 0, finite */
+} uvs_lt_det_params;
+
+typedef struct uvs_lt_det_result {
+    int32_t status;                    /* UVS_LT_DET_* */
+    int32_t n_found;                   /* all kept segments */
+    int32_t n_returned;                /* min(n_found, max_lines) */
+    int32_t n_support;                 /* support pixels */
+    int32_t n_regions[2];              /* regions of partition A, of partition B (of every size) */
+} uvs_lt_det_result;
+
+/* Stateless: it touches no slot.  The outputs hold max_lines rows PER ITEM (item b's rows start at b max_lines; rows from n_returned on are
+ * zero): seg[n_items max_lines][4], width2[n_items max_lines], info[n_items max_lines][4]; results[n_items].  An item gives the same bits
+ * alone or in a batch.
+ * UVS_ERR_INVALID_ARG: null pointer, n_items < 1, a null image, a width or height below UVS_LT_MIN_SIZE, a parameter outside the ranges above;
+ * UVS_ERR_CAPACITY: n_items above max_streams, a width or a height above the handle's capacity.  A rejected call changes nothing, and the
+ * handle stays usable after it.  The first call allocates the detection's work space (about 160 bytes per pixel of max_streams images of
+ * max_width x max_height). */
+int uvs_lt_detect(uvs_lt_tracker *lt, int n_items, const uvs_lt_det_item *items, const uvs_lt_det_params *params, double *seg, double *width2,
+                  int32_t *info, uvs_lt_det_result *det_results);
+/* uvs_lt_detect, then exactly what uvs_lt_track does with the returned segments of every item in the slot item.stream; the image is uploaded
+ * once.  seg, width2, info, det_results as above;  desc, line_status, prev_index, distance, results as uvs_lt_track's, PACKED over the items'
+ * n_returned lines in order.  The results and the slots afterwards equal uvs_lt_detect followed by uvs_lt_track on the same images, bit for
+ * bit.  The checks are those of both calls (a stream outside the slots or given twice: UVS_ERR_INVALID_ARG); a rejected call changes no slot. */
+int uvs_lt_detect_track(uvs_lt_tracker *lt, int n_items, const uvs_lt_det_item *items, const uvs_lt_det_params *params, double *seg,
+                        double *width2, int32_t *info, uvs_lt_det_result *det_results, uint8_t *desc, int32_t *line_status,
+                        int32_t *prev_index, int32_t *distance, uvs_lt_result *results);
+/* HIP-event time of the last successful uvs_lt_detect or uvs_lt_detect_track: upload, the kernels, download, on the handle's stream
+ * (milliseconds; for uvs_lt_detect_track the detection's and the tracking's added). */
+double uvs_lt_last_detect_device_ms(const uvs_lt_tracker *lt);
+/* Diagnostic (tests only): ONE image through the detection's kernels with the per-pixel stages, each [height][width]: blur, grad (gx in the
+ * low, gy in the high 16 bits), sector_a and sector_b (255 = no support), name_a and name_b (-1 = none), vote (0 = A, 1 = B, 255 = no
+ * support).  It touches no slot. */
+int uvs_lt_debug_detect(uvs_lt_tracker *lt, const uint8_t *image, int width, int height, const uvs_lt_det_params *params, uint8_t *blur,
+                        uint32_t *grad, uint8_t *sector_a, uint8_t *sector_b, int32_t *name_a, int32_t *name_b, uint8_t *vote);
 
 #ifdef __cplusplus
 }

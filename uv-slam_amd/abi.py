@@ -778,3 +778,33 @@ def lt_items(items):
         arr[b].n_lines = int(d.get("n_lines", len(segs)))            # n_lines: for the tests of the argument checks
         arr[b].segments = segs.ctypes.data_as(c_double_p) if len(segs) else None
     return arr, keep
+
+
+# ---- segment detection of the line front end (uvs_lt_detect, uvs_lt_detect_track, include/uvs_solver.h) -------------------
+LT_DET_MAX_THRESHOLD = 2040
+LT_DET_OK, LT_DET_OVERFLOW = 0, 1
+
+
+class LtDetItem(C.Structure):
+    _fields_ = [("image", c_u8_p), ("stream", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LtDetParams(C.Structure):
+    _fields_ = [("grad_threshold", C.c_int32), ("min_pixels", C.c_int32), ("min_length", C.c_double)]
+
+
+class LtDetResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_found", C.c_int32), ("n_returned", C.c_int32), ("n_support", C.c_int32), ("n_regions", C.c_int32 * 2)]
+
+
+def lt_det_items(items):
+    """(LtDetItem array, keepalive) from dicts with image [H, W] uint8 and stream (uvs_lt_detect_track's slot; optional)."""
+    arr = (LtDetItem * max(len(items), 1))()
+    keep = []
+    for b, d in enumerate(items):
+        im = np.ascontiguousarray(d["image"], dtype=np.uint8)
+        keep.append(im)
+        arr[b].image = im.ctypes.data_as(c_u8_p)
+        arr[b].stream = int(d.get("stream", 0))
+        arr[b].height, arr[b].width = im.shape
+    return arr, keep

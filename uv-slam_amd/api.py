@@ -29,6 +29,7 @@ EXPORTS = [
     "uvs_ft_set_equalize", "uvs_ft_equalize", "uvs_ft_last_equalize_device_ms", "uvs_ft_debug_equalize",
     "uvs_lt_create", "uvs_lt_destroy", "uvs_lt_last_error", "uvs_lt_reset", "uvs_lt_track", "uvs_lt_match", "uvs_lt_last_device_ms", "uvs_lt_debug_line",
     "uvs_lt_gauss_tables",
+    "uvs_lt_detect", "uvs_lt_detect_track", "uvs_lt_last_detect_device_ms", "uvs_lt_debug_detect",
 ]
 
 
@@ -165,6 +166,14 @@ def lib():
         L.uvs_lt_debug_line.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, abi.c_double_p, abi.c_i32_p, C.POINTER(C.c_int64), abi.c_double_p, abi.c_u8_p]
         L.uvs_lt_debug_line.restype = C.c_int
         L.uvs_lt_gauss_tables.argtypes = [abi.c_double_p, abi.c_double_p]; L.uvs_lt_gauss_tables.restype = None
+        det_args = [C.c_void_p, C.c_int, C.POINTER(abi.LtDetItem), C.POINTER(abi.LtDetParams), abi.c_double_p, abi.c_double_p, abi.c_i32_p, C.POINTER(abi.LtDetResult)]
+        L.uvs_lt_detect.argtypes = det_args; L.uvs_lt_detect.restype = C.c_int
+        L.uvs_lt_detect_track.argtypes = det_args + [abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, C.POINTER(abi.LtResult)]
+        L.uvs_lt_detect_track.restype = C.c_int
+        L.uvs_lt_last_detect_device_ms.argtypes = [C.c_void_p]; L.uvs_lt_last_detect_device_ms.restype = C.c_double
+        L.uvs_lt_debug_detect.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, C.POINTER(abi.LtDetParams), abi.c_u8_p, C.POINTER(C.c_uint32), abi.c_u8_p,
+                                          abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_u8_p]
+        L.uvs_lt_debug_detect.restype = C.c_int
         _lib = L
     return _lib
 
@@ -1015,7 +1024,8 @@ class LineTracker(_Handle):
     """Owns one `uvs_lt_tracker` handle: the line tracking of the line front end (lineBiDes->compute and lineMatching of the reference's
     line_feature_tracker.cpp) on one GPU.  The caller supplies a frame's segments with the image they were detected in; each slot keeps its
     previous lines' descriptors and gate points on the device, and a call describes a batch of new frames, one per slot, and says which
-    previous line each new line continues.
+    previous line each new line continues.  detect() finds the segments of an image on the device (line-support regions, the project's own
+    rule), detect_track() does both steps with one upload of the image.
 
     Fails loudly (RuntimeError) without a GPU -- there is no CPU path (gauss_tables needs none)."""
 
@@ -1023,6 +1033,7 @@ class LineTracker(_Handle):
 
     def __init__(self, device=0, max_streams=1, max_width=752, max_height=480, max_lines=256, max_length=abi.LT_MAX_LENGTH):
         self._create(device, max_streams, max_width, max_height, max_lines, max_length)
+        self.max_lines = int(max_lines)
 
     @staticmethod
     def gauss_tables():
@@ -1102,3 +1113,91 @@ class LineTracker(_Handle):
         if rc != abi.UVS_OK:
             raise self._error("uvs_lt_debug_line", rc)
         return out
+
+    # ---- segment detection (uvs_lt_detect, uvs_lt_detect_track)
+    @staticmethod
+    def _det_params(grad_threshold=40, min_pixels=10, min_length=12.0):
+        return abi.LtDetParams(int(grad_threshold), int(min_pixels), float(min_length))
+
+    def _det_call(self, track, items, params, n_items=None, null=()):
+        arr, keep = abi.lt_det_items(items)
+        n = max(len(items), 1); ml = self.max_lines
+        seg = np.zeros((n * ml, 4)); w2 = np.zeros(n * ml); info = np.zeros((n * ml, 4), np.int32)
+        dres = (abi.LtDetResult * n)()
+        desc = np.zeros((n * ml, abi.LT_DESC_BYTES), np.uint8); status = np.zeros(n * ml, np.int32); prev = np.full(n * ml, -1, np.int32)
+        dist = np.full(n * ml, -1, np.int32); res = (abi.LtResult * n)()
+        pr = self._det_params(**params)
+        args = dict(items=C.cast(arr, C.POINTER(abi.LtDetItem)), params=C.pointer(pr), seg=abi._dp(seg), width2=abi._dp(w2), info=abi._ip(info),
+                    det_results=C.cast(dres, C.POINTER(abi.LtDetResult)), desc=desc.ctypes.data_as(abi.c_u8_p), line_status=abi._ip(status),
+                    prev_index=abi._ip(prev), distance=abi._ip(dist), results=C.cast(res, C.POINTER(abi.LtResult)))
+        for k in null:
+            args[k] = None
+        order = ["items", "params", "seg", "width2", "info", "det_results"] + (["desc", "line_status", "prev_index", "distance", "results"] if track else [])
+        fn = lib().uvs_lt_detect_track if track else lib().uvs_lt_detect
+        t0 = time.perf_counter()
+        rc = fn(self._h, len(items) if n_items is None else int(n_items), *[args[k] for k in order])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernels, download
+        self.last_detect_device_ms = float(lib().uvs_lt_last_detect_device_ms(self._h))      # HIP events around upload, kernels, download
+        out = []
+        off = 0
+        for b in range(len(items)):
+            k = int(dres[b].n_returned); r = slice(b * ml, b * ml + k)
+            d = dict(seg=seg[r].copy(), width2=w2[r].copy(), info=info[r].copy(), n_found=int(dres[b].n_found), n_returned=k,
+                     n_support=int(dres[b].n_support), n_regions=[int(dres[b].n_regions[0]), int(dres[b].n_regions[1])], det_status=int(dres[b].status),
+                     tail_is_zero=not seg[b * ml + k:(b + 1) * ml].any() and not info[b * ml + k:(b + 1) * ml].any())
+            if track:
+                t = slice(off, off + k); off += k
+                d.update(desc=desc[t].copy(), status=status[t].copy(), prev_index=prev[t].copy(), distance=dist[t].copy(),
+                         n_described=int(res[b].n_described), n_matched=int(res[b].n_matched))
+            out.append(d)
+        return rc, out
+
+    def detect_raw(self, items, n_items=None, null=(), **params):
+        """-> (return code, [dict per item]) without raising: for the tests of the argument checks.  `null` names arguments passed as NULL
+        ("items", "params", "seg", "width2", "info", "det_results")."""
+        return self._det_call(False, items, params, n_items, null)
+
+    def detect(self, items, **params):
+        """items: list of dicts (image [H, W] uint8); params: grad_threshold, min_pixels, min_length -> list of dicts: seg [k, 4] (start x, y,
+        end x, y, ranked by length), width2 [k], info [k, 4] (name, partition, n, s), n_found, n_returned = k, n_support, n_regions [2],
+        det_status (abi.LT_DET_*).  Stateless."""
+        rc, out = self.detect_raw(items, **params)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_detect", rc)
+        return out
+
+    def detect_track_raw(self, items, n_items=None, null=(), **params):
+        """As detect_raw for uvs_lt_detect_track; `null` may also name "desc", "line_status", "prev_index", "distance", "results"."""
+        return self._det_call(True, items, params, n_items, null)
+
+    def detect_track(self, items, **params):
+        """items: list of dicts (stream, image) -> detect()'s dicts with track()'s entries for the returned segments beside them (desc, status,
+        prev_index, distance, n_described, n_matched).  The image is uploaded once."""
+        rc, out = self.detect_track_raw(items, **params)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_detect_track", rc)
+        return out
+
+    def debug_detect_raw(self, image, null=(), **params):
+        im = np.ascontiguousarray(image, np.uint8)
+        H, W = im.shape
+        o = dict(blur=np.zeros((H, W), np.uint8), grad=np.zeros((H, W), np.uint32), sector_a=np.zeros((H, W), np.uint8), sector_b=np.zeros((H, W), np.uint8),
+                 name_a=np.zeros((H, W), np.int32), name_b=np.zeros((H, W), np.int32), vote=np.zeros((H, W), np.uint8))
+        pr = self._det_params(**params)
+        args = dict(image=im.ctypes.data_as(abi.c_u8_p), params=C.pointer(pr), blur=o["blur"].ctypes.data_as(abi.c_u8_p),
+                    grad=o["grad"].ctypes.data_as(C.POINTER(C.c_uint32)), sector_a=o["sector_a"].ctypes.data_as(abi.c_u8_p),
+                    sector_b=o["sector_b"].ctypes.data_as(abi.c_u8_p), name_a=abi._ip(o["name_a"]), name_b=abi._ip(o["name_b"]),
+                    vote=o["vote"].ctypes.data_as(abi.c_u8_p))
+        for k in null:
+            args[k] = None
+        rc = lib().uvs_lt_debug_detect(self._h, args["image"], W, H, args["params"], args["blur"], args["grad"], args["sector_a"], args["sector_b"],
+                                       args["name_a"], args["name_b"], args["vote"])
+        return rc, o
+
+    def debug_detect(self, image, **params):
+        """ONE image with the per-pixel stages (tests only) -> dict of [H, W] arrays: blur, grad (gx | gy << 16), sector_a, sector_b (255 = no
+        support), name_a, name_b (-1 = none), vote (0 = A, 1 = B, 255 = no support)."""
+        rc, o = self.debug_detect_raw(image, **params)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_debug_detect", rc)
+        return o

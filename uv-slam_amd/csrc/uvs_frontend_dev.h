@@ -1,9 +1,11 @@
 // uvs_frontend_dev.h -- the device helpers the front-end units share, one statement of each: the counter-based generator of the RANSAC units
 // (uvs_loop_verify, uvs_vanishing_points, uvs_feature_reject), reflect-101 of the image units (uvs_keyframe_features, uvs_feature_track,
-// uvs_feature_detect) and the ordered compaction by 64-pixel row segments (k_kf_select_*, k_ft_detect_*).  Integer arithmetic only, so the
+// uvs_feature_detect), the packed Sobel of the line units (uvs_line_track, uvs_line_detect) and the ordered compaction by 64-pixel row
+// segments (k_kf_select_*, k_ft_detect_*).  Integer arithmetic only, so the
 // contraction flag of the including unit does not matter; everything is inlined into the kernels that call it.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 
 // the splitmix64 finalizer
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
@@ -25,6 +27,17 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     i = i < 0 ? -i : i;
     i = i >= n ? 2 * n - 2 - i : i;
     return min(max(i, 0), n - 1);
+}
+
+// the Sobel gx, gy of uvs_ft_detect's rule at (x, y) of the 8-bit image p[H][W] (stride W), every read through reflect-101: gx in the low, gy in
+// the high 16 bits of one word (|g| <= 1020), so that a sample of a gradient image is ONE gather (k_lt_gradient, k_lt_det_sectors)
+__device__ __forceinline__ uint32_t uvs_sobel_packed(const uint8_t* __restrict__ p, int W, int H, int x, int y) {
+    const int xm = reflect101(x - 1, W), xp = reflect101(x + 1, W), ym = reflect101(y - 1, H), yp = reflect101(y + 1, H);
+    const int a = p[ym * W + xm], b = p[ym * W + x], c = p[ym * W + xp], d = p[y * W + xm], f = p[y * W + xp], q = p[yp * W + xm],
+              r = p[yp * W + x], s = p[yp * W + xp];
+    const int gx = (c - a) + 2 * (f - d) + (s - q);
+    const int gy = (q - a) + 2 * (r - b) + (s - c);
+    return ((uint32_t)gx & 0xFFFFu) | ((uint32_t)gy << 16);
 }
 
 // ---- ordered compaction by 64-pixel row segments: a mark kernel writes every segment's ballot and its popcount, a workgroup per item scans

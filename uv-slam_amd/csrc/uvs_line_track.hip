@@ -1,7 +1,8 @@
 // uvs_line_track.hip -- line tracking of the line front end (reference feature_tracker/src/line_feature_tracker.cpp: lineExtraction's
 // lineBiDes->compute, lineMatching, the matches consumed at :351-433) behind the uvs_lt_* calls of include/uvs_solver.h: one 256-bit LBD
 // descriptor per caller-supplied segment, the Hamming match of a slot's previous lines against the new ones with the 30 px endpoint gates,
-// and the slots' previous lines resident on the device.  gfx950, one stream per handle.
+// and the slots' previous lines resident on the device.  gfx950, one stream per handle.  The handle is csrc/uvs_lt_handle.h's, shared with the
+// detection unit (uvs_line_detect.hip), which calls lt_run below for uvs_lt_detect_track.
 //
 // One call takes a batch of items; no kernel reads another item's data, so an item gives the same bits alone or in a batch.  This unit is
 // compiled with -ffp-contract=off: products and sums round as written, which is what tests/lt_ref.py (the numpy restatement, the pin) does.
@@ -27,30 +28,13 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_frontend_dev.h"
-#include "uvs_handle.h"
+#include "uvs_lt_handle.h"
 
 namespace uvslt {
 
-constexpr int kRows = UVS_LT_ROWS, kFloats = UVS_LT_DESC_FLOATS, kBytes = UVS_LT_DESC_BYTES;
-constexpr int kMaxLines = UVS_LT_MAX_LINES;
 constexpr int kGradThreads = 256, kPrepThreads = 64, kRowThreads = 256, kRowWaves = kRowThreads / 64, kBandThreads = 64, kMatchThreads = 256;
 static_assert(kRows == 63 && kFloats == 72 && kBytes == 32, "9 bands of width 7, 4 sums, 32 of the 36 band pairs");
 static_assert(kMaxLines <= 65536, "the packed match key keeps t in 16 bits");
-
-struct LtItem {                    // device copy of one item
-    int W, H, n_lines, l_off;      // image size; lines, offset of the first one in the concatenated arrays
-    long long img_off;             // of the image in the packed input
-    uint8_t* slot_desc;            // where the new lines' descriptors [n][32], gate points [n][4] and statuses [n] go (the slot's new set)
-    int32_t* slot_ends;
-    int32_t* slot_stat;
-};
-struct LtMatchJob {                // one match: the queries, the train set, the outputs (each may be null)
-    const uint8_t* pdesc; const int32_t* pends; const int32_t* pstat;      // pstat / cstat null: every line is OK
-    const uint8_t* cdesc; const int32_t* cends; const int32_t* cstat;
-    int n_prev, n_cur;
-    int32_t* match_of_prev; int32_t* dist_prev; int32_t* prev_of_cur; int32_t* dist_cur;
-    uvs_lt_result* result;         // n_matched is written here
-};
 
 // ---- gradient: gx in the low, gy in the high 16 bits
 __global__ void __launch_bounds__(kGradThreads) k_lt_gradient(const LtItem* __restrict__ items, const uint8_t* __restrict__ in,
@@ -61,12 +45,7 @@ __global__ void __launch_bounds__(kGradThreads) k_lt_gradient(const LtItem* __re
     uint32_t* g = grad + grad_stride * blockIdx.y;
     for (int i = blockIdx.x * kGradThreads + threadIdx.x; i < W * H; i += gridDim.x * kGradThreads) {
         const int x = i % W, y = i / W;
-        const int xm = reflect101(x - 1, W), xp = reflect101(x + 1, W), ym = reflect101(y - 1, H), yp = reflect101(y + 1, H);
-        const int a = p[ym * W + xm], b = p[ym * W + x], c = p[ym * W + xp], d = p[y * W + xm], f = p[y * W + xp], q = p[yp * W + xm],
-                  r = p[yp * W + x], s = p[yp * W + xp];
-        const int gx = (c - a) + 2 * (f - d) + (s - q);
-        const int gy = (q - a) + 2 * (r - b) + (s - c);
-        g[i] = ((uint32_t)gx & 0xFFFFu) | ((uint32_t)gy << 16);
+        g[i] = uvs_sobel_packed(p, W, H, x, y);
     }
 }
 
@@ -267,80 +246,11 @@ __global__ void __launch_bounds__(64) k_lt_count(const LtItem* __restrict__ item
 
 using namespace uvslt;
 
-struct LtSlot { int n_prev = 0, cur = 0; };      // lines of the previous set; which of the slot's two sets holds it
+namespace uvslt {
 
-struct uvs_lt_tracker : UvsHandle {
-    int max_streams = 0, max_width = 0, max_height = 0, max_lines = 0, max_length = 0;
-    float device_ms = 0.f;                      // uvs_lt_last_device_ms
-    size_t in_bytes = 0, out_bytes = 0, grad_stride = 0;
-    std::vector<LtSlot> slots;
-    DevBuf<char> d_in, d_out;                   // packed inputs (items | jobs | segments | images) / outputs of one call
-    PinnedBuf<char> h_in, h_out;                // pinned staging
-    DevBuf<uint32_t> d_grad;                    // [items][max_width max_height] gx | gy
-    DevBuf<int32_t> d_geom, d_line_item;        // [lines][8]; [lines]
-    DevBuf<long long> d_S;                      // [lines][63][4]
-    DevBuf<double> d_tables;                    // G[63] | Lc[21]
-    DevBuf<uint8_t> d_slot_desc;                // [streams + 1][2][max_lines][32]: the slots' two sets; the last "slot" is the debug call's
-    DevBuf<int32_t> d_slot_ends, d_slot_stat;   // [streams + 1][2][max_lines][4]; [streams + 1][2][max_lines]
-    DevBuf<double> d_dbg_float;                 // uvs_lt_debug_line only: [72]
-
-    uint8_t* set_desc(int slot, int set) const { return d_slot_desc + ((size_t)(2 * slot + set) * max_lines) * kBytes; }
-    int32_t* set_ends(int slot, int set) const { return d_slot_ends + ((size_t)(2 * slot + set) * max_lines) * 4; }
-    int32_t* set_stat(int slot, int set) const { return d_slot_stat + (size_t)(2 * slot + set) * max_lines; }
-};
-
-namespace {
-
-struct LtLayout { size_t o_jobs, o_seg, o_img, in_used, o_desc, o_stat, o_prev, o_dist, out_used; };
-
-// offsets of one call's packed buffers for n items, tl lines and the given image bytes (each image starts 256-aligned)
-LtLayout lt_layout(size_t n, size_t tl, const std::vector<size_t>& img_bytes, std::vector<size_t>* img_off) {
-    LtLayout Y;
-    UvsArena in;
-    (void)in.take(n * sizeof(LtItem));
-    Y.o_jobs = in.take(n * sizeof(LtMatchJob));
-    Y.o_seg = in.take(tl * 32);
-    Y.o_img = in.o;
-    for (size_t b : img_bytes) { const size_t at = in.take(b); if (img_off) img_off->push_back(at); }
-    Y.in_used = in.o;
-    UvsArena out;
-    (void)out.take(n * sizeof(uvs_lt_result));
-    Y.o_desc = out.take(tl * kBytes); Y.o_stat = out.take(tl * 4); Y.o_prev = out.take(tl * 4); Y.o_dist = out.take(tl * 4);
-    Y.out_used = out.o;
-    return Y;
-}
-
-int lt_check_items(uvs_lt_tracker* h, const std::string& fn, int n_items, const uvs_lt_item* items, bool slots, size_t* tl_out, int* max_n_out) {
-    std::vector<char> seen(h->max_streams, 0);
-    size_t tl = 0; int max_n = 0;
-    for (int b = 0; b < n_items; ++b) {
-        const uvs_lt_item& it = items[b];
-        const std::string who = fn + ": item " + std::to_string(b);
-        if (!it.image || it.n_lines < 0 || (it.n_lines > 0 && !it.segments)) { h->err = who + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG; }
-        if (slots) {
-            if (it.stream < 0 || it.stream >= h->max_streams) { h->err = who + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
-            if (seen[it.stream]) { h->err = who + ": stream given twice"; return UVS_ERR_INVALID_ARG; }
-            seen[it.stream] = 1;
-        }
-        if (it.width < UVS_LT_MIN_SIZE || it.height < UVS_LT_MIN_SIZE) { h->err = who + ": width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG; }
-        if (it.width > h->max_width || it.height > h->max_height || it.n_lines > h->max_lines) {
-            h->err = who + " exceeds the capacity given to uvs_lt_create"; return UVS_ERR_CAPACITY;
-        }
-        for (int l = 0; l < it.n_lines; ++l)
-            for (int k = 0; k < 4; ++k) {
-                const double v = it.segments[4 * (size_t)l + k];
-                if (!std::isfinite(v) || std::fabs(v) > UVS_KF_MAX_COORD) { h->err = who + ": a coordinate is not finite or beyond UVS_KF_MAX_COORD"; return UVS_ERR_INVALID_ARG; }
-            }
-        tl += it.n_lines; max_n = std::max(max_n, it.n_lines);
-    }
-    *tl_out = tl; *max_n_out = max_n;
-    return UVS_OK;
-}
-
-// One call's device work.  slot_of[b]: the slot whose sets item b uses (max_streams = the debug call's); with `match`, the slot's previous set
-// is matched against the new one.  The caller swaps the slots' sets after a success.
+// One call's device work (uvs_lt_handle.h has the contract).
 int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::vector<int>& slot_of, bool match, size_t tl, int max_n,
-           double* dbg_float, LtLayout* layout) {
+           double* dbg_float, LtLayout* layout, const uint8_t* dev_images, const size_t* dev_img_off) {
     std::vector<size_t> img_bytes, img_off;
     for (int b = 0; b < n_items; ++b) img_bytes.push_back((size_t)items[b].width * items[b].height);
     const LtLayout Y = lt_layout(n_items, tl, img_bytes, &img_off);
@@ -358,7 +268,7 @@ int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::
         const int s = slot_of[b];
         const int nw = s < h->max_streams ? 1 - h->slots[s].cur : 0;      // the set that is not the previous one
         LtItem d;
-        d.W = it.width; d.H = it.height; d.n_lines = it.n_lines; d.l_off = (int)lo; d.img_off = (long long)img_off[b];
+        d.W = it.width; d.H = it.height; d.n_lines = it.n_lines; d.l_off = (int)lo; d.img_off = (long long)(dev_images ? dev_img_off[b] : img_off[b]);
         d.slot_desc = h->set_desc(s, nw); d.slot_ends = h->set_ends(s, nw); d.slot_stat = h->set_stat(s, nw);
         hi[b] = d;
         LtMatchJob j;
@@ -371,17 +281,17 @@ int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::
         }
         hj[b] = j;
         if (it.n_lines) std::memcpy(h->h_in + Y.o_seg + lo * 32, it.segments, (size_t)it.n_lines * 32);
-        std::memcpy(h->h_in + img_off[b], it.image, img_bytes[b]);
+        if (!dev_images) std::memcpy(h->h_in + img_off[b], it.image, img_bytes[b]);
         lo += it.n_lines; max_px = std::max(max_px, it.width * it.height);
     }
     const LtItem* dI = reinterpret_cast<const LtItem*>(h->d_in.get());
     const LtMatchJob* dJ = reinterpret_cast<const LtMatchJob*>(h->d_in + Y.o_jobs);
     const double* dSeg = reinterpret_cast<const double*>(h->d_in + Y.o_seg);
-    const uint8_t* dIn = reinterpret_cast<const uint8_t*>(h->d_in.get());
+    const uint8_t* dIn = dev_images ? dev_images : reinterpret_cast<const uint8_t*>(h->d_in.get());
     hipStream_t st = h->st;
     UVS_HIP(h->err, hipSetDevice(h->device));
     UVS_HIP(h->err, hipEventRecord(h->ev0, st));
-    UVS_HIP(h->err, hipMemcpyAsync(h->d_in, h->h_in, Y.in_used, hipMemcpyHostToDevice, st));
+    UVS_HIP(h->err, hipMemcpyAsync(h->d_in, h->h_in, dev_images ? Y.o_img : Y.in_used, hipMemcpyHostToDevice, st));
     k_lt_gradient<<<dim3(std::min((max_px + kGradThreads - 1) / kGradThreads, 1024), n_items), kGradThreads, 0, st>>>(dI, dIn, h->d_grad, h->grad_stride);
     if (tl) {
         k_lt_prepare<<<dim3((max_n + kPrepThreads - 1) / kPrepThreads, n_items), kPrepThreads, 0, st>>>(dI, dSeg, h->max_length, h->d_geom, h->d_line_item, dStat);
@@ -397,7 +307,7 @@ int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::
     return UVS_OK;
 }
 
-}  // namespace
+}  // namespace uvslt
 
 extern "C" {
 

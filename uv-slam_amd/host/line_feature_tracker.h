@@ -1,9 +1,10 @@
 // line_feature_tracker.h -- the reference's line front end after segment detection (feature_tracker/src/line_feature_tracker.cpp:351-433,
 // 449-488: the ids and track counts of readImage4Line; :1140-1159 normalizePoints; :1205-1217 updateID) in the reference's own terms, above
-// uvs_lt_track(): an image and its segments in, ids / track_cnt / curr_start_pts / curr_end_pts / the normalized end points out.  Header-only.
+// uvs_lt_track() and uvs_lt_detect_track(): an image, with or without its segments, in, ids / track_cnt / curr_start_pts / curr_end_pts / the normalized end points out.  Header-only.
 // The descriptors (lineBiDes->compute) and lineMatching are on the GPU (csrc/uvs_line_track.hip); what is here is the bookkeeping around them.
-// Differences from the reference, all from the C ABI below: the caller detects the segments (ELSED is not part of this library) in an image
-// that is already undistorted, positions are FP64 (cv::Point2f there), and n_id is a member, not a static, so that two trackers of one
+// Differences from the reference, all from the C ABI below: the segments are the caller's detector's or, through the overload without
+// segments, uvs_lt_detect's line-support regions (ELSED is not part of this library, and not in the reference tree), the image is already
+// undistorted, positions are FP64 (cv::Point2f there), and n_id is a member, not a static, so that two trackers of one
 // process number their lines apart.  With a uvs::VanishingPoints attached, `vps` is filled per line as :379-385 does.
 #pragma once
 #include <cstdint>
@@ -77,6 +78,17 @@ public:
         return false;
     }
 
+    // One frame WITHOUT segments: detectTrack() finds and matches them (on the device in LineFeatureTracker; a test may override it and give
+    // them by hand), then the bookkeeping above and finishFrame() (the vanishing points of LineFeatureTracker).  Returns detectTrack's or
+    // finishFrame's error; after the former the frame changes nothing.
+    int readImage4Line(const uint8_t* img, int width, int height, double time) {
+        size_t n = 0;
+        const int rc = detectTrack(img, width, height, n);
+        if (rc != UVS_OK) return rc;
+        applyMatches(time, n, det_seg.data(), det_prev_index.data());
+        return finishFrame(n, det_seg.data());
+    }
+
     void reset() {
         ids.clear(); track_cnt.clear(); curr_start_pts.clear(); curr_end_pts.clear(); curr_start_un_pts.clear(); curr_end_un_pts.clear();
         prev_start_un_pts.clear(); prev_end_un_pts.clear(); start_pts_velocity.clear(); end_pts_velocity.clear(); vps.clear();
@@ -88,8 +100,15 @@ public:
     std::vector<Eigen::Vector3d> vps;                                   // per line, when a VanishingPoints is attached
     double cur_time = 0.0;
     int n_id = 0;
+    // the last frame of the overload without segments: seg[n][4], width2[n], info[n][4] as uvs_lt_detect returns them, and the matches
+    std::vector<double> det_seg, det_width2;
+    std::vector<int32_t> det_info, det_prev_index;
+    uvs_lt_det_result last_detect{};
 
 protected:
+    // fills det_seg, det_width2, det_info, det_prev_index and last_detect for the image; n = the lines returned
+    virtual int detectTrack(const uint8_t*, int, int, size_t& n) { n = 0; return UVS_ERR_NO_DEVICE; }
+    virtual int finishFrame(size_t, const double*) { return UVS_OK; }
     LinePoint2d lift(const LinePoint2d& p) const {
         const double mx = inv_K11_ * p.x + inv_K13_, my = inv_K22_ * p.y + inv_K23_, z = 1.0;
         LinePoint2d o;
@@ -124,9 +143,42 @@ public:
         desc.assign(32 * n + 32, 0); line_status.assign(n + 1, 0); prev_index_.assign(n + 1, -1); distance.assign(n + 1, -1);
         uvs_lt_item it;
         it.image = img; it.stream = 0; it.width = width; it.height = height; it.n_lines = (int32_t)n; it.segments = segments;
-        int rc = uvs_lt_track(lt_, 1, &it, desc.data(), line_status.data(), prev_index_.data(), distance.data(), &last);
+        const int rc = uvs_lt_track(lt_, 1, &it, desc.data(), line_status.data(), prev_index_.data(), distance.data(), &last);
         if (rc != UVS_OK) { last_error = uvs_lt_last_error(lt_); return rc; }
         applyMatches(cur_time, n, segments, prev_index_.data());
+        return finishFrame(n, segments);
+    }
+    using LineFeatureTrackerBook::readImage4Line;      // (img, width, height, cur_time): uvs_lt_detect_track finds the segments
+
+    void reset() { LineFeatureTrackerBook::reset(); (void)uvs_lt_reset(lt_, 0); }
+
+    uvs_lt_result last{};
+    std::vector<uint8_t> desc;               // [n][32] of the last frame
+    std::vector<int32_t> line_status, distance;
+    std::string last_error;
+    // uvs_lt_detect's parameters for the overload without segments
+    int grad_threshold = 40, min_pixels = 10;
+    double min_length = 12.0;
+
+protected:
+    int detectTrack(const uint8_t* img, int width, int height, size_t& n) override {
+        const size_t m = (size_t)max_lines_;
+        det_seg.assign(4 * m, 0.0); det_width2.assign(m, 0.0); det_info.assign(4 * m, 0); det_prev_index.assign(m + 1, -1);
+        desc.assign(32 * m + 32, 0); line_status.assign(m + 1, 0); distance.assign(m + 1, -1);
+        uvs_lt_det_item it;
+        it.image = img; it.stream = 0; it.width = width; it.height = height; it.reserved = 0;
+        uvs_lt_det_params pr;
+        pr.grad_threshold = grad_threshold; pr.min_pixels = min_pixels; pr.min_length = min_length;
+        const int rc = uvs_lt_detect_track(lt_, 1, &it, &pr, det_seg.data(), det_width2.data(), det_info.data(), &last_detect, desc.data(),
+                                           line_status.data(), det_prev_index.data(), distance.data(), &last);
+        if (rc != UVS_OK) { last_error = uvs_lt_last_error(lt_); n = 0; return rc; }
+        n = (size_t)last_detect.n_returned;
+        return UVS_OK;
+    }
+
+    // :379-385
+    int finishFrame(size_t n, const double* segments) override {
+        int rc = UVS_OK;
         if (vp_ && n > 1) {
             std::vector<KeyLineEnds> lines(n);
             for (size_t l = 0; l < n; ++l) lines[l] = {segments[4 * l], segments[4 * l + 1], segments[4 * l + 2], segments[4 * l + 3]};
@@ -139,13 +191,6 @@ public:
         }
         return UVS_OK;
     }
-
-    void reset() { LineFeatureTrackerBook::reset(); (void)uvs_lt_reset(lt_, 0); }
-
-    uvs_lt_result last{};
-    std::vector<uint8_t> desc;               // [n][32] of the last frame
-    std::vector<int32_t> line_status, distance;
-    std::string last_error;
 
 private:
     uvs_lt_tracker* lt_ = nullptr;
