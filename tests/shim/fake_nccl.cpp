@@ -3,7 +3,7 @@
 // solver code under test is byte for byte what runs over xGMI: the per-rank MAX slots of the first exchange, k_large_sum_bsums and the
 // second (5-scalar) all-reduce execute for real; only the transport differs.
 //
-// Exports the five entry points the solver binds (csrc/uvs_solver.hip: RcclApi):  ncclGetUniqueId, ncclCommInitRank, ncclAllReduce,
+// Exports the five entry points the solver binds (csrc/uvs_large.hip: RcclApi):  ncclGetUniqueId, ncclCommInitRank, ncclAllReduce,
 // ncclCommDestroy, ncclGetErrorString.  Transport: a POSIX shared-memory segment named in the unique id; an all-reduce waits for the
 // stream, copies the buffer to the rank's slot, meets the other ranks at a barrier, adds the slots IN RANK ORDER (every rank gets the
 // same bits, as a ring all-reduce of RCCL does) and copies the sum back.  Every wait has a deadline, so a lost peer is an error, not a hang.

@@ -8,7 +8,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry      # noqa: E402
 
-REBUILT_BY_VARIANT = {"uvs_solver", "uvs_solve512", "uvs_solve_dstep256", "uvs_pack"}      # the persistent kernel's units and the packing that feeds it: what a variant varies
+CSRC = os.path.join(ROOT, "uv-slam_amd", "csrc")
+
+
+def _includes(path, seen=None):
+    """The csrc headers a source reaches through its #include "..." lines."""
+    seen = set() if seen is None else seen
+    with open(path) as f:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', f.read(), re.M):
+            if name not in seen and os.path.exists(os.path.join(CSRC, name)):
+                seen.add(name); _includes(os.path.join(CSRC, name), seen)
+    return seen
+
+
+# what a variant varies: every unit built from the persistent kernel's header or from the blob layout, and the packing that feeds them
+REBUILT_BY_VARIANT = {row[0] for row in entry.UNITS if {"uvs_solve_kernel.h", "uvs_layout.h"} & _includes(os.path.join(CSRC, row[0] + ".hip"))} | {"uvs_pack"}
 
 
 def test_unit_table_is_the_hip_sources():

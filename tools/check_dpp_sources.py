@@ -3,7 +3,7 @@ does not see: a DPP operand must not be read within two wait states of the VALU 
 (trsv_dpp_source); this script checks the emitted ISA: for every such instruction, no VALU write of its DPP source in the two wait states before it.
 
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -mllvm -disable-machine-licm -S --cuda-device-only uv-slam_amd/csrc/uvs_solve512.hip -o /tmp/s512.s
-       python tools/check_dpp_sources.py /tmp/s512.s        (likewise uvs_solver.hip and uvs_solve_dstep256.hip: the three units that hold the kernel)"""
+       python tools/check_dpp_sources.py /tmp/s512.s        (likewise uvs_solver.hip and uvs_solve_dstep256.hip: the three units that instantiate the kernel)"""
 import re
 import sys
 

@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 #include "uvs_solve_kernel.h"
-#include "uvs_hip_buf.h"
+#include "uvs_solver_handle.h"      // EvalScratch: the staging of an evaluation, owned by the handle
 
 namespace uvsdev {
 
@@ -104,13 +104,6 @@ __global__ __launch_bounds__(NT) void k_evaluate(char* blob, double* ws, KOpts o
     block_reduce(sh, s4, &mx);
     if (tid == 0) out.cost[0] = s4[0];
 }
-
-// device + pinned-host staging of one evaluation, kept by the solver handle (no allocation on the per-call path once it has grown)
-struct EvalScratch {
-    DevBuf<double> d;                          // device
-    PinnedBuf<double> h;                       // pinned host
-    std::vector<double> work[11];              // host work arrays of the marginalization, kept between calls (a fresh 160 KB vector per call is an mmap / page-fault / munmap round trip)
-};
 
 // host driver: blob of window 0 must already be on the device (uvs_batch_upload)
 // `view` (marginalization): *out receives POINTERS into the pinned staging buffer instead of copies into caller arrays (valid until the next

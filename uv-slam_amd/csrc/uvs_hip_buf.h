@@ -1,5 +1,5 @@
 // uvs_hip_buf.h -- host-only owners of the HIP memory of the library's handles and the one way a failed HIP call becomes a handle's error
-// text.  Included by every translation unit that owns a handle: uvs_solver.hip directly, the front-end units through uvs_handle.h (which adds
+// text.  Included by every translation unit that owns a handle: the solver's units through uvs_solver_handle.h, the front-end units through uvs_handle.h (which adds
 // what those handles share besides their buffers).  Nothing here runs on the device.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -40,7 +40,7 @@ enum { LC_RADIUS = 0, LC_DECR, LC_COST, LC_GMAX, LC_XNORM, LC_FRAME_X2, LC_IT, L
 struct LargeCtl { const double* ctl; int rank, nranks; };
 // debug timeline of k_large_chunks (KOpts::debug == 7, UVS_LARGE_PROF=<file> in uvs_large_solve_fused): per workgroup 8 stamps of the 100 MHz wall clock
 // {start, state + rotations staged, first chunk done, all chunks done, parts summed, partial written, -, chunks taken}; the LAST launch wins
-__device__ long long g_large_prof[1024 * 8];
+inline namespace UVS_UNIT { __device__ long long g_large_prof[1024 * 8]; }
 #define UVS_LPROF(k) do { if (o.debug == 7 && tid == 0 && blockIdx.x < 1024) g_large_prof[8 * blockIdx.x + (k)] = wall_clock64(); } while (0)      // ctl == nullptr: the step-wise API (host-side control, arguments as given)
 
 

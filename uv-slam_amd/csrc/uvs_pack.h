@@ -2,7 +2,7 @@
 //
 // Host-only (uvs_pack.cpp): the unit includes the C ABI header, uvs_layout.h and the standard library, nothing of HIP, and compiles with a plain
 // g++ -std=c++17 as well as with hipcc's clang -- tools/pack_dump.cpp links it alone (tests/test_pack_blob.py, sanitizer runs).  Everything that talks
-// to a device (upload_windows, the worker pool, the handle) stays in uvs_solver.hip.  The gather-group constants come from uvs_layout.h, so a variant
+// to a device (upload_windows in uvs_solver.hip; the worker pool and the handle, uvs_solver_handle.h) stays outside.  The gather-group constants come from uvs_layout.h, so a variant
 // library (tools/ab/build_variant.sh -DUVS_GLANES=...) rebuilds this unit with its kernels; the names are hidden so that two libraries in one
 // process each keep their own packing.
 #pragma once

@@ -2,8 +2,8 @@
 // wavefronts per SIMD, 256 registers per lane, waves 0..3 evaluate observations and waves 4..7 own the gather groups (ROLES).
 //
 // It is its own translation unit because the workgroup size is a compile-time constant of the kernel header (LDS map, loop strides, batch
-// sizes): everything else in the library -- the landmark-sharded kernels, k_evaluate, k_marg_linearize, the 256-thread k_solve that
-// UVS_KSOLVE_NT=256 selects for A/B runs -- is built with 256 threads in uvs_solver.hip.  The namespace is renamed so that the two
+// sizes): everything else in the library -- the landmark-sharded kernels (uvs_large.hip), k_evaluate and k_marg_linearize (uvs_marginalize.hip), the 256-thread k_solve that
+// UVS_KSOLVE_NT=256 selects for A/B runs (uvs_solver.hip) -- is built with 256 threads.  The namespace is renamed so that the two
 // instantiations do not collide at link time; the blob and workspace layout (uvs_layout.h: UVS_GT = 256 gather threads either way), the
 // kernel arguments and the report are the same, so the host side only picks which launcher to call (launch_solve).
 //
@@ -12,7 +12,8 @@
 // -mllvm -sink-insts-to-avoid-spills takes another dozen away (34).
 #define UVS_NT 512
 #define UVS_ALLOW_EXPERIMENTAL_NT 1
-#define UVS_SOLVE_KERNEL_ONLY 1
+#define UVS_EMIT_K_SOLVE 1
+#define UVS_EMIT_K_SOLVE_DSTEP 1
 #define UVS_CHUNK_TOUCH 1
 #define UVS_TU_512 1
 #define uvsdev uvsdev512
@@ -24,13 +25,7 @@ using namespace uvsdev512;
 extern "C" {
 // block table of the output-stationary gather (the __constant__ copies of this translation unit) + the LDS opt-in; once per device
 int uvs_k_solve512_init(const unsigned char* fa, const unsigned char* fb, int n) {
-    if (n != UVS_NBLK) return UVS_ERR_INVALID_ARG;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, n) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, n) != hipSuccess) return UVS_ERR_HIP;
-    if (hipFuncSetAttribute((const void*)k_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
-    if (hipFuncSetAttribute((const void*)k_solve_dstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
-    if (hipFuncSetAttribute((const void*)k_large_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
-    if (hipFuncSetAttribute((const void*)k_large_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
-    return UVS_OK;
+    return unit_init(fa, fb, n, {(const void*)k_solve, (const void*)k_solve_dstep, (const void*)k_large_chunks, (const void*)k_large_solve});
 }
 // k_large_chunks with 512 threads per workgroup (grid = chunk workgroups + the frame-terms workgroup, as for the 256-thread kernel)
 int uvs_k_large_chunks512_launch(int grid, hipStream_t stream, char* blob, double* ws, const void* kopts, size_t kopts_bytes, const double* state, int sel, int first, double radius,

@@ -1,8 +1,7 @@
 // uvs_solve_dstep256.hip -- k_solve_dstep (uvs_solve_kernel.h: the persistent LM kernel's debug-step instantiation behind uvs_debug_step) with 256 threads
 // per workgroup, the build of the 256-thread k_solve in uvs_solver.hip.  Its own translation unit so that the product kernel's register figures stay those of
 // a module without it (the two would share the noinline factorization calls).  The namespace is renamed as in uvs_solve512.hip.
-#define UVS_SOLVE_KERNEL_ONLY 1
-#define UVS_DSTEP_ONLY 1
+#define UVS_EMIT_K_SOLVE_DSTEP 1
 #define uvsdev uvsdev256d
 #include "uvs_solve_kernel.h"
 
@@ -11,10 +10,7 @@ using namespace uvsdev256d;
 extern "C" {
 // block table of the output-stationary gather (this translation unit's __constant__ copies) + the LDS opt-in; once per device
 int uvs_k_solve256d_init(const unsigned char* fa, const unsigned char* fb, int n) {
-    if (n != UVS_NBLK) return UVS_ERR_INVALID_ARG;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, n) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, n) != hipSuccess) return UVS_ERR_HIP;
-    if (hipFuncSetAttribute((const void*)k_solve_dstep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
-    return UVS_OK;
+    return unit_init(fa, fb, n, {(const void*)k_solve_dstep});
 }
 // kopts / ds: the caller's uvsdev::KOpts / uvsdev::DebugStep (same definitions, other namespace); window 0 of the uploaded batch
 int uvs_k_solve256d_launch(hipStream_t stream, char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,

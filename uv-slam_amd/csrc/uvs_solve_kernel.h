@@ -15,6 +15,7 @@
 //   * the reduced system is factored by a blocked right-looking Cholesky on 16x16 LDS blocks.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <utility>
 #include "../../include/uvs_solver.h"
 #include "uvs_layout.h"
@@ -22,6 +23,12 @@
 
 namespace uvsdev {
 
+// The device globals of the kernel headers (g_lin_tl, c_blk_fa, c_blk_fb here, g_large_prof in uvs_large_kernel.h) keep external linkage: the host finds them by name, and with
+// internal linkage the compiler drops the stores to a log that no device code reads.  So that several units can be built from the headers and linked into one library, each unit
+// names an inline namespace for its copies.  (uvs_solve512.hip and uvs_solve_dstep256.hip rename the whole namespace and need no name of their own.)
+#ifndef UVS_UNIT
+#define UVS_UNIT unit
+#endif
 
 // threadIdx.x behind an optimization barrier.  With the plain intrinsic the compiler hoists every per-lane address computation of the
 // LM iteration (base + k * tid ...) out of the iteration loop, keeps ~50 of them alive across the whole loop -- the kernel sits at the
@@ -105,7 +112,7 @@ enum { P_SETUP = 0, P_OBS, P_LMPREP, P_GATHER, P_ASSEMBLE, P_CHOL, P_TRSV, P_BAC
 static constexpr size_t LDS_BYTES = (size_t)L_TOTAL * 8;
 // debug == 5 (UVS_DEBUG_LIN_TIMELINE, first window of a launch): every wave logs (stamp id, clock) pairs of the linearization's inner steps; tools/lin_timeline.py prints them
 static constexpr int TL_PER_WAVE = 4096;
-__device__ long long g_lin_tl[8 * TL_PER_WAVE * 2];
+inline namespace UVS_UNIT { __device__ long long g_lin_tl[8 * TL_PER_WAVE * 2]; }
 #define UVS_TLOG(c, id) do { if ((c).o.debug == 5 && (threadIdx.x & 63) == 0 && blockIdx.x == 0) { const int w_ = threadIdx.x >> 6; const int n_ = (int)(c).sh[L_WPROF + w_]; \
     if (n_ < TL_PER_WAVE) { g_lin_tl[2 * (w_ * TL_PER_WAVE + n_)] = (id); g_lin_tl[2 * (w_ * TL_PER_WAVE + n_) + 1] = clock64(); (c).sh[L_WPROF + w_] = (double)(n_ + 1); } } } while (0)
 
@@ -122,8 +129,10 @@ struct KOpts {   // device copy of uvs_options
     int redamp;      // 1 (default): a rejected step is followed by a re-damping of the stored linearization; 0 (UVS_REDAMP=0 at uvs_create): by a new linearization
 };
 
+inline namespace UVS_UNIT {      // (every unit has its own copies, filled by its unit_init below)
 __constant__ unsigned char c_blk_fa[UVS_NBLK];
 __constant__ unsigned char c_blk_fb[UVS_NBLK];
+}
 
 UVS_DEV int sidx(int i, int j) {   // i >= j, padded index space
     const int bi = i >> 4, bj = j >> 4;
@@ -3259,7 +3268,7 @@ UVS_DEV void k_solve_body(char* blobs, const long long* blob_off, double* ws_all
         ((DevWin*)blob)->cur_sel = cur;
     }
 }
-#ifndef UVS_DSTEP_ONLY
+#ifdef UVS_EMIT_K_SOLVE
 __global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
                                               KOpts o, uvs_report* reports, DebugOut dbg) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
@@ -3268,7 +3277,7 @@ __global__ __launch_bounds__(NT) void k_solve(char* blobs, const long long* blob
 #endif
 // (not beside the 256-thread k_solve of uvs_solver.hip: the two kernels share the noinline factorization calls, and a second caller moves the product kernel's
 // register figures; uvs_solve_dstep256.hip instantiates it alone)
-#ifndef UVS_NO_DSTEP
+#ifdef UVS_EMIT_K_SOLVE_DSTEP
 __global__ __launch_bounds__(NT) void k_solve_dstep(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off,
                                                     KOpts o, uvs_report* reports, DebugStep ds) {
     extern __shared__ __attribute__((aligned(16))) double sh[];
@@ -3277,67 +3286,13 @@ __global__ __launch_bounds__(NT) void k_solve_dstep(char* blobs, const long long
 }
 #endif
 
-#ifndef UVS_SOLVE_KERNEL_ONLY      // (uvs_solve512.hip instantiates k_solve alone)
-// ------------------------------------------------------------------ marginalization on the device (MARGIN_OLD)
-// The window here is the SUB-window of the factors that touch the departing frame 0 (marginalization_factor.cpp:174-297 via estimator.cpp:1002-1135: IMU block 0,
-// the points anchored in frame 0, the lines that start there without their anchor observation, the prior), packed with a FREE extrinsic (the reference's prior
-// keeps para_Ex_Pose whether or not the solve estimates it).  One linearization of it at the post-solve state with an infinite trust-region radius IS the
-// assembly A = sum J^T J, b = sum J^T r of the reference followed by the elimination of every dropped landmark block: the kernel's reduced frame system.
-// out = [S lower packed (i >= j: i (i + 1) / 2 + j, padded indices) | g[176] | {cost, number of lanes with a landmark pivot <= 1e-8, 0...}[8]].
-// The host eliminates the 15 dofs of frame 0 from it and factors the rest (csrc/uvs_marg.h: marg_finish).
-static constexpr int MARG_OUT = UVS_RD * (UVS_RD + 1) / 2 + UVS_RD + 8;
-UVS_DEV void marg_linearize_body(char* blob, double* ws, KOpts o, double* out, double* sh) {
-    const int tid = lane_tid();
-    Ctx c;
-    c.hdr = (DevWinK*)blob; c.bd = (const double*)blob; c.bi = (const int*)blob; c.ws = ws; c.sh = sh; c.o = o; c.o.debug = 0;
-    DevWinK& h = *c.hdr;
-    if (tid < UVS_XDIM) sh[L_X + tid] = c.bd[h.d_frames + tid];
-    for (int k = tid; k < h.n_points; k += NT) c.ws[h.w_invd0 + k] = c.bd[h.d_invd + k];
-    for (int k = tid; k < 4 * h.n_lines; k += NT) c.ws[h.w_line0 + k] = c.bd[h.d_line + k];
-    for (int k = tid; k < h.n_lines; k += NT) line_trig(c.bd + h.d_line + 4 * k, c.ws + h.w_ltrig0 + 8 * k);
-    c.ltrig_ok = 1;
-    if (tid < 24) sh[L_PROF + tid] = 0.0;
-    if (tid < 8) sh[L_WPROF + tid] = 0.0;
-    setup_window(c, (double*)blob);
-    __syncthreads();
-    GAcc gacc;
-    linearize(c, sh + L_X, c.ws + h.w_invd0, c.ws + h.w_line0, true, o.r0, 0, gacc);
-    // smallest pivot of the UNDAMPED landmark blocks (the reference cuts eigenvalues of A_mm at 1e-8: a landmark block that is not safely regular
-    // sends the caller to the host path, which applies that cut)
-    double worst = 1e300;
-    for (int k = tid; k < h.n_points; k += NT) if (c.bi[h.i_pt_beg + k + 1] > c.bi[h.i_pt_beg + k]) worst = fmin(worst, c.ws[h.w_pt_x + 4 * (size_t)k + 3]);
-    for (int k = tid; k < h.n_lines; k += NT) {
-        if (c.bi[h.i_ln_beg + k + 1] == c.bi[h.i_ln_beg + k]) continue;
-        const double* H = c.ws + h.w_ln_x + UVS_LN_X * (size_t)k + 12;      // lower packed (0,0)(1,0)(1,1)(2,0)...
-        double L[10];
-        const double p0 = H[0]; L[0] = sqrt(fmax(p0, 1e-300));
-        L[1] = H[1] / L[0]; const double p1 = H[2] - L[1] * L[1]; L[2] = sqrt(fmax(p1, 1e-300));
-        L[3] = H[3] / L[0]; L[4] = (H[4] - L[3] * L[1]) / L[2]; const double p2 = H[5] - L[3] * L[3] - L[4] * L[4]; L[5] = sqrt(fmax(p2, 1e-300));
-        L[6] = H[6] / L[0]; L[7] = (H[7] - L[6] * L[1]) / L[2]; L[8] = (H[8] - L[6] * L[3] - L[7] * L[4]) / L[5];
-        const double p3 = H[9] - L[6] * L[6] - L[7] * L[7] - L[8] * L[8];
-        worst = fmin(worst, fmin(fmin(p0, p1), fmin(p2, p3)));
-    }
-    double s4[4] = {(worst > 1e-8) ? 0.0 : 1.0, 0, 0, 0}, mx = 0.0;      // lanes that hold a landmark block with a pivot at or under the reference's eps (marginalization_factor.h:70)
-    block_reduce(sh, s4, &mx);
-    for (int t = tid; t < UVS_RD * (UVS_RD + 1) / 2; t += NT) {
-        int i = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-        while ((i + 1) * (i + 2) / 2 <= t) ++i;
-        while (i * (i + 1) / 2 > t) --i;
-        const int j = t - i * (i + 1) / 2;
-        out[t] = sh[L_S + sidx(i, j)];
-    }
-    if (tid < UVS_RD) out[UVS_RD * (UVS_RD + 1) / 2 + tid] = sh[L_G + tid];
-    if (tid == 0) { double* sc = out + UVS_RD * (UVS_RD + 1) / 2 + UVS_RD; sc[0] = sh[L_CTRL + C_COST]; sc[1] = s4[0]; }
+// The device setup every unit built from this header owns: its own copy of the block table of the output-stationary gather (c_blk_fa / c_blk_fb above) and the
+// dynamic-LDS opt-in of its kernels -- a per-device function attribute, set for the current device at every uvs_create (idempotent).  One init function per unit calls this.
+// (static: it names this unit's own copies of the table)
+static int unit_init(const unsigned char* fa, const unsigned char* fb, int n, std::initializer_list<const void*> kernels) {
+    if (n != UVS_NBLK) return UVS_ERR_INVALID_ARG;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fa), fa, n) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(c_blk_fb), fb, n) != hipSuccess) return UVS_ERR_HIP;
+    for (const void* fn : kernels) if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES) != hipSuccess) return UVS_ERR_HIP;
+    return UVS_OK;
 }
-__global__ __launch_bounds__(NT) void k_marg_linearize(char* blob, double* ws, KOpts o, double* out) {
-    extern __shared__ __attribute__((aligned(16))) double sh[];
-    marg_linearize_body(blob, ws, o, out, sh);
-}
-// the same for a BATCH of sub-windows (uvs_marginalize_batch): one workgroup per window, blobs / workspaces through offset tables like k_solve, outputs MARG_OUT doubles apart
-__global__ __launch_bounds__(NT) void k_marg_linearize_batch(char* blobs, const long long* blob_off, double* ws_all, const long long* ws_off, KOpts o, double* out_all) {
-    extern __shared__ __attribute__((aligned(16))) double sh[];
-    marg_linearize_body(blobs + blob_off[blockIdx.x], ws_all + ws_off[blockIdx.x], o, out_all + (size_t)MARG_OUT * blockIdx.x, sh);
-}
-
-#endif
 }  // namespace uvsdev
