@@ -1197,6 +1197,72 @@ double uvs_lt_last_detect_device_ms(const uvs_lt_tracker *lt);
 int uvs_lt_debug_detect(uvs_lt_tracker *lt, const uint8_t *image, int width, int height, const uvs_lt_det_params *params, uint8_t *blur,
                         uint32_t *grad, uint8_t *sector_a, uint8_t *sector_b, int32_t *name_a, int32_t *name_b, uint8_t *vote);
 
+/* ---- place recognition of loop closure (reference pose_graph/src/pose_graph.cpp:304-386 detectLoop; ThirdParty/DBoW/TemplatedVocabulary.h
+ * transform, TemplatedDatabase.h add / queryL1, BowVector.cpp addWeight / normalize) ----
+ * Which old keyframe to try: a vocabulary tree over 256-bit BRIEF descriptors, the tf-idf bag-of-words vector of a keyframe, and the L1 query
+ * of an append-only database of such vectors.  Everything below is integer arithmetic or FP64 in a stated order, so a keyframe gives the same
+ * bits alone or in a batch, from run to run and on any machine; tests/pr_ref.py restates it.
+ *   vocabulary  the caller's, in the arrays of the reference's binary file (ThirdParty/VocabularyBinary.hpp: records {nodeId, parentId, weight,
+ *               descriptor[4]} and {nodeId, wordId}); the root is node 0 and has no record; a node's children are in the order of their
+ *               records.  Descriptor bit i is bit (i & 63) of word (i >> 6), the layout of uvs_kf_extract's desc.  Only weightingType 0
+ *               (TF_IDF) and scoringType 0 (L1_NORM).
+ *   transform   a descriptor descends from the root, at every inner node to the child of the smallest Hamming distance, a tie to the earlier
+ *               child; the leaf it ends at gives (word id, weight).  The vector of a keyframe: words of weight <= 0 dropped; per word
+ *               v = w, then v += w once per further occurrence; norm = the sum of |v| in ascending word id, one add after the other; every v
+ *               divided by norm when norm > 0.  Sorted by word id.
+ *   query       entry e of a database of n entries is eligible iff e < max_id || max_id == -1 || e == n - 1.  Its raw score is
+ *               s(e) = sum over the words it shares with the query, in ascending word id, of |q - d| - |q| - |d|, starting from the first
+ *               term; an entry that shares no word is no result.  Results in ascending s, a tie to the lower entry id (the reference's
+ *               std::sort leaves ties open: this is the library's definition), cut to max_results (0: all), Score = -s / 2.
+ *   detect      detectLoop: query(4, frame_index - 50), then add; a loop iff Score[0] > 0.05 and some i >= 1 has Score[i] > 0.015; when
+ *               frame_index > 50 as well, the smallest id among result 0 (whatever its score) and the results i >= 1 with Score[i] > 0.015;
+ *               otherwise -1.
+ * No CPU path: uvs_pr_create fails with UVS_ERR_NO_DEVICE without a GPU (uvs_pr_check_vocabulary needs none). */
+#define UVS_PR_MAX_K 16                       /* most children of a node: one lane of a 16-lane group each (DBoW2 vocabularies in use have k = 10) */
+#define UVS_PR_MAX_L 16                       /* largest depth L */
+#define UVS_PR_MAX_FRAMES 64                  /* most keyframes of one uvs_pr_transform / uvs_pr_add / uvs_pr_query call */
+#define UVS_PR_DETECT_RESULTS 4               /* results detectLoop asks for */
+typedef struct uvs_place_recognizer uvs_place_recognizer;  /* opaque: the vocabulary and the database on the device, staging, stream */
+
+/* Host only.  node_id / parent_id / weight / descriptor[][4]: the n_nodes node records; word_node_id / word_id: the n_words word records.
+ * UVS_ERR_UNSUPPORTED: a weighting or scoring other than 0.  UVS_ERR_INVALID_ARG with a text in message (message_capacity bytes, may be
+ * NULL): a null array, k outside 1 .. UVS_PR_MAX_K, L outside 1 .. UVS_PR_MAX_L, a node id outside 1 .. n_nodes or given twice, a parent
+ * outside 0 .. n_nodes, a cycle, a node deeper than L, more than UVS_PR_MAX_K children, a word id outside 0 .. n_words - 1 or given twice,
+ * a node with two words, a leaf without a word, a word on an inner node, a root without children, a weight that is negative or not finite.
+ * Leaves may sit above depth L, and ids need not be contiguous among siblings. */
+int uvs_pr_check_vocabulary(int k, int L, int scoring_type, int weighting_type, int n_nodes, const int32_t *node_id, const int32_t *parent_id,
+                            const double *weight, const uint64_t *descriptor, int n_words, const int32_t *word_node_id, const int32_t *word_id,
+                            char *message, int message_capacity);
+/* max_features: most descriptors of a keyframe, 1 .. UVS_LC_MAX_OLD (what uvs_kf_extract returns at most).  initial_entries >= 1: the
+ * database's first capacity; it grows by doubling (a new buffer, a device-to-device copy, the old one freed).  The checks of
+ * uvs_pr_check_vocabulary apply; UVS_ERR_CAPACITY: max_features above its bound. */
+int uvs_pr_create(int device, int k, int L, int scoring_type, int weighting_type, int n_nodes, const int32_t *node_id, const int32_t *parent_id,
+                  const double *weight, const uint64_t *descriptor, int n_words, const int32_t *word_node_id, const int32_t *word_id,
+                  int max_features, int initial_entries, uvs_place_recognizer **out);
+void uvs_pr_destroy(uvs_place_recognizer *pr);
+const char *uvs_pr_last_error(const uvs_place_recognizer *pr);
+/* Entries in the database / forget them all (the capacity stays). */
+int uvs_pr_size(const uvs_place_recognizer *pr);
+int uvs_pr_clear(uvs_place_recognizer *pr);
+/* n_features[n_frames]; descriptors[][4] PACKED over the frames in order.  words_out[] / weights_out[]: one per descriptor, packed alike
+ * (stop words included).  bow_n[n_frames]; bow_words / bow_values are STRIDED: frame f owns entries f * max_features .. + bow_n[f] - 1.
+ * Changes no state.  UVS_ERR_INVALID_ARG: null pointer, n_frames < 1, a negative count; UVS_ERR_CAPACITY: n_frames > UVS_PR_MAX_FRAMES or
+ * a count above max_features.  An empty frame (n_features 0) is valid everywhere below. */
+int uvs_pr_transform(uvs_place_recognizer *pr, int n_frames, const int32_t *n_features, const uint64_t *descriptors, int32_t *words_out,
+                     double *weights_out, int32_t *bow_n, int32_t *bow_words, double *bow_values);
+/* Appends the vectors of n_frames keyframes in order; entry_ids[n_frames] = their entry ids (the order of addition since the last clear). */
+int uvs_pr_add(uvs_place_recognizer *pr, int n_frames, const int32_t *n_features, const uint64_t *descriptors, int32_t *entry_ids);
+/* n_frames queries against the database as it is; changes no state.  max_results >= 0 (0: all); max_id[n_frames].  n_results[n_frames];
+ * ids / scores are STRIDED by (max_results > 0 ? max_results : uvs_pr_size()) per frame. */
+int uvs_pr_query(uvs_place_recognizer *pr, int n_frames, const int32_t *n_features, const uint64_t *descriptors, int max_results,
+                 const int32_t *max_id, int32_t *n_results, int32_t *ids, double *scores);
+/* detectLoop for one keyframe: the query, the add (one transform serves both), the gates.  ids / scores: UVS_PR_DETECT_RESULTS entries. */
+int uvs_pr_detect(uvs_place_recognizer *pr, int n_features, const uint64_t *descriptors, int frame_index, int32_t *loop_index,
+                  int32_t *n_results, int32_t *ids, double *scores);
+/* HIP-event time of the last successful call on the handle's stream (milliseconds): part 0 the whole call, 1 the transform (upload, descent,
+ * vector), 2 the query (scoring, download); a part the call did not run is 0. */
+double uvs_pr_last_device_ms(const uvs_place_recognizer *pr, int part);
+
 #ifdef __cplusplus
 }
 #endif

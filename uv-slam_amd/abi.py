@@ -808,3 +808,69 @@ def lt_det_items(items):
         arr[b].stream = int(d.get("stream", 0))
         arr[b].height, arr[b].width = im.shape
     return arr, keep
+
+
+# ---- place recognition of loop closure (uvs_pr_*, include/uvs_solver.h) -------------------------------------------------
+PR_MAX_K = 16
+PR_MAX_L = 16
+PR_MAX_FRAMES = 64
+PR_DETECT_RESULTS = 4
+PR_HEADER = np.dtype([("k", "<i4"), ("L", "<i4"), ("scoring", "<i4"), ("weighting", "<i4"), ("n_nodes", "<i4"), ("n_words", "<i4")])      # 24 bytes
+PR_NODE = np.dtype([("node_id", "<i4"), ("parent_id", "<i4"), ("weight", "<f8"), ("descriptor", "<u8", (4,))])                             # 48 bytes
+PR_WORD = np.dtype([("node_id", "<i4"), ("word_id", "<i4")])                                                                               # 8 bytes
+
+
+def load_vocabulary(path):
+    """The reference's binary vocabulary (ThirdParty/VocabularyBinary.hpp: a 24-byte header k, L, scoringType, weightingType, nNodes, nWords;
+    nNodes records {int32 nodeId, int32 parentId, double weight, uint64 descriptor[4]}; nWords records {int32 nodeId, int32 wordId}) ->
+    dict(k, L, scoring, weighting, node_id, parent_id, weight, descriptor [n, 4] uint64, word_node_id, word_id).  The root is node 0 and has
+    no record; descriptor bit i is bit (i & 63) of word (i >> 6)."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < PR_HEADER.itemsize:
+        raise ValueError(f"{path}: shorter than the 24-byte header")
+    h = np.frombuffer(raw, PR_HEADER, 1)[0]
+    nn, nw = int(h["n_nodes"]), int(h["n_words"])
+    if nn < 0 or nw < 0 or len(raw) != PR_HEADER.itemsize + nn * PR_NODE.itemsize + nw * PR_WORD.itemsize:
+        raise ValueError(f"{path}: {len(raw)} bytes do not hold {nn} node records and {nw} word records")
+    nodes = np.frombuffer(raw, PR_NODE, nn, PR_HEADER.itemsize)
+    words = np.frombuffer(raw, PR_WORD, nw, PR_HEADER.itemsize + nn * PR_NODE.itemsize)
+    return dict(k=int(h["k"]), L=int(h["L"]), scoring=int(h["scoring"]), weighting=int(h["weighting"]),
+                node_id=nodes["node_id"].copy(), parent_id=nodes["parent_id"].copy(), weight=nodes["weight"].copy(),
+                descriptor=nodes["descriptor"].copy(), word_node_id=words["node_id"].copy(), word_id=words["word_id"].copy())
+
+
+def save_vocabulary(path, voc):
+    """The inverse of load_vocabulary, byte for byte."""
+    nodes = np.zeros(len(voc["node_id"]), PR_NODE)
+    nodes["node_id"], nodes["parent_id"], nodes["weight"] = voc["node_id"], voc["parent_id"], voc["weight"]
+    nodes["descriptor"] = np.asarray(voc["descriptor"], np.uint64).reshape(-1, 4)
+    words = np.zeros(len(voc["word_id"]), PR_WORD)
+    words["node_id"], words["word_id"] = voc["word_node_id"], voc["word_id"]
+    h = np.zeros(1, PR_HEADER)
+    h["k"], h["L"], h["scoring"], h["weighting"], h["n_nodes"], h["n_words"] = voc["k"], voc["L"], voc.get("scoring", 0), voc.get("weighting", 0), len(nodes), len(words)
+    with open(path, "wb") as f:
+        f.write(h.tobytes()); f.write(nodes.tobytes()); f.write(words.tobytes())
+
+
+def pr_vocabulary_args(voc):
+    """(the arguments k .. word_id of uvs_pr_check_vocabulary / uvs_pr_create, keepalive) from a load_vocabulary dict."""
+    a = dict(node_id=np.ascontiguousarray(voc["node_id"], np.int32), parent_id=np.ascontiguousarray(voc["parent_id"], np.int32),
+             weight=np.ascontiguousarray(voc["weight"], np.float64), descriptor=np.ascontiguousarray(voc["descriptor"], np.uint64).reshape(-1, 4),
+             word_node_id=np.ascontiguousarray(voc["word_node_id"], np.int32), word_id=np.ascontiguousarray(voc["word_id"], np.int32))
+    if not (len(a["node_id"]) == len(a["parent_id"]) == len(a["weight"]) == len(a["descriptor"])) or len(a["word_node_id"]) != len(a["word_id"]):
+        raise ValueError("vocabulary: arrays of unequal length")
+    args = [int(voc["k"]), int(voc["L"]), int(voc.get("scoring", 0)), int(voc.get("weighting", 0)), len(a["node_id"]),
+            a["node_id"].ctypes.data_as(c_i32_p), a["parent_id"].ctypes.data_as(c_i32_p), _dp(a["weight"]), a["descriptor"].ctypes.data_as(c_u64_p),
+            len(a["word_id"]), a["word_node_id"].ctypes.data_as(c_i32_p), a["word_id"].ctypes.data_as(c_i32_p)]
+    return args, a
+
+
+def pr_frames(frames):
+    """(n_features int32 [n], descriptors uint64 [sum, 4]) from a list of [n_f, 4] uint64 descriptor arrays (empty ones allowed)."""
+    ds = [np.ascontiguousarray(d, dtype=np.uint64).reshape(-1, 4) for d in frames]
+    nf = np.array([len(d) for d in ds], np.int32)
+    desc = np.ascontiguousarray(np.concatenate(ds) if ds else np.zeros((0, 4), np.uint64))
+    if len(desc) == 0:
+        desc = np.zeros((1, 4), np.uint64)
+    return nf, desc

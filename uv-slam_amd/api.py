@@ -30,6 +30,8 @@ EXPORTS = [
     "uvs_lt_create", "uvs_lt_destroy", "uvs_lt_last_error", "uvs_lt_reset", "uvs_lt_track", "uvs_lt_match", "uvs_lt_last_device_ms", "uvs_lt_debug_line",
     "uvs_lt_gauss_tables",
     "uvs_lt_detect", "uvs_lt_detect_track", "uvs_lt_last_detect_device_ms", "uvs_lt_debug_detect",
+    "uvs_pr_check_vocabulary", "uvs_pr_create", "uvs_pr_destroy", "uvs_pr_last_error", "uvs_pr_size", "uvs_pr_clear", "uvs_pr_transform", "uvs_pr_add",
+    "uvs_pr_query", "uvs_pr_detect", "uvs_pr_last_device_ms",
 ]
 
 
@@ -174,6 +176,21 @@ def lib():
         L.uvs_lt_debug_detect.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, C.POINTER(abi.LtDetParams), abi.c_u8_p, C.POINTER(C.c_uint32), abi.c_u8_p,
                                           abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_u8_p]
         L.uvs_lt_debug_detect.restype = C.c_int
+        voc_args = [C.c_int] * 5 + [abi.c_i32_p, abi.c_i32_p, abi.c_double_p, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p]
+        L.uvs_pr_check_vocabulary.argtypes = voc_args + [C.c_char_p, C.c_int]; L.uvs_pr_check_vocabulary.restype = C.c_int
+        L.uvs_pr_create.argtypes = [C.c_int] + voc_args + [C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_pr_create.restype = C.c_int
+        L.uvs_pr_destroy.argtypes = [C.c_void_p]; L.uvs_pr_destroy.restype = None
+        L.uvs_pr_last_error.argtypes = [C.c_void_p]; L.uvs_pr_last_error.restype = C.c_char_p
+        L.uvs_pr_size.argtypes = [C.c_void_p]; L.uvs_pr_size.restype = C.c_int
+        L.uvs_pr_clear.argtypes = [C.c_void_p]; L.uvs_pr_clear.restype = C.c_int
+        L.uvs_pr_transform.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_u64_p, abi.c_i32_p, abi.c_double_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p]
+        L.uvs_pr_transform.restype = C.c_int
+        L.uvs_pr_add.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_u64_p, abi.c_i32_p]; L.uvs_pr_add.restype = C.c_int
+        L.uvs_pr_query.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p]
+        L.uvs_pr_query.restype = C.c_int
+        L.uvs_pr_detect.argtypes = [C.c_void_p, C.c_int, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p]
+        L.uvs_pr_detect.restype = C.c_int
+        L.uvs_pr_last_device_ms.argtypes = [C.c_void_p, C.c_int]; L.uvs_pr_last_device_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -1201,3 +1218,99 @@ class LineTracker(_Handle):
         if rc != abi.UVS_OK:
             raise self._error("uvs_lt_debug_detect", rc)
         return o
+
+
+def check_vocabulary(voc):
+    """uvs_pr_check_vocabulary on an abi.load_vocabulary dict -> (return code, message).  Host only: needs no GPU."""
+    args, keep = abi.pr_vocabulary_args(voc)
+    msg = C.create_string_buffer(256)
+    rc = lib().uvs_pr_check_vocabulary(*args, msg, len(msg))
+    return rc, msg.value.decode()
+
+
+class PlaceRecognizer(_Handle):
+    """Owns one `uvs_place_recognizer` handle: place recognition of loop closure (PoseGraph::detectLoop of the reference: DBoW2's vocabulary
+    tree, tf-idf bag-of-words vectors and the L1 query of their database) on one GPU.
+
+    `voc` is a vocabulary as abi.load_vocabulary gives it (the reference's brief_k10L6.bin).  Descriptors are uint64 [n, 4] arrays as
+    KeyframeExtractor returns them.  Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    _UNIT = "uvs_pr"
+
+    def __init__(self, voc, device=0, max_features=4096, initial_entries=1024):
+        rc, msg = check_vocabulary(voc)
+        if rc != abi.UVS_OK:
+            raise ValueError(f"uvs_pr_check_vocabulary: {lib().uvs_status_string(rc).decode()} / {msg}")
+        args, keep = abi.pr_vocabulary_args(voc)
+        self.max_features = int(max_features)
+        self._create(device, *args, max_features, initial_entries)
+        self.last_device_ms = dict(total=0.0, transform=0.0, query=0.0)
+
+    def _check(self, what, rc):
+        if rc != abi.UVS_OK:
+            raise self._error(what, rc)
+        L = lib()
+        self.last_device_ms = dict(total=float(L.uvs_pr_last_device_ms(self._h, 0)), transform=float(L.uvs_pr_last_device_ms(self._h, 1)),
+                                   query=float(L.uvs_pr_last_device_ms(self._h, 2)))
+
+    def size(self):
+        return int(lib().uvs_pr_size(self._h))
+
+    def clear(self):
+        self._check("uvs_pr_clear", lib().uvs_pr_clear(self._h))
+
+    def transform_raw(self, frames, n_frames=None):
+        """-> (return code, [dict(words, weights, bow_words, bow_values) per frame]) without raising."""
+        nf, desc = abi.pr_frames(frames)
+        n, tot = len(frames), max(int(nf.sum()), 1)
+        words = np.zeros(tot, np.int32); weights = np.zeros(tot); bow_n = np.zeros(max(n, 1), np.int32)
+        bw = np.zeros(max(n, 1) * self.max_features, np.int32); bv = np.zeros(max(n, 1) * self.max_features)
+        rc = lib().uvs_pr_transform(self._h, n if n_frames is None else int(n_frames), nf.ctypes.data_as(abi.c_i32_p), desc.ctypes.data_as(abi.c_u64_p),
+                                    words.ctypes.data_as(abi.c_i32_p), abi._dp(weights), bow_n.ctypes.data_as(abi.c_i32_p), bw.ctypes.data_as(abi.c_i32_p), abi._dp(bv))
+        off = np.r_[0, np.cumsum(nf)].astype(int)
+        out = []
+        for f in range(n):
+            s = slice(f * self.max_features, f * self.max_features + int(bow_n[f]))
+            out.append(dict(words=words[off[f]:off[f + 1]].copy(), weights=weights[off[f]:off[f + 1]].copy(), bow_words=bw[s].copy(), bow_values=bv[s].copy()))
+        return rc, out
+
+    def transform(self, frames):
+        """frames: list of uint64 [n_f, 4] descriptor arrays -> list of dicts: words int32 [n_f] and weights [n_f] (the leaf of every
+        descriptor, stop words included), bow_words int32 [m] ascending and bow_values [m] (the normalized tf-idf vector).  Changes no state."""
+        rc, out = self.transform_raw(frames)
+        self._check("uvs_pr_transform", rc)
+        return out
+
+    def add(self, frames):
+        """Appends the frames' vectors in order -> their entry ids int32 [n]."""
+        nf, desc = abi.pr_frames(frames)
+        ids = np.zeros(max(len(frames), 1), np.int32)
+        rc = lib().uvs_pr_add(self._h, len(frames), nf.ctypes.data_as(abi.c_i32_p), desc.ctypes.data_as(abi.c_u64_p), ids.ctypes.data_as(abi.c_i32_p))
+        self._check("uvs_pr_add", rc)
+        return ids[:len(frames)].copy()
+
+    def query(self, frames, max_results=4, max_id=-1):
+        """The frames against the database as it is -> list of (ids int32 [m], scores [m]) in descending score, a tie to the lower id.
+        max_results 0: all; max_id: one int or one per frame (entry e is eligible iff e < max_id or max_id == -1 or e is the last entry)."""
+        nf, desc = abi.pr_frames(frames)
+        n = len(frames)
+        mid = np.ascontiguousarray(np.broadcast_to(np.asarray(max_id, np.int32), (n,)))
+        stride = max(int(max_results) if max_results > 0 else self.size(), 1)
+        nres = np.zeros(max(n, 1), np.int32); ids = np.zeros(max(n, 1) * stride, np.int32); sc = np.zeros(max(n, 1) * stride)
+        rc = lib().uvs_pr_query(self._h, n, nf.ctypes.data_as(abi.c_i32_p), desc.ctypes.data_as(abi.c_u64_p), int(max_results), mid.ctypes.data_as(abi.c_i32_p),
+                                nres.ctypes.data_as(abi.c_i32_p), ids.ctypes.data_as(abi.c_i32_p), abi._dp(sc))
+        self._check("uvs_pr_query", rc)
+        st = int(max_results) if max_results > 0 else self.size()
+        return [(ids[f * st:f * st + int(nres[f])].copy(), sc[f * st:f * st + int(nres[f])].copy()) for f in range(n)]
+
+    def detect(self, desc, frame_index):
+        """detectLoop for one keyframe: query(4, frame_index - 50), then add, then the score gates -> (loop index or -1, ids, scores)."""
+        nf, d = abi.pr_frames([desc])
+        loop = C.c_int32(-1); nres = C.c_int32(0)
+        ids = np.zeros(abi.PR_DETECT_RESULTS, np.int32); sc = np.zeros(abi.PR_DETECT_RESULTS)
+        t0 = time.perf_counter()
+        rc = lib().uvs_pr_detect(self._h, int(nf[0]), d.ctypes.data_as(abi.c_u64_p), int(frame_index), C.byref(loop), C.byref(nres),
+                                 ids.ctypes.data_as(abi.c_i32_p), abi._dp(sc))
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call
+        self._check("uvs_pr_detect", rc)
+        return int(loop.value), ids[:nres.value].copy(), sc[:nres.value].copy()

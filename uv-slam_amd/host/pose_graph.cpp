@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include "utility.h"
 
@@ -70,7 +71,7 @@ bool KeyFrame::findConnection(KeyFrame* old_kf, uvs_loop_verifier* lc, const Eig
     return true;
 }
 
-PoseGraph::PoseGraph(int device, int max_keyframes, int max_loops) {
+PoseGraph::PoseGraph(int device, int max_keyframes, int max_loops) : device_(device) {
     sequence_loop.push_back(0);                             // :14
     int rc = uvs_pg_create(device, max_keyframes, max_loops, &pg_);
     if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_pg_create: ") + uvs_status_string(rc));
@@ -81,7 +82,79 @@ PoseGraph::PoseGraph(int device, int max_keyframes, int max_loops) {
 PoseGraph::~PoseGraph() {
     uvs_pg_destroy(pg_);
     uvs_lc_destroy(lc_);
+    uvs_pr_destroy(pr_);
     for (KeyFrame* kf : keyframelist) delete kf;
+}
+
+void PoseGraph::loadVocabulary(int k, int L, int scoring_type, int weighting_type, int n_nodes, const int32_t* node_id, const int32_t* parent_id,
+                               const double* weight, const uint64_t* descriptor, int n_words, const int32_t* word_node_id, const int32_t* word_id,
+                               int max_features, int initial_entries) {
+    uvs_place_recognizer* pr = nullptr;
+    char msg[256] = "";
+    int rc = uvs_pr_check_vocabulary(k, L, scoring_type, weighting_type, n_nodes, node_id, parent_id, weight, descriptor, n_words, word_node_id, word_id,
+                                     msg, (int)sizeof msg);
+    if (rc == UVS_OK)
+        rc = uvs_pr_create(device_, k, L, scoring_type, weighting_type, n_nodes, node_id, parent_id, weight, descriptor, n_words, word_node_id, word_id,
+                           max_features, initial_entries, &pr);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("loadVocabulary: ") + uvs_status_string(rc) + " / " + msg);
+    uvs_pr_destroy(pr_);
+    pr_ = pr;
+}
+
+void PoseGraph::loadVocabulary(const std::string& path) {      // ThirdParty/VocabularyBinary.cpp:27-35 deserialize
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("loadVocabulary: cannot open " + path);
+    int32_t head[6];                                           // k, L, scoringType, weightingType, nNodes, nWords
+    bool ok = std::fread(head, sizeof head, 1, f) == 1 && head[4] >= 0 && head[5] >= 0;
+    std::vector<char> nodes, words;
+    if (ok) {
+        nodes.resize((size_t)head[4] * 48); words.resize((size_t)head[5] * 8);
+        ok = (nodes.empty() || std::fread(nodes.data(), nodes.size(), 1, f) == 1) && (words.empty() || std::fread(words.data(), words.size(), 1, f) == 1);
+    }
+    std::fclose(f);
+    if (!ok) throw std::runtime_error("loadVocabulary: " + path + " is shorter than its header says");
+    const size_t nn = (size_t)head[4], nw = (size_t)head[5];
+    std::vector<int32_t> node_id(nn), parent_id(nn), word_node_id(nw), word_id(nw);
+    std::vector<double> weight(nn);
+    std::vector<uint64_t> descriptor(4 * nn);
+    for (size_t i = 0; i < nn; ++i) {                          // {int32 nodeId, int32 parentId, double weight, uint64 descriptor[4]}
+        const char* r = nodes.data() + 48 * i;
+        std::memcpy(&node_id[i], r, 4); std::memcpy(&parent_id[i], r + 4, 4); std::memcpy(&weight[i], r + 8, 8); std::memcpy(&descriptor[4 * i], r + 16, 32);
+    }
+    for (size_t i = 0; i < nw; ++i) {                          // {int32 nodeId, int32 wordId}
+        std::memcpy(&word_node_id[i], words.data() + 8 * i, 4); std::memcpy(&word_id[i], words.data() + 8 * i + 4, 4);
+    }
+    loadVocabulary(head[0], head[1], head[2], head[3], head[4], node_id.data(), parent_id.data(), weight.data(), descriptor.data(), head[5],
+                   word_node_id.data(), word_id.data());
+}
+
+int PoseGraph::detectLoop(KeyFrame* keyframe, int frame_index) {
+    last_detect_ids.assign(UVS_PR_DETECT_RESULTS, -1); last_detect_scores.assign(UVS_PR_DETECT_RESULTS, 0.0);
+    if (!pr_) { last_error = "detectLoop: no vocabulary (loadVocabulary)"; last_detect_ids.clear(); last_detect_scores.clear(); return -1; }
+    int32_t loop_index = -1, n_results = 0;
+    const int n = (int)keyframe->brief_descriptors.size();
+    const int rc = uvs_pr_detect(pr_, n, n ? keyframe->brief_descriptors[0].data() : nullptr, frame_index, &loop_index, &n_results,
+                                 last_detect_ids.data(), last_detect_scores.data());
+    if (rc != UVS_OK) { last_error = std::string("detectLoop: ") + uvs_pr_last_error(pr_); n_results = 0; loop_index = -1; }
+    last_detect_ids.resize(n_results); last_detect_scores.resize(n_results);
+    return loop_index;
+}
+
+void PoseGraph::addKeyFrameIntoVoc(KeyFrame* keyframe) {
+    if (!pr_) { last_error = "addKeyFrameIntoVoc: no vocabulary (loadVocabulary)"; return; }
+    const int32_t n = (int32_t)keyframe->brief_descriptors.size();
+    int32_t id = -1;
+    if (uvs_pr_add(pr_, 1, &n, n ? keyframe->brief_descriptors[0].data() : nullptr, &id) != UVS_OK)
+        last_error = std::string("addKeyFrameIntoVoc: ") + uvs_pr_last_error(pr_);
+}
+
+bool PoseGraph::addKeyFrameDetectLoop(KeyFrame* cur_kf, bool flag_detect_loop) {
+    int candidate = -1;                                        // :64-73; the index addKeyFrameImpl is about to give cur_kf is global_index
+    if (flag_detect_loop) candidate = detectLoop(cur_kf, global_index);
+    else addKeyFrameIntoVoc(cur_kf);
+    last_candidate = candidate;
+    addKeyFrameImpl(cur_kf, candidate, -1, nullptr);
+    return cur_kf->has_loop;
 }
 
 KeyFrame* PoseGraph::getKeyFrame(int index) {

@@ -3,8 +3,10 @@
 // and a synchronous optimize4DoF (:403-579) whose ceres::Solve is uvs_pg_optimize(); KeyFrame::findConnection (keyframe.cpp:259-521: BRIEF
 // matching, PnP-RANSAC, the loop_info gates) runs on the GPU through uvs_lc_verify(), and the online KeyFrame constructor (keyframe.cpp:14-41:
 // computeWindowBRIEFPoint, computeBRIEFPoint) extracts FAST corners, BRIEF descriptors and normalized keypoints from the image on the GPU
-// through uvs_kf_extract().  Place recognition (DBoW2 detectLoop) is not mirrored: addKeyFrameWithCandidate takes the candidate detectLoop
-// would return, and addKeyFrame still takes a loop as the caller found it.  A keyframe may also carry descriptors and normalized keypoints
+// through uvs_kf_extract().  Place recognition (detectLoop, :304-386, and addKeyFrameIntoVoc, :388-401: DBoW2's vocabulary tree, database and
+// L1 query) runs on the GPU through uvs_pr_detect() / uvs_pr_add() once loadVocabulary() has been given the caller's vocabulary:
+// addKeyFrameDetectLoop is the reference's addKeyFrame(cur_kf, flag_detect_loop).  addKeyFrameWithCandidate still takes the candidate from
+// the caller, and addKeyFrame a loop as the caller found it.  A keyframe may also carry descriptors and normalized keypoints
 // as the caller extracted them (the first constructor).  No thumbnail, no polling thread, no save / load, no visualization.
 #pragma once
 #include <array>
@@ -82,6 +84,21 @@ class PoseGraph {
     // Returns whether a loop was accepted.  Needs setExtrinsic() first.
     bool addKeyFrameWithCandidate(KeyFrame* cur_kf, int candidate_index);
     void setExtrinsic(const Eigen::Vector3d& tic, const Eigen::Quaterniond& qic) { tic_ = tic; qic_ = qic; }
+    // the vocabulary of place recognition, as the arrays of the reference's binary file (ThirdParty/VocabularyBinary.hpp; the arguments of
+    // uvs_pr_create) or as that file (the reference's support_files/brief_k10L6.bin).  Replaces an earlier vocabulary and empties the
+    // database.  Throws std::runtime_error when the file cannot be read or uvs_pr_create fails.
+    void loadVocabulary(int k, int L, int scoring_type, int weighting_type, int n_nodes, const int32_t* node_id, const int32_t* parent_id,
+                        const double* weight, const uint64_t* descriptor, int n_words, const int32_t* word_node_id, const int32_t* word_id,
+                        int max_features = UVS_LC_MAX_OLD, int initial_entries = 1024);
+    void loadVocabulary(const std::string& path);
+    // :304-386 through uvs_pr_detect: the query of the keyframe's brief_descriptors, their add, the score gates; -1: no candidate (also when
+    // the call fails: last_error tells).  last_detect_ids / last_detect_scores keep the query's results.  Needs loadVocabulary() first.
+    int detectLoop(KeyFrame* keyframe, int frame_index);
+    // :388-401 through uvs_pr_add
+    void addKeyFrameIntoVoc(KeyFrame* keyframe);
+    // addKeyFrame(cur_kf, flag_detect_loop) of the reference (:42-211): detectLoop(cur_kf, its index) when the flag is set, and its answer
+    // through addKeyFrameWithCandidate's path; otherwise addKeyFrameIntoVoc and addKeyFrame without a loop.  Returns whether a loop was accepted.
+    bool addKeyFrameDetectLoop(KeyFrame* cur_kf, bool flag_detect_loop);
     // one pass of the reference's optimize4DoF loop body for cur_index (first_looped_index = earliest_loop_index); returns the uvs status
     int optimize4DoF(int cur_index);
     KeyFrame* getKeyFrame(int index);
@@ -96,11 +113,16 @@ class PoseGraph {
     double yaw_drift = 0.0;
     uvs_pg_report last_report{};
     std::string last_error;
+    int last_candidate = -1;                               // what addKeyFrameDetectLoop's detectLoop returned
+    std::vector<int32_t> last_detect_ids;
+    std::vector<double> last_detect_scores;
 
   private:
     void addKeyFrameImpl(KeyFrame* cur_kf, int candidate_index, int loop_index, const LoopInfo* loop_info);
     uvs_pose_graph* pg_ = nullptr;
     uvs_loop_verifier* lc_ = nullptr;
+    uvs_place_recognizer* pr_ = nullptr;
+    int device_ = 0;
     Eigen::Vector3d tic_;
     Eigen::Quaterniond qic_;
 };

@@ -3,7 +3,8 @@
 // out_pose[n][7] = corrected (P, q x y z w) of every keyframe, out_drift[4] = (yaw_drift, t_drift), out_yaw_t[m][4] = the solve's raw output
 // for the m keyframes first_looped_index .. cur_index (m returned through *out_m); tum_path (may be NULL) receives the corrected path.
 // uvs_host_pose_graph_verify_run (below): the same stream with loop candidates instead of loops, verified on the GPU by findConnection.
-// uvs_host_pose_graph_image_run (last): the same again from IMAGES: every keyframe extracts its own descriptors and keypoints on the GPU.
+// uvs_host_pose_graph_image_run: the same again from IMAGES: every keyframe extracts its own descriptors and keypoints on the GPU.
+// uvs_host_pose_graph_detect_run (last): the verify run WITHOUT candidates: place recognition finds them on the GPU (addKeyFrameDetectLoop).
 #include <cstdio>
 #include <stdexcept>
 #include "pose_graph.h"
@@ -163,4 +164,62 @@ extern "C" int uvs_host_pose_graph_image_run(int device, int n, const double* st
     }
     uvs_kf_destroy(kf);
     return rc;
+}
+
+// Test hook: place recognition through the mirrored PoseGraph.  The arguments of uvs_host_pose_graph_verify_run, with the vocabulary (the
+// arguments of uvs_pr_create) in place of the candidates: every keyframe goes through addKeyFrameDetectLoop(kf, true), so detectLoop runs on
+// the GPU and its answer goes to findConnection; then optimize4DoF runs at the last keyframe with an accepted loop.  out_candidate[n] = what
+// detectLoop returned, the other outputs as uvs_host_pose_graph_verify_run's.
+extern "C" int uvs_host_pose_graph_detect_run(int device, int n, const double* stamps, const double* t, const double* q_xyzw, const int* sequence,
+                                              const double* tic, const double* qic_xyzw, const int* n_query, const double* p3d, const uint64_t* desc,
+                                              const int* n_kp, const double* uv_norm, const uint64_t* kp_desc, int k, int L, int scoring_type,
+                                              int weighting_type, int n_nodes, const int32_t* node_id, const int32_t* parent_id, const double* weight,
+                                              const uint64_t* descriptor, int n_words, const int32_t* word_node_id, const int32_t* word_id,
+                                              int* out_candidate, int* out_accepted, double* out_loop_info, double* out_pose) {
+    if (n < 1 || !stamps || !t || !q_xyzw || !sequence || !tic || !qic_xyzw || !n_query || !n_kp || !out_candidate || !out_accepted || !out_loop_info || !out_pose)
+        return UVS_ERR_INVALID_ARG;
+    try {
+        PoseGraph graph(device, n, 256);
+        graph.setExtrinsic(Eigen::Vector3d(tic[0], tic[1], tic[2]), Eigen::Quaterniond(qic_xyzw[3], qic_xyzw[0], qic_xyzw[1], qic_xyzw[2]));
+        graph.loadVocabulary(k, L, scoring_type, weighting_type, n_nodes, node_id, parent_id, weight, descriptor, n_words, word_node_id, word_id,
+                             UVS_LC_MAX_OLD, 64);
+        size_t qo = 0, ko = 0;
+        int last_loop = -1;
+        for (int f = 0; f < n; ++f) {
+            const Eigen::Quaterniond Q(q_xyzw[4 * f + 3], q_xyzw[4 * f], q_xyzw[4 * f + 1], q_xyzw[4 * f + 2]);
+            KeyFrame* kf = new KeyFrame(stamps[f], sequence[f], Eigen::Vector3d(t[3 * f], t[3 * f + 1], t[3 * f + 2]), Q.toRotationMatrix());
+            for (int i = 0; i < n_query[f]; ++i, ++qo) {
+                kf->point_3d.push_back(Eigen::Vector3d(p3d[3 * qo], p3d[3 * qo + 1], p3d[3 * qo + 2]));
+                kf->point_id.push_back((double)i);
+                kf->window_brief_descriptors.push_back({desc[4 * qo], desc[4 * qo + 1], desc[4 * qo + 2], desc[4 * qo + 3]});
+            }
+            for (int i = 0; i < n_kp[f]; ++i, ++ko) {
+                kf->keypoints_norm.push_back({uv_norm[2 * ko], uv_norm[2 * ko + 1]});
+                kf->brief_descriptors.push_back({kp_desc[4 * ko], kp_desc[4 * ko + 1], kp_desc[4 * ko + 2], kp_desc[4 * ko + 3]});
+            }
+            graph.last_error.clear();
+            const bool acc = graph.addKeyFrameDetectLoop(kf, true);      // the graph owns kf from here
+            if (!graph.last_error.empty()) { std::fprintf(stderr, "%s\n", graph.last_error.c_str()); return UVS_ERR_INVALID_ARG; }
+            out_candidate[f] = graph.last_candidate;
+            if (kf->last_verify.reason < 0) { std::fprintf(stderr, "findConnection: uvs_lc_verify failed at keyframe %d\n", f); return UVS_ERR_INVALID_ARG; }
+            out_accepted[f] = acc;
+            for (int c = 0; c < 8; ++c) out_loop_info[8 * f + c] = acc ? kf->loop_info[c] : 0.0;
+            if (acc) last_loop = kf->index;
+        }
+        if (last_loop >= 0) {
+            const int rc = graph.optimize4DoF(last_loop);
+            if (rc != UVS_OK) { std::fprintf(stderr, "optimize4DoF: %s\n", graph.last_error.c_str()); return rc; }
+        }
+        int f = 0;
+        for (const KeyFrame* kf : graph.keyframelist) {
+            const Eigen::Quaterniond Q(kf->R_w_i);
+            const double v[7] = {kf->T_w_i.x(), kf->T_w_i.y(), kf->T_w_i.z(), Q.x(), Q.y(), Q.z(), Q.w()};
+            for (int c = 0; c < 7; ++c) out_pose[7 * f + c] = v[c];
+            ++f;
+        }
+    } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return UVS_ERR_NO_DEVICE;
+    }
+    return UVS_OK;
 }
