@@ -1153,7 +1153,8 @@ enum { UVS_LT_DET_OK = 0, UVS_LT_DET_OVERFLOW = 1 };      /* OVERFLOW: n_found >
 typedef struct uvs_lt_det_item {
     const uint8_t *image;              /* [height][width] grey levels, row-major, stride = width */
     int32_t stream;                    /* uvs_lt_detect_track: the slot, at most once per call; uvs_lt_detect ignores it */
-    int32_t width;                     /* UVS_LT_MIN_SIZE .. max_width */
+    int32_t width;                     /* UVS_LT_MIN_SIZE .. max_width; in uvs_lt_detect_track, for a slot with a map (uvs_lt_set_undistort
+                                          below): the RAW frame, of the map's source size */
     int32_t height;                    /* UVS_LT_MIN_SIZE .. max_height */
     int32_t reserved;                  /* 0 */
 } uvs_lt_det_item;
@@ -1196,6 +1197,51 @@ double uvs_lt_last_detect_device_ms(const uvs_lt_tracker *lt);
  * support).  It touches no slot. */
 int uvs_lt_debug_detect(uvs_lt_tracker *lt, const uint8_t *image, int width, int height, const uvs_lt_det_params *params, uint8_t *blur,
                         uint32_t *grad, uint8_t *sector_a, uint8_t *sector_b, int32_t *name_a, int32_t *name_b, uint8_t *vote);
+
+/* ---- undistortion of the line front end's images (reference feature_tracker/src/line_feature_tracker.cpp:35-47 readImage4Line: imageUndistortion
+ * :1161-1188 = cv::undistort with the pinhole matrix and k1, k2, p1, p2, then the crop by ROW_MARGIN / COL_MARGIN) ----
+ * Calls on the line tracker's handle.  A slot may hold a MAP from the pixels of an undistorted, cropped image Wo x Ho to positions in the raw
+ * image W x H; uvs_lt_detect_track then takes the item's image as the RAW frame, and everything it returns is in pixels of the undistorted
+ * image.  cv::undistort is not in the reference tree and OpenCV's output could not be compared where this was written; the rule is this
+ * project's own integer statement with OpenCV's structure: a fixed-point map with 5 fractional bits, a bilinear blend, a constant zero border.
+ * One deliberate deviation: OpenCV rounds a float weight table to 15 bits, here the four weights are the exact products below (they sum to 1024);
+ * the two differ by at most one grey level.  Conventions as above: rint rounds half to even, >> is arithmetic.
+ *   map         camera = a uvs_kf_camera, margins cm, rm >= 0, Wo = W - 2 cm, Ho = H - 2 rm.  For output pixel (uo, vo): u = uo + cm, v = vo + rm as
+ *               doubles, then in FP64, every operation rounded once in the order written (no fused multiply-add):
+ *                 x = (u - cx) / fx, y = (v - cy) / fy;  x2 = x x, y2 = y y, xy = x y, r2 = x2 + y2;
+ *                 kr = 1 + (k1 r2 + k2 (r2 r2));
+ *                 xd = x kr + ((2 p1) xy + p2 (r2 + 2 x2)),  yd = y kr + (p1 (r2 + 2 y2) + (2 p2) xy);
+ *                 mx = fx xd + cx, my = fy yd + cy;  X = rint(32 mx), Y = rint(32 my)
+ *               X and Y are clamped to -2^24 .. 2^24, a value that is not finite becomes -2^24; both are stored as int32: map_xy[vo][uo] = (X, Y)
+ *   remap       xi = X >> 5, ax = X & 31, yi = Y >> 5, ay = Y & 31;  the taps p00 = S(yi, xi), p01 = S(yi, xi + 1), p10 = S(yi + 1, xi),
+ *               p11 = S(yi + 1, xi + 1) of the raw image S, a tap outside [0, H) x [0, W) being 0 (decided per tap);
+ *               out = ((32 - ax)(32 - ay) p00 + ax (32 - ay) p01 + (32 - ax) ay p10 + ax ay p11 + 512) >> 10
+ * With k1 = k2 = p1 = p2 = 0 the map is X = 32 u, Y = 32 v exactly and the output is the cropped input.  The rule is restated in
+ * tests/ud_ref.py, which the device is held to word for word and byte for byte; DESIGN.md 3.17 has the kernel plan.  No CPU path.
+ *
+ * The map is the state of a slot like the camera it describes: it survives uvs_lt_reset (unlike uvs_ft_set_equalize's state, which uvs_ft_reset
+ * switches off) and dies with the handle.  Its memory, 8 Wo Ho bytes, is allocated by the slot's first set call.  uvs_lt_detect (stateless, it
+ * ignores `stream`) and uvs_lt_track (the segments and their image are the caller's) never look at it.  In uvs_lt_detect_track an item whose
+ * slot holds a map must have the map's source size as width x height (else UVS_ERR_INVALID_ARG); after the one upload a kernel writes the
+ * undistorted image into device memory, which the detection and the tracking both read.  A call that mixes slots with and without a map gives
+ * every item the bits it gives alone; a call without a mapped slot issues exactly the operations it issued before this existed.
+ *
+ * uvs_lt_set_undistort builds the map of a rad-tan pinhole camera on the device; camera == NULL switches the slot's map off (the other
+ * arguments are not looked at).  uvs_lt_set_remap uploads the caller's own map_xy[out_height][out_width][2] in the same convention (any other
+ * camera model; values are clamped to -2^24 .. 2^24).  uvs_lt_get_remap returns the slot's sizes and, where map_xy is not NULL, the map.
+ * UVS_ERR_INVALID_ARG: a null pointer, a stream outside the handle's slots, a camera that is not finite or with fx or fy <= 0, a negative
+ * margin, a source or an output width or height below UVS_LT_MIN_SIZE, uvs_lt_get_remap on a slot without a map;  UVS_ERR_CAPACITY: a source or
+ * output width or height above the handle's.  A rejected call changes nothing, and the handle stays usable after it. */
+int uvs_lt_set_undistort(uvs_lt_tracker *lt, int stream, const uvs_kf_camera *camera, int width, int height, int col_margin, int row_margin);
+int uvs_lt_set_remap(uvs_lt_tracker *lt, int stream, int src_width, int src_height, int out_width, int out_height, const int32_t *map_xy);
+int uvs_lt_get_remap(uvs_lt_tracker *lt, int stream, int32_t *out_width, int32_t *out_height, int32_t *map_xy);
+/* Undistorts n_images (1 .. max_streams) RAW images, image b through the map of the slot images[b].stream (two images may name one slot;
+ * `reserved` is not looked at).  It touches no line state.  out receives the images PACKED in order, each [Ho][Wo] of its slot with stride = Wo.
+ * UVS_ERR_INVALID_ARG: null pointer, n_images < 1, a null image, a stream outside the slots, a slot without a map, a width or height that is not
+ * the map's source size;  UVS_ERR_CAPACITY: n_images above max_streams.  A rejected call changes nothing. */
+int uvs_lt_undistort(uvs_lt_tracker *lt, int n_images, const uvs_lt_det_item *images, uint8_t *out);
+/* HIP-event time of the last successful uvs_lt_undistort: upload, the kernel, download, on the handle's stream (milliseconds). */
+double uvs_lt_last_undistort_device_ms(const uvs_lt_tracker *lt);
 
 /* ---- place recognition of loop closure (reference pose_graph/src/pose_graph.cpp:304-386 detectLoop; ThirdParty/DBoW/TemplatedVocabulary.h
  * transform, TemplatedDatabase.h add / queryL1, BowVector.cpp addWeight / normalize) ----

@@ -810,6 +810,11 @@ def lt_det_items(items):
     return arr, keep
 
 
+# ---- undistortion of the line front end's images (uvs_lt_set_undistort, uvs_lt_set_remap, uvs_lt_undistort, include/uvs_solver.h) ----
+# The camera is a KfCamera (kf_camera), an image of uvs_lt_undistort an LtDetItem (lt_det_items: image and stream), a map int32 [Ho, Wo, 2].
+LT_UD_FRACTION_BITS = 5                  # a map word is a position in 1 / 32 px of the raw image
+LT_UD_LIMIT = 1 << 24                    # |X|, |Y| of a map word; uvs_lt_set_remap clamps to it
+
 # ---- place recognition of loop closure (uvs_pr_*, include/uvs_solver.h) -------------------------------------------------
 PR_MAX_K = 16
 PR_MAX_L = 16

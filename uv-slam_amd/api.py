@@ -30,6 +30,7 @@ EXPORTS = [
     "uvs_lt_create", "uvs_lt_destroy", "uvs_lt_last_error", "uvs_lt_reset", "uvs_lt_track", "uvs_lt_match", "uvs_lt_last_device_ms", "uvs_lt_debug_line",
     "uvs_lt_gauss_tables",
     "uvs_lt_detect", "uvs_lt_detect_track", "uvs_lt_last_detect_device_ms", "uvs_lt_debug_detect",
+    "uvs_lt_set_undistort", "uvs_lt_set_remap", "uvs_lt_get_remap", "uvs_lt_undistort", "uvs_lt_last_undistort_device_ms",
     "uvs_pr_check_vocabulary", "uvs_pr_create", "uvs_pr_destroy", "uvs_pr_last_error", "uvs_pr_size", "uvs_pr_clear", "uvs_pr_transform", "uvs_pr_add",
     "uvs_pr_query", "uvs_pr_detect", "uvs_pr_last_device_ms",
 ]
@@ -176,6 +177,11 @@ def lib():
         L.uvs_lt_debug_detect.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, C.POINTER(abi.LtDetParams), abi.c_u8_p, C.POINTER(C.c_uint32), abi.c_u8_p,
                                           abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_u8_p]
         L.uvs_lt_debug_detect.restype = C.c_int
+        L.uvs_lt_set_undistort.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.KfCamera), C.c_int, C.c_int, C.c_int, C.c_int]; L.uvs_lt_set_undistort.restype = C.c_int
+        L.uvs_lt_set_remap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, abi.c_i32_p]; L.uvs_lt_set_remap.restype = C.c_int
+        L.uvs_lt_get_remap.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p]; L.uvs_lt_get_remap.restype = C.c_int
+        L.uvs_lt_undistort.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LtDetItem), abi.c_u8_p]; L.uvs_lt_undistort.restype = C.c_int
+        L.uvs_lt_last_undistort_device_ms.argtypes = [C.c_void_p]; L.uvs_lt_last_undistort_device_ms.restype = C.c_double
         voc_args = [C.c_int] * 5 + [abi.c_i32_p, abi.c_i32_p, abi.c_double_p, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p]
         L.uvs_pr_check_vocabulary.argtypes = voc_args + [C.c_char_p, C.c_int]; L.uvs_pr_check_vocabulary.restype = C.c_int
         L.uvs_pr_create.argtypes = [C.c_int] + voc_args + [C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_pr_create.restype = C.c_int
@@ -1218,6 +1224,81 @@ class LineTracker(_Handle):
         if rc != abi.UVS_OK:
             raise self._error("uvs_lt_debug_detect", rc)
         return o
+
+    # ---- undistortion: a slot's map (uvs_lt_set_undistort, uvs_lt_set_remap, uvs_lt_get_remap) and loose raw images through it (uvs_lt_undistort)
+    def set_undistort_raw(self, stream, camera, width, height, col_margin=0, row_margin=0):
+        cam = None if camera is None else C.byref(abi.kf_camera(camera))
+        return lib().uvs_lt_set_undistort(self._h, int(stream), cam, int(width), int(height), int(col_margin), int(row_margin))
+
+    def set_undistort(self, stream, camera, width, height, col_margin=0, row_margin=0):
+        """Builds the slot's map on the device from camera = (fx, fy, cx, cy, k1, k2, p1, p2) of the raw image width x height, cropped by the
+        margins: detect_track() then takes the slot's images raw.  camera = None switches it off; reset() keeps it."""
+        rc = self.set_undistort_raw(stream, camera, width, height, col_margin, row_margin)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_set_undistort", rc)
+
+    def set_remap_raw(self, stream, src_width, src_height, map_xy, out_width=None, out_height=None, null=False):
+        m = np.ascontiguousarray(map_xy, np.int32)
+        oh, ow = m.shape[:2]
+        return lib().uvs_lt_set_remap(self._h, int(stream), int(src_width), int(src_height), ow if out_width is None else int(out_width),
+                                      oh if out_height is None else int(out_height), None if null else abi._ip(m))
+
+    def set_remap(self, stream, src_width, src_height, map_xy):
+        """The caller's own map [Ho, Wo, 2] int32 (X, Y in 1/32 px of the raw image src_width x src_height) as the slot's map."""
+        rc = self.set_remap_raw(stream, src_width, src_height, map_xy)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_set_remap", rc)
+
+    def get_remap_raw(self, stream, sizes_only=False, null=()):
+        """-> (return code, map [Ho, Wo, 2] int32 or, with sizes_only, (Wo, Ho)) without raising."""
+        ow = C.c_int32(0); oh = C.c_int32(0)
+        args = dict(out_width=C.byref(ow), out_height=C.byref(oh))
+        for k in null:
+            args[k] = None
+        rc = lib().uvs_lt_get_remap(self._h, int(stream), args["out_width"], args["out_height"], None)
+        if rc != abi.UVS_OK or sizes_only:
+            return rc, (int(ow.value), int(oh.value))
+        m = np.zeros((oh.value, ow.value, 2), np.int32)
+        rc = lib().uvs_lt_get_remap(self._h, int(stream), args["out_width"], args["out_height"], abi._ip(m))
+        return rc, m
+
+    def get_remap(self, stream):
+        """-> the slot's map [Ho, Wo, 2] int32."""
+        rc, m = self.get_remap_raw(stream)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_get_remap", rc)
+        return m
+
+    def undistort_raw(self, images, n_images=None, null=()):
+        """-> (return code, [undistorted image]) without raising: for the tests of the argument checks.  images: dicts (stream, image [H, W]
+        uint8, the raw image).  n_images overrides the count passed; `null` names arguments passed as NULL ("images", "out")."""
+        arr, keep = abi.lt_det_items(images)
+        shapes = []
+        for d in images:          # the sizes of the outputs are the slots'; a slot without a map has none, and the call says so
+            rc, wh = self.get_remap_raw(d.get("stream", 0), sizes_only=True)
+            shapes.append((wh[1], wh[0]) if rc == abi.UVS_OK else (0, 0))
+        out = np.zeros(max(sum(h * w for h, w in shapes), 1), np.uint8)
+        args = dict(images=C.cast(arr, C.POINTER(abi.LtDetItem)), out=out.ctypes.data_as(abi.c_u8_p))
+        for k in null:
+            args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_lt_undistort(self._h, len(images) if n_images is None else int(n_images), args["images"], args["out"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernel, download
+        self.last_undistort_device_ms = float(lib().uvs_lt_last_undistort_device_ms(self._h))
+        if rc != abi.UVS_OK:
+            return rc, []
+        res, o = [], 0
+        for h, w in shapes:
+            res.append(out[o:o + h * w].reshape(h, w).copy()); o += h * w
+        return rc, res
+
+    def undistort(self, images):
+        """images: list of dicts (stream, image [H, W] uint8: a raw image of the size of the slot's map) -> the undistorted, cropped images.
+        Two images may name one slot; no line state is touched."""
+        rc, out = self.undistort_raw(images)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_undistort", rc)
+        return out
 
 
 def check_vocabulary(voc):

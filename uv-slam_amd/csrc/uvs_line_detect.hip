@@ -506,12 +506,29 @@ int det_check(uvs_lt_tracker* h, const std::string& fn, int n_items, const uvs_l
     return UVS_OK;
 }
 
-// the work space, at the handle's capacity, by the first call
-int det_ensure(uvs_lt_tracker* h) {
+// what a call with mapped slots (uvs_lt_set_undistort) adds behind the packed input: the remap's items, uploaded with it, and the undistorted
+// images the remap writes, which are what the detection and the tracking then read
+struct UdPlan { size_t o_items = 0, upload = 0, used = 0; std::vector<size_t> out_off; };
+
+UdPlan ud_plan(size_t in_used, size_t n, const std::vector<size_t>& out_bytes) {
+    UdPlan P;
+    UvsArena a;
+    a.o = in_used;
+    P.o_items = a.take(n * sizeof(uvslt::UdItem));
+    P.upload = a.o;
+    for (size_t b : out_bytes) P.out_off.push_back(a.take(b));
+    P.used = a.o;
+    return P;
+}
+
+// the work space, at the handle's capacity, by the first call; with_maps: the input buffers also hold what ud_plan adds
+int det_ensure(uvs_lt_tracker* h, bool with_maps) {
     const size_t B = h->max_streams, px = (size_t)h->max_width * h->max_height;
     const DetLayout Y = det_layout(B, h->max_lines, std::vector<size_t>(B, px), nullptr);
+    size_t host_in = Y.in_used, dev_in = Y.in_used;
+    if (with_maps) { const UdPlan P = ud_plan(Y.in_used, B, std::vector<size_t>(B, px)); host_in = P.upload; dev_in = P.used; }
     int rc;
-    if ((rc = h->h_det_in.ensure(Y.in_used, h->err)) != UVS_OK || (rc = h->d_det_in.ensure(Y.in_used, h->err)) != UVS_OK ||
+    if ((rc = h->h_det_in.ensure(host_in, h->err)) != UVS_OK || (rc = h->d_det_in.ensure(dev_in, h->err)) != UVS_OK ||
         (rc = h->h_det_out.ensure(Y.out_used, h->err)) != UVS_OK || (rc = h->d_det_out.ensure(Y.out_used, h->err)) != UVS_OK ||
         (rc = h->d_det_blur.ensure(B * px, h->err)) != UVS_OK || (rc = h->d_det_sec.ensure(2 * B * px, h->err)) != UVS_OK ||
         (rc = h->d_det_vote.ensure(B * px, h->err)) != UVS_OK || (rc = h->d_det_grad.ensure(4 * B * px, h->err)) != UVS_OK ||
@@ -521,21 +538,41 @@ int det_ensure(uvs_lt_tracker* h) {
     return UVS_OK;
 }
 
-// One call's device work through the download and the wait (the arguments are checked); the images stay in d_det_in at img_off
-int det_run(uvs_lt_tracker* h, int n_items, const uvs_lt_det_item* items, const uvs_lt_det_params* params, DetLayout* layout, std::vector<size_t>* img_off) {
-    int rc = det_ensure(h);
+// One call's device work through the download and the wait (the arguments are checked); the images stay in d_det_in at img_off.
+// maps: null, or per item the slot's undistortion or null (uvs_lt_detect_track with at least one mapped slot).  A mapped item's image is the raw
+// frame: it is uploaded with the others, the remap writes the undistorted image behind the upload, and that image is the item's from there on
+// (its offset in img_off; its size is the map's output size).
+int det_run(uvs_lt_tracker* h, int n_items, const uvs_lt_det_item* items, const uvs_lt_det_params* params, DetLayout* layout, std::vector<size_t>* img_off,
+            const std::vector<const LtUndistort*>* maps = nullptr) {
+    int rc = det_ensure(h, maps != nullptr);
     if (rc != UVS_OK) return rc;
     std::vector<size_t> img_bytes;
     for (int b = 0; b < n_items; ++b) img_bytes.push_back((size_t)items[b].width * items[b].height);
     const DetLayout Y = det_layout(n_items, h->max_lines, img_bytes, img_off);
     *layout = Y;
+    UdPlan P;
+    int n_ud = 0, max_out = 0;
+    if (maps) {
+        std::vector<size_t> out_bytes;
+        for (int b = 0; b < n_items; ++b) if ((*maps)[b]) out_bytes.push_back((size_t)(*maps)[b]->Wo * (*maps)[b]->Ho);
+        P = ud_plan(Y.in_used, out_bytes.size(), out_bytes);
+    }
     DetItem* hi = reinterpret_cast<DetItem*>(h->h_det_in.get());
     int max_threads = 0;
     for (int b = 0; b < n_items; ++b) {
         DetItem d;
         d.W = items[b].width; d.H = items[b].height; d.img_off = (long long)(*img_off)[b];
-        hi[b] = d;
         std::memcpy(h->h_det_in + (*img_off)[b], items[b].image, img_bytes[b]);
+        if (maps && (*maps)[b]) {
+            const LtUndistort& U = *(*maps)[b];
+            uvslt::UdItem u;
+            u.W = U.W; u.H = U.H; u.n_out = U.Wo * U.Ho; u.pad = 0; u.src_off = d.img_off; u.dst_off = (long long)P.out_off[n_ud]; u.map = U.map;
+            reinterpret_cast<uvslt::UdItem*>(h->h_det_in + P.o_items)[n_ud++] = u;
+            max_out = std::max(max_out, u.n_out);
+            d.W = U.Wo; d.H = U.Ho; d.img_off = u.dst_off;
+            (*img_off)[b] = (size_t)u.dst_off;
+        }
+        hi[b] = d;
         max_threads = std::max(max_threads, ((d.W + 63) & ~63) * d.H);
     }
     DetBufs B;
@@ -550,7 +587,11 @@ int det_run(uvs_lt_tracker* h, int n_items, const uvs_lt_det_item* items, const 
     hipStream_t st = h->st;
     UVS_HIP(h->err, hipSetDevice(h->device));
     UVS_HIP(h->err, hipEventRecord(h->ev0, st));
-    UVS_HIP(h->err, hipMemcpyAsync(h->d_det_in, h->h_det_in, Y.in_used, hipMemcpyHostToDevice, st));
+    UVS_HIP(h->err, hipMemcpyAsync(h->d_det_in, h->h_det_in, maps ? P.upload : Y.in_used, hipMemcpyHostToDevice, st));
+    if (n_ud) {
+        uint8_t* din = reinterpret_cast<uint8_t*>(h->d_det_in.get());
+        if ((rc = uvslt::ud_launch(h, n_ud, reinterpret_cast<const uvslt::UdItem*>(h->d_det_in + P.o_items), din, din, max_out)) != UVS_OK) return rc;
+    }
     UVS_HIP(h->err, hipMemsetAsync(h->d_det_out, 0, Y.out_used, st));      // the counters of the results, and the rows that are not returned
     k_lt_det_blur<<<grid, kThreads, 0, st>>>(dI, B);
     k_lt_det_sectors<<<grid, kThreads, 0, st>>>(dI, B, params->grad_threshold);
@@ -610,8 +651,19 @@ int uvs_lt_detect_track(uvs_lt_tracker* h, int n_items, const uvs_lt_det_item* i
     }
     int rc = det_check(h, fn, n_items, items, params, true);
     if (rc != UVS_OK) return rc;
+    // the items of mapped slots (uvs_lt_set_undistort) bring the raw frame; without one, `maps` stays empty and nothing below differs
+    std::vector<const LtUndistort*> maps;
+    for (int b = 0; b < n_items; ++b) {
+        const LtUndistort& U = h->ud[items[b].stream];
+        if (!U.on) continue;
+        if (items[b].width != U.W || items[b].height != U.H) {
+            h->err = fn + ": item " + std::to_string(b) + ": width or height is not the source size of the slot's map"; return UVS_ERR_INVALID_ARG;
+        }
+        maps.resize(n_items, nullptr);
+        maps[b] = &U;
+    }
     DetLayout Y; std::vector<size_t> img_off;
-    rc = det_run(h, n_items, items, params, &Y, &img_off);
+    rc = det_run(h, n_items, items, params, &Y, &img_off, maps.empty() ? nullptr : &maps);
     if (rc != UVS_OK) return rc;
     float det_ms = 0.f;
     UVS_HIP(h->err, hipEventElapsedTime(&det_ms, h->ev0, h->ev1));
@@ -623,6 +675,7 @@ int uvs_lt_detect_track(uvs_lt_tracker* h, int n_items, const uvs_lt_det_item* i
     size_t tl = 0; int max_n = 0;
     for (int b = 0; b < n_items; ++b) {
         lit[b].image = items[b].image; lit[b].stream = items[b].stream; lit[b].width = items[b].width; lit[b].height = items[b].height;
+        if (!maps.empty() && maps[b]) { lit[b].width = maps[b]->Wo; lit[b].height = maps[b]->Ho; }      // the image on the device is the undistorted one
         lit[b].n_lines = dr[b].n_returned; lit[b].segments = hseg + 4 * (size_t)b * h->max_lines;
         slot_of[b] = items[b].stream;
         tl += lit[b].n_lines; max_n = std::max(max_n, lit[b].n_lines);

@@ -326,6 +326,7 @@ int uvs_lt_create(int device, int max_streams, int max_width, int max_height, in
     uvs_lt_tracker* h = new uvs_lt_tracker();
     h->max_streams = max_streams; h->max_width = max_width; h->max_height = max_height; h->max_lines = max_lines; h->max_length = max_length;
     h->slots.assign(max_streams, LtSlot());
+    h->ud.resize(max_streams);
     const size_t B = max_streams, Lt = B * max_lines, px = (size_t)max_width * max_height, sets = 2 * (B + 1) * (size_t)max_lines;
     h->grad_stride = px;
     // the larger of a full uvs_lt_track and a full uvs_lt_match (two descriptor sets and their gate points in, three index arrays out)

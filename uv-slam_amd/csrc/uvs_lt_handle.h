@@ -1,7 +1,8 @@
-// uvs_lt_handle.h -- the handle behind the uvs_lt_* calls, shared by the two units of the line front end: csrc/uvs_line_track.hip (creates and
-// destroys it, describes and matches segments, keeps the slots' previous lines) and csrc/uvs_line_detect.hip (detects the segments of an image
-// and hands them to the tracking unit without a second upload of the image).  Device, stream, events and error text are the base's
-// (uvs_handle.h).  Host only, but for the two structs the kernels read.
+// uvs_lt_handle.h -- the handle behind the uvs_lt_* calls, shared by the three units of the line front end: csrc/uvs_line_track.hip (creates and
+// destroys it, describes and matches segments, keeps the slots' previous lines), csrc/uvs_line_detect.hip (detects the segments of an image
+// and hands them to the tracking unit without a second upload of the image) and csrc/uvs_line_undistort.hip (the slots' undistortion maps and
+// the remap of a raw image, which the detection unit calls in front of its own kernels).  Device, stream, events and error text are the base's
+// (uvs_handle.h).  Host only, but for the three structs the kernels read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -33,10 +34,17 @@ struct LtMatchJob {                // one match: the queries, the train set, the
     int32_t* match_of_prev; int32_t* dist_prev; int32_t* prev_of_cur; int32_t* dist_cur;
     uvs_lt_result* result;         // n_matched is written here
 };
+struct UdItem {                    // one remap: the raw image W x H at src_off, n_out = Wo Ho output pixels at dst_off, the slot's map [n_out][2]
+    int W, H, n_out, pad;
+    long long src_off, dst_off;
+    const int32_t* map;
+};
 
 }  // namespace uvslt
 
 struct LtSlot { int n_prev = 0, cur = 0; };      // lines of the previous set; which of the slot's two sets holds it
+// a slot's undistortion (uvs_line_undistort.hip): the raw size W x H, the output size Wo x Ho, the map [Ho][Wo][2] in Q5.  uvs_lt_reset keeps it
+struct LtUndistort { bool on = false; int W = 0, H = 0, Wo = 0, Ho = 0; DevBuf<int32_t> map; };
 
 struct uvs_lt_tracker : UvsHandle {
     int max_streams = 0, max_width = 0, max_height = 0, max_lines = 0, max_length = 0;
@@ -63,6 +71,11 @@ struct uvs_lt_tracker : UvsHandle {
     DevBuf<char> d_det_rec;                     // [items][2][px] records of 64 bytes, read at a region's name only
     DevBuf<unsigned long long> d_det_list_len;  // [items][px] the kept segments in no order: the bits of the length ...
     DevBuf<uint32_t> d_det_list_id;             // ... and 2 name + partition
+    // undistortion (uvs_line_undistort.hip): a slot's map is allocated by its first set call, the staging by the first uvs_lt_undistort
+    float undistort_ms = 0.f;                   // uvs_lt_last_undistort_device_ms
+    std::vector<LtUndistort> ud;                // [max_streams]
+    PinnedBuf<char> h_ud_io;                    // uvs_lt_undistort's pinned staging and device buffer, one layout: (items | raw images | outputs)
+    DevBuf<char> d_ud_io;
 
     uint8_t* set_desc(int slot, int set) const { return d_slot_desc + ((size_t)(2 * slot + set) * max_lines) * uvslt::kBytes; }
     int32_t* set_ends(int slot, int set) const { return d_slot_ends + ((size_t)(2 * slot + set) * max_lines) * 4; }
@@ -123,5 +136,9 @@ inline int lt_check_items(uvs_lt_tracker* h, const std::string& fn, int n_items,
 // images are not uploaded a second time).
 int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::vector<int>& slot_of, bool match, size_t tl, int max_n,
            double* dbg_float, LtLayout* layout, const uint8_t* dev_images = nullptr, const size_t* dev_img_off = nullptr);
+
+// The remap kernel of uvs_line_undistort.hip on the handle's stream: n items (the device array `items`) of at most max_out output pixels, the raw
+// images at src + src_off, the outputs at dst + dst_off.  uvs_lt_detect_track launches it between its upload and its first kernel.
+int ud_launch(uvs_lt_tracker* h, int n, const UdItem* items, const uint8_t* src, uint8_t* dst, int max_out);
 
 }  // namespace uvslt

@@ -3,9 +3,11 @@
 // uvs_lt_track() and uvs_lt_detect_track(): an image, with or without its segments, in, ids / track_cnt / curr_start_pts / curr_end_pts / the normalized end points out.  Header-only.
 // The descriptors (lineBiDes->compute) and lineMatching are on the GPU (csrc/uvs_line_track.hip); what is here is the bookkeeping around them.
 // Differences from the reference, all from the C ABI below: the segments are the caller's detector's or, through the overload without
-// segments, uvs_lt_detect's line-support regions (ELSED is not part of this library, and not in the reference tree), the image is already
-// undistorted, positions are FP64 (cv::Point2f there), and n_id is a member, not a static, so that two trackers of one
-// process number their lines apart.  With a uvs::VanishingPoints attached, `vps` is filled per line as :379-385 does.
+// segments, uvs_lt_detect's line-support regions (ELSED is not part of this library, and not in the reference tree), positions are FP64
+// (cv::Point2f there), and n_id is a member, not a static, so that two trackers of one process number their lines apart.  The image is already
+// undistorted and cropped, unless setUndistortion() was called: then the overload of readImage4Line without segments takes the raw frame, as
+// the reference's does (:35-47), and the device undistorts and crops it (uvs_lt_set_undistort).  The overload with the caller's segments always
+// takes the image those segments were found in.  With a uvs::VanishingPoints attached, `vps` is filled per line as :379-385 does.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -123,7 +125,8 @@ public:
     // throws std::runtime_error without a GPU (no CPU path)
     LineFeatureTracker(int device, double fx, double fy, double cx, double cy, int max_width, int max_height, int max_lines = 256,
                        int max_length = UVS_LT_MAX_LENGTH, int col_margin = 0, int row_margin = 0)
-        : LineFeatureTrackerBook(fx, fy, cx, cy, col_margin, row_margin), device_(device), max_lines_(max_lines) {
+        : LineFeatureTrackerBook(fx, fy, cx, cy, col_margin, row_margin), device_(device), max_lines_(max_lines), raw_fx_(fx), raw_fy_(fy), raw_cx_(cx),
+          raw_cy_(cy), max_width_(max_width), max_height_(max_height), col_margin_(col_margin), row_margin_(row_margin) {
         const int rc = uvs_lt_create(device, 1, max_width, max_height, max_lines, max_length, &lt_);
         if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_lt_create: ") + uvs_status_string(rc));
     }
@@ -137,6 +140,19 @@ public:
         th_angle_ = thAngle;
     }
 
+    // :1161-1188 imageUndistortion and the crop of :43-47, on the device: from now on readImage4Line(img, width, height, cur_time) takes the RAW
+    // frame of width x height (0: the constructor's max_width x max_height, the reference's COL x ROW).  The map is built from the UNSHIFTED
+    // fx, fy, cx, cy and the constructor's margins; the bookkeeping's shifted cx, cy then fit the cropped image.  Every parameter is rounded
+    // through float first: the reference fills CV_32F matrices with them (:1168-1177), and cv::undistort works from those.
+    // Returns UVS_OK or uvs_lt_set_undistort's error (its text in last_error; the map stays as it was).
+    int setUndistortion(double k1, double k2, double p1, double p2, int width = 0, int height = 0) {
+        const auto f32 = [](double v) { return (double)(float)v; };
+        const uvs_kf_camera cam{f32(raw_fx_), f32(raw_fy_), f32(raw_cx_), f32(raw_cy_), f32(k1), f32(k2), f32(p1), f32(p2)};
+        const int rc = uvs_lt_set_undistort(lt_, 0, &cam, width > 0 ? width : max_width_, height > 0 ? height : max_height_, col_margin_, row_margin_);
+        if (rc != UVS_OK) last_error = uvs_lt_last_error(lt_);
+        return rc;
+    }
+
     // One frame: img[height][width] (undistorted, 8 bit), segments[n][4] = sx, sy, ex, ey of the caller's detector.  Returns UVS_OK or the
     // error of uvs_lt_track (its text in last_error; the frame changes nothing) or of uvs_vp_estimate (the lines are tracked, `vps` stays empty).
     int readImage4Line(const uint8_t* img, int width, int height, size_t n, const double* segments, double cur_time) {
@@ -148,7 +164,8 @@ public:
         applyMatches(cur_time, n, segments, prev_index_.data());
         return finishFrame(n, segments);
     }
-    using LineFeatureTrackerBook::readImage4Line;      // (img, width, height, cur_time): uvs_lt_detect_track finds the segments
+    using LineFeatureTrackerBook::readImage4Line;      // (img, width, height, cur_time): uvs_lt_detect_track finds the segments; after
+                                                       // setUndistortion img is the raw frame and the segments are those of the undistorted one
 
     void reset() { LineFeatureTrackerBook::reset(); (void)uvs_lt_reset(lt_, 0); }
 
@@ -199,6 +216,8 @@ private:
     double th_angle_ = 0.0;
     uint64_t frame_ = 0;
     int device_, max_lines_;
+    double raw_fx_, raw_fy_, raw_cx_, raw_cy_;         // as given, before the margins' shift
+    int max_width_, max_height_, col_margin_, row_margin_;
 };
 
 }  // namespace uvs

@@ -101,6 +101,13 @@ int uvs_host_lt_set_detect(void* p, int grad_threshold, int min_pixels, double m
     return UVS_OK;
 }
 
+// setUndistortion(k1, k2, p1, p2) of a tracker: uvs_host_lt_read_image_detect then takes raw frames of the tracker's max_width x max_height
+int uvs_host_lt_set_undistortion(void* p, double k1, double k2, double p1, double p2) {
+    LtHook* h = static_cast<LtHook*>(p);
+    if (!h || !h->tracker) return UVS_ERR_INVALID_ARG;
+    return h->tracker->setUndistortion(k1, k2, p1, p2);
+}
+
 // readImage4Line(img, width, height, time): the segments are detected (a tracker) or injected (a stub)
 int uvs_host_lt_read_image_detect(void* p, const uint8_t* img, int width, int height, double time) {
     LtHook* h = static_cast<LtHook*>(p);
