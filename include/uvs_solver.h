@@ -1243,6 +1243,77 @@ int uvs_lt_undistort(uvs_lt_tracker *lt, int n_images, const uvs_lt_det_item *im
 /* HIP-event time of the last successful uvs_lt_undistort: upload, the kernel, download, on the handle's stream (milliseconds). */
 double uvs_lt_last_undistort_device_ms(const uvs_lt_tracker *lt);
 
+/* ---- camera models of the front ends: MEI and Kannala-Brandt beside the pinhole (reference camera_model/src/camera_models/CataCamera.cc
+ * :556-659 liftProjective / spaceToPlane, :766-782 distortion; EquidistantCamera.cc:428-461 liftProjective / spaceToPlane, :716-818
+ * backprojectSymmetric; CameraFactory::generateCameraFromYamlFile) ----
+ * A uvs_kf_camera is a radial-tangential pinhole.  A uvs_camera_model is one of three models; csrc/uvs_camera_models.h states them once for
+ * the device and the host, in FP64, every operation rounded once in the order written (no fused multiply-add); tests/cm_ref.py restates it.
+ *   lift      pixel (x, y) -> ray (X, Y, Z) and the normalized point (X / Z, Y / Z), as undistortedPoints forms it.
+ *   project   ray -> pixel (spaceToPlane).
+ * Below, D(x, y) is the distortion both pinhole and MEI use: x2 = x x, y2 = y y, xy = x y, r2 = x2 + y2, rad = k1 r2 + (k2 r2) r2,
+ *   dx = (x rad + ((2 p1) xy)) + p2 (r2 + 2 x2), dy = (y rad + ((2 p2) xy)) + p1 (r2 + 2 y2); and (xd, yd) = (iK11 x + iK13, iK22 y + iK23) with
+ *   iK11 = 1 / sx, iK13 = -u0 / sx, iK22 = 1 / sy, iK23 = -v0 / sy for the model's scales (sx, sy) and centre (u0, v0).
+ *   PINHOLE   p = fx fy cx cy k1 k2 p1 p2.  lift: uvs_kf_extract's liftProjective unchanged (the recursive model: (xu, yu) = (xd, yd), then 8 times
+ *             (xu, yu) = (xd, yd) - D(xu, yu); none when k1 = k2 = p1 = p2 = 0), ray = (xu, yu, 1): the bits of the same camera given as a
+ *             uvs_kf_camera.  project: x = X / Z, y = Y / Z, then the forward map of uvs_lt_set_undistort above (kr, xd, yd, mx, my).
+ *   MEI       p = xi k1 k2 p1 p2 gamma1 gamma2 u0 v0.  lift: (xu, yu) as for the pinhole with (gamma1, gamma2, u0, v0) (none of the 8 passes when
+ *             the four coefficients are 0), then Z = ((1 - xu xu) - yu yu) / 2 when xi == 1, else rho2 = xu xu + yu yu,
+ *             Z = 1 - (xi (rho2 + 1)) / (xi + sqrt(1 + (1 - xi xi) rho2)); ray = (xu, yu, Z).  project: n = sqrt(X X + (Y Y + Z Z)), z = Z + xi n,
+ *             x = X / z, y = Y / z, (x, y) += D(x, y) unless the four coefficients are 0, pixel = (gamma1 x + u0, gamma2 y + v0).  Multiplies, adds,
+ *             divides and one correctly rounded sqrt: the device and the restatement agree bit for bit.
+ *   KANNALA_BRANDT  p = k2 k3 k4 k5 mu mv u0 v0.  With t = th th:  r(th) = th + th (t (k2 + t (k3 + t (k4 + t k5)))),
+ *             r'(th) = 1 + t (3 k2 + t (5 k3 + t (7 k4 + t (9 k5)))).  th_max: the first th in (0, pi] with r'(th) <= 0, found once per model on the
+ *             host (a scan of r' at i pi / 4096, i = 1 .. 4096, then the bisection of that step down to neighbouring doubles; th_max is the
+ *             lower one, where r' > 0), or pi if there is none; r_max = r(th_max).
+ *             lift: (px, py) = (xd, yd) with (mu, mv, u0, v0), rr = sqrt(px px + py py).  th = rr when the four k are 0 or !(rr < r_max);
+ *             otherwise the root of r(th) = rr on [0, th_max] by a safeguarded Newton iteration: lo = 0, hi = th_max, th = min(rr, th_max), then
+ *             at most UVS_CAM_KB_ITERATIONS times: f = r(th) - rr; stop if f == 0; hi = th if f > 0 else lo = th; tn = th - f / r'(th); stop if
+ *             tn == th or tn == the th of the step before (two neighbouring doubles straddle the root: the later one is kept);
+ *             tn = (lo + hi) / 2 unless lo <= tn <= hi; th = tn.  ray = ((sin th px) / rr, (sin th py) / rr, cos th), and
+ *             (sin th, 0, cos th) when rr < 1e-10 (the reference's phi = 0).
+ *             project: h = sqrt(X X + Y Y), th = atan2(h, Z), q = r(th), pixel = (mu ((q X) / h) + u0, mv ((q Y) / h) + v0), and (mu q + u0, v0)
+ *             when h == 0.  Neither direction forms phi.
+ *             Deviation: the reference takes th as the smallest non-negative real eigenvalue of the polynomial's companion matrix, per pixel.
+ *             On the first monotone branch [0, th_max] that is the root found here (tests/cm_ref.py holds both to a 60-digit evaluation of
+ *             the reference's definition over the image rectangles of the shipped fisheye configurations).  For rr beyond the branch the
+ *             reference would return a root of a later, physically meaningless branch if one exists; here th = rr, the reference's own
+ *             fallback when it finds no root.  sin, cos and atan2 are the device library's: KB results are held to a tolerance, not to bits.
+ *
+ * uvs_ft_set_camera_model / uvs_kf_set_camera_model put a model on a handle (model == NULL takes it off).  While a tracker holds one,
+ * uvs_ft_track, uvs_ft_detect, uvs_ft_debug_point and uvs_ft_debug_detect lift next_norm / new_norm through it; while an extractor holds one,
+ * uvs_kf_extract and uvs_kf_debug_frame lift keypoints_norm through it.  Their `camera` argument may then be NULL and is not looked at.
+ * Nothing else of those calls changes, and without a model they issue exactly the operations they issued before.  The model is the
+ * handle's, not a slot's: it survives uvs_ft_reset.
+ *
+ * uvs_ft_lift / uvs_ft_project: n loose points through a model on the tracker's device and stream (the place of m_camera->liftProjective and
+ * spaceToPlane for a caller with points of its own, e.g. in front of uvs_ft_reject); one thread per point, and a point gets the bits it gets
+ * alone.  xy[n][2], ray[n][3], norm[n][2]; either output of uvs_ft_lift may be NULL.  n == 0 is a successful no-op.
+ *
+ * uvs_lt_set_undistort_model builds a slot's undistortion map for any model (camodocal's initUndistortRectifyMap with the identity rotation):
+ * for output pixel (uo, vo), u = uo + cm, v = vo + rm, the ray ((u - cx_out) / fx_out, (v - cy_out) / fy_out, 1) of the output pinhole goes
+ * through project of the model to the raw position (mx, my), which is quantised and stored exactly as uvs_lt_set_undistort does.  The slot's
+ * state is the same, so uvs_lt_get_remap, uvs_lt_undistort and uvs_lt_detect_track work on it unchanged; a PINHOLE model whose output pinhole
+ * is its own (fx, fy, cx, cy) gives uvs_lt_set_undistort's map.  model == NULL switches the slot's map off.
+ *
+ * UVS_ERR_INVALID_ARG: a null pointer, n < 0, an unknown model id, a parameter p[0 .. count) that is not finite, a scale (fx / fy, gamma1 /
+ * gamma2, mu / mv, fx_out / fy_out) <= 0, xi < 0, and for the map the size and margin checks of uvs_lt_set_undistort (UVS_ERR_CAPACITY alike).
+ * A rejected call changes nothing, and the handle stays usable after it.  DESIGN.md 3.18 has the kernel plan.  No CPU path. */
+#define UVS_CAM_PINHOLE 0
+#define UVS_CAM_MEI 1
+#define UVS_CAM_KANNALA_BRANDT 2
+#define UVS_CAM_KB_ITERATIONS 32              /* most Newton / bisection steps of the Kannala-Brandt root search */
+typedef struct uvs_camera_model {
+    int32_t model;      /* UVS_CAM_* */
+    int32_t reserved;
+    double  p[12];      /* PINHOLE: fx fy cx cy k1 k2 p1 p2 | MEI: xi k1 k2 p1 p2 gamma1 gamma2 u0 v0 | KANNALA_BRANDT: k2 k3 k4 k5 mu mv u0 v0 */
+} uvs_camera_model;
+int uvs_ft_set_camera_model(uvs_ft_tracker *ft, const uvs_camera_model *model);
+int uvs_kf_set_camera_model(uvs_kf_extractor *kf, const uvs_camera_model *model);
+int uvs_ft_lift(uvs_ft_tracker *ft, const uvs_camera_model *model, int n, const double *xy, double *ray, double *norm);
+int uvs_ft_project(uvs_ft_tracker *ft, const uvs_camera_model *model, int n, const double *ray, double *xy);
+int uvs_lt_set_undistort_model(uvs_lt_tracker *lt, int stream, const uvs_camera_model *model, int width, int height, int col_margin,
+                               int row_margin, double fx_out, double fy_out, double cx_out, double cy_out);
+
 /* ---- place recognition of loop closure (reference pose_graph/src/pose_graph.cpp:304-386 detectLoop; ThirdParty/DBoW/TemplatedVocabulary.h
  * transform, TemplatedDatabase.h add / queryL1, BowVector.cpp addWeight / normalize) ----
  * Which old keyframe to try: a vocabulary tree over 256-bit BRIEF descriptors, the tf-idf bag-of-words vector of a keyframe, and the L1 query

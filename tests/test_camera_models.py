@@ -1,0 +1,625 @@
+"""The camera models of the front ends (include/uvs_solver.h: uvs_camera_model, uvs_ft_set_camera_model, uvs_kf_set_camera_model, uvs_ft_lift,
+uvs_ft_project, uvs_lt_set_undistort_model; csrc/uvs_camera_models.h and .hip).
+
+CPU: tests/cm_ref.py, the FP64 restatement, against a 60-digit evaluation of the reference's definition (E_ref); the round trip; the pinhole
+given as a model; the calibration loader; the host mirror; the recovery of straight edges from a 150-degree fisheye frame by the numpy chain.
+GPU: the device against cm_ref, bit for bit for PINHOLE and MEI, within 4 E_ref of the 60-digit reference for Kannala-Brandt; the lifts inside
+uvs_ft_track, uvs_ft_detect and uvs_kf_extract; the map of uvs_lt_set_undistort_model and uvs_lt_detect_track on it; the argument checks."""
+import ctypes as C
+import os
+
+import mpmath
+import numpy as np
+import pytest
+
+import cm_cases as cc
+import cm_ref
+import fd_cases
+import ft_cases
+import kf_cases
+import kf_ref
+import ld_cases
+import lt_cases
+import lt_ref
+import ud_cases
+import ud_ref
+from helpers import uvs, abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CM_SYMBOLS = ["uvs_ft_set_camera_model", "uvs_kf_set_camera_model", "uvs_ft_lift", "uvs_ft_project", "uvs_lt_set_undistort_model"]
+INV = abi.UVS_ERR_INVALID_ARG
+KB_MODELS = tuple(n for n in cc.MODEL_NAMES if cc.models()[n][0] == cc.KB)
+EXACT_MODELS = tuple(n for n in cc.MODEL_NAMES if cc.models()[n][0] != cc.KB)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def model_of(name):
+    model, params, _, _ = cc.models()[name]
+    return abi.camera_model(model, params)
+
+
+# ================================================================ CPU: the definition
+def test_symbols_are_declared_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "uvs_solver.h")).read()
+    L = uvs.api.lib()
+    for s in CM_SYMBOLS:
+        assert s + "(" in hdr and s in uvs.api.EXPORTS and hasattr(L, s), s
+    assert "#define UVS_ABI_VERSION 7" in hdr and L.uvs_abi_version() == 7
+    assert C.sizeof(abi.CameraModel) == 8 + 12 * 8
+    for name, value in (("UVS_CAM_PINHOLE", abi.CAM_PINHOLE), ("UVS_CAM_MEI", abi.CAM_MEI), ("UVS_CAM_KANNALA_BRANDT", abi.CAM_KANNALA_BRANDT),
+                        ("UVS_CAM_KB_ITERATIONS", abi.CAM_KB_ITERATIONS)):
+        assert f"#define {name} {value}" in hdr, name
+    assert cm_ref.KB_ITERATIONS == abi.CAM_KB_ITERATIONS
+
+
+def test_definition_restatement_against_60_digits():
+    """cm_ref's FP64 rays against the 60-digit evaluation of the reference's definition: on every model's points (cm_cases) and on a grid, the
+    corners and the principal point of the five shipped image rectangles.  For Kannala-Brandt this shows that the safeguarded Newton iteration
+    on the first branch returns the reference's root, the smallest non-negative real one among all roots, at every such pixel: no pixel of a
+    shipped rectangle takes the fallback.  The largest error is E_ref; cm_cases.E_REF records it and the device's allowance is built on it.
+    Measured: 3.5e-16 on the grids (tum), 1.165e-15 over the points (realsense_fisheye just above th = pi / 2, where r' is small), below
+    4.9e-16 on every other model's points."""
+    worst = 0.0
+    for name in cc.FIXTURES:
+        model, params, _, _ = cc.models()[name]
+        g = cc.grid(name)
+        ray, _ = cm_ref.lift(model, params, g)
+        hp, dev = cm_ref.lift_hp(model, params, g)
+        assert not dev.any(), (name, g[dev])                  # inside a shipped image the reference's root IS on the first branch
+        e = cm_ref.ray_error(ray, hp).max()
+        print(f"E_ref grid {name}: {e:.3e}")
+        worst = max(worst, e)
+    for name in cc.MODEL_NAMES:
+        model, params, _, _ = cc.models()[name]
+        ray = cc.lifted(name)[0][:cc.N_HP]
+        hp, dev = cc.lifted_hp(name)
+        e = cm_ref.ray_error(ray, hp).max()
+        print(f"E_ref points {name}: {e:.3e} ({int(dev.sum())} beyond the branch)")
+        worst = max(worst, e)
+        P = cm_ref.pack(model, params)
+        if model == cc.KB and P.flag:                         # the reference leaves the first branch exactly where the library takes th = r
+            p = cc.points(name)[:cc.N_HP]
+            rr = np.hypot((p[:, 0] - P.u0) / P.sx, (p[:, 1] - P.v0) / P.sy)
+            assert np.array_equal(dev, ~(rr < P.r_max)), name
+            assert dev[8] == (1.1 * P.r_max < cc.BEYOND_LIMIT) and not dev[[0, 1, 6, 7]].any(), name
+        else:
+            assert not dev.any(), name
+    print(f"E_ref = {worst:.3e}")
+    assert worst <= cc.E_REF
+    assert cc.E_REF <= 8 * 2.0 ** -52                         # the record is of the order of the format's precision, not a loose bound
+
+
+def test_kannala_brandt_root_search_is_short_and_bounded():
+    """Inside the shipped images the search ends by its own exits after a handful of steps (the tracker runs it on one lane of a wave); nowhere
+    does it need the cap.  Measured over EVERY pixel of the three images: 2 .. 6 steps for tum, 2 .. 5 for cla, 2 .. 7 for realsense_fisheye,
+    3.3 to 3.8 on average; every third pixel here shows the same extremes."""
+    for name, most in zip(cc.KB_FIXTURES, (6, 5, 7)):
+        model, params, W, H = cc.models()[name]
+        P = cm_ref.pack(model, params)
+        v, u = np.mgrid[0:H:3, 0:W:3].astype(np.float64)
+        rr = np.hypot((u.ravel() - P.u0) / P.sx, (v.ravel() - P.v0) / P.sy)
+        th, steps = cm_ref.kb_theta(P, rr, return_steps=True)
+        assert 2 <= steps.min() and steps.max() <= most and 3.0 < steps.mean() < 4.0, (name, steps.min(), steps.max(), steps.mean())
+        assert np.abs(cm_ref._kb_r(P.c, th) - rr).max() <= 4 * 2.0 ** -52 * max(1.0, rr.max())
+    # th_max: pi where r' stays positive, the first zero of r' otherwise
+    assert cm_ref.pack(*cc.models()["tum"][:2]).c[4] == np.float64(3.141592653589793)
+    P = cm_ref.pack(*cc.models()["realsense_fisheye"][:2])
+    assert 1.5 < P.c[4] < 1.7 and cm_ref._kb_dr(P.c, P.c[4]) > 0 >= cm_ref._kb_dr(P.c, np.nextafter(P.c[4], 4.0))
+
+
+def _mei_inverse_residual(params, W, H):
+    """A bound on what the eight passes of the recursive distortion model leave: the fixed-point iteration x <- xd - D(x) contracts by
+    L = max |dD/dx| over the image, so after 8 passes the error is at most L^8 max |D| / (1 - L) in normalized units."""
+    xi, k1, k2, p1, p2, g1, g2, u0, v0 = params
+    r = max(np.hypot((x - u0) / g1, (y - v0) / g2) for x in (0, W - 1) for y in (0, H - 1)) * 1.05
+    r2 = r * r
+    L = 3 * abs(k1) * r2 + 5 * abs(k2) * r2 * r2 + 6 * (abs(p1) + abs(p2)) * r
+    D = r * (abs(k1) * r2 + abs(k2) * r2 * r2) + 3 * (abs(p1) + abs(p2)) * r2
+    assert L < 0.5
+    return L ** 8 * D / (1 - L)
+
+
+def _round_trip_bound(scale, z_min, pixel_max):
+    """What project(lift(p)) - p may be, in pixels, from E_ref and the model's scale.  lift leaves each ray component within E_ref of the exact
+    ray; that turns the ray by at most sqrt(2) E_ref, and project's own atan2 / sqrt and polynomial (or, for MEI, its division by z) are as
+    accurate again: 2 sqrt(2) E_ref in angle.  A pixel moves by scale * r'(th) per radian for Kannala-Brandt, r' <= 1.4 inside the shipped
+    images, and by scale / z^2 per unit of the normalized plane for MEI: 2 sqrt(2) 1.4 < 4, hence 4 scale E_ref / z_min^2 (z_min = 1 for
+    Kannala-Brandt).  The last two operations, scale * u and + u0, each round at the pixel's own magnitude: 2 ulp(max |pixel|)."""
+    return 4 * scale * cc.E_REF / z_min ** 2 + 2 * float(np.spacing(pixel_max))
+
+
+@pytest.mark.parametrize("name", cc.FIXTURES)
+def test_round_trip(name):
+    """project(lift(p)) = p over the image, within _round_trip_bound: 4 mu E_ref + 2 ulp(pixel) for Kannala-Brandt (9e-13 .. 2.5e-12 px; measured
+    1.1e-13 on the grids, 2.3e-13 over every third pixel).  For MEI the reference's inverse is eight passes of a fixed-point iteration, not
+    the exact inverse: what it leaves is bounded by _mei_inverse_residual and added.  (The pinhole's round trip is
+    tests/test_keyframe_features.py's.)"""
+    model, params, W, H = cc.models()[name]
+    g = cc.grid(name)
+    if model == cc.KB:                                        # ... and every third pixel of the image
+        v, u = np.mgrid[0:H:3, 0:W:3].astype(np.float64)
+        g = np.concatenate([g, np.stack([u.ravel(), v.ravel()], 1)])
+    ray, _ = cm_ref.lift(model, params, g)
+    back = cm_ref.project(model, params, ray)
+    P = cm_ref.pack(model, params)
+    scale = float(max(P.sx, P.sy))
+    z_min = 1.0 if model == cc.KB else float(np.abs(ray[:, 2]).min())
+    if model == cc.KB:                                        # what _round_trip_bound takes for granted
+        assert cm_ref._kb_dr(P.c, np.arccos(np.clip(ray[:, 2], -1, 1))).max() <= 1.4
+    bound = _round_trip_bound(scale, z_min, float(np.abs(g).max()))
+    if model == cc.MEI:
+        bound += 2 * scale * _mei_inverse_residual(params, W, H)
+    err = float(np.abs(back - g).max())
+    print(f"round trip {name}: {err:.3e} px, bound {bound:.3e}")
+    assert err <= bound
+    # ... and at 60 digits the reference's spaceToPlane of the 60-digit ray gives the same pixel: project is the reference's map.  The same
+    # bound without the inverse's residual: the 60-digit ray enters project rounded to FP64, which is within E_ref of it
+    hp, _ = cm_ref.lift_hp(model, params, g[:8])
+    p_hp = cm_ref.project_hp(model, params, hp)
+    back_hp = cm_ref.project(model, params, np.array([[float(c) for c in r] for r in hp]))
+    e = max(abs(float(mpmath.mpf(float(b)) - q)) for row, qrow in zip(back_hp, p_hp) for b, q in zip(row, qrow))
+    print(f"project against the 60-digit spaceToPlane {name}: {e:.3e} px")
+    assert e <= _round_trip_bound(scale, 1.0 if model == cc.KB else float(np.abs(ray[:8, 2]).min()), float(np.abs(g[:8]).max()))
+
+
+@pytest.mark.parametrize("name", ("pinhole", "pinhole_no_distortion"))
+def test_pinhole_model_equals_the_pinhole(name):
+    model, params, _, _ = cc.models()[name]
+    ray, norm = cc.lifted(name)
+    want = kf_ref.lift(params, cc.points(name))
+    assert np.array_equal(bits(norm), bits(want)) and np.array_equal(bits(ray[:, :2]), bits(want)) and (ray[:, 2] == 1.0).all()
+    # project is the forward map of uvs_lt_set_undistort: the maps agree word for word
+    c = ud_cases.CASES["96x80_m5_pincushion"]
+    got = cm_ref.build_map(cc.PINHOLE, c["cam"], c["W"], c["H"], c["cam"][:4], c["cm"], c["rm"])
+    assert np.array_equal(got, ud_ref.build_map(c["cam"], c["W"], c["H"], c["cm"], c["rm"]))
+
+
+def test_calibration_loader_reads_the_fixtures(tmp_path):
+    want = {
+        "tum": (abi.CAM_KANNALA_BRANDT, 512, 512, (0.0034823894022493434, 0.0007150348452162257, -0.0020532361418706202, 0.00020293673591811182,
+                                                   190.97847715128717, 190.9733070521226, 254.93170605935475, 256.8974428996504)),
+        "cla": (abi.CAM_KANNALA_BRANDT, 752, 480, (-0.005740195474458931, 0.02878252863739417, -0.04010621197185408, 0.02008469575876223,
+                                                   472.2863830700696, 470.83759684346785, 368.8316828103749, 232.23688706965652)),
+        "realsense_fisheye": (abi.CAM_KANNALA_BRANDT, 640, 480, (1.7280355035195181e-02, -2.5505200860040985e-02, 2.2621441637715487e-02,
+                                                                 -7.3355871719731113e-03, 2.7723712054408202e+02, 2.7699784668734617e+02,
+                                                                 3.3625356873985868e+02, 2.3603924727453901e+02)),
+    }
+    for name, (model, W, H, params) in want.items():
+        f = cc.fixture(name)
+        assert (f["model"], f["width"], f["height"], f["params"]) == (model, W, H, params), name
+    for name in ("black_box", "3dm"):
+        f = cc.fixture(name)
+        assert f["model"] == abi.CAM_MEI and f["model_type"] == "MEI" and (f["width"], f["height"]) == (752, 480) and len(f["params"]) == 9
+    bb = cc.fixture("black_box")["params"]
+    assert bb[0] == 2.2134257311108083 and bb[1] == 1.4213768437132895e-01 and bb[5] == 1.1659242643040975e+03 and bb[7] == 3.9238492754088008e+02
+    assert cc.fixture("3dm")["params"][:5] == (2.057, 7.145e-02, 5.059e-01, 4.727e-05, -5.492e-04)
+    # a pinhole file, and the failures
+    p = tmp_path / "pinhole.yaml"
+    p.write_text("%YAML:1.0\n---\nmodel_type: PINHOLE\ncamera_name: cam0\nimage_width: 752\nimage_height: 480\ndistortion_parameters:\n   k1: -2.917e-01\n"
+                 "   k2: 8.228e-02\n   p1: 5.333e-05\n   p2: -1.578e-04\nprojection_parameters:\n   fx: 4.616e+02\n   fy: 4.603e+02\n   cx: 3.630e+02\n"
+                 "   cy: 2.481e+02\n")
+    f = abi.load_camera_calibration(str(p))
+    assert f["model"] == abi.CAM_PINHOLE and f["params"] == (461.6, 460.3, 363.0, 248.1, -0.2917, 0.08228, 5.333e-05, -1.578e-04) and f["camera_name"] == "cam0"
+    m = abi.camera_model(f)
+    assert m.as_tuple() == (abi.CAM_PINHOLE, f["params"])
+    p.write_text("model_type: SCARAMUZZA\n")
+    with pytest.raises(ValueError):
+        abi.load_camera_calibration(str(p))
+    p.write_text("model_type: MEI\nmirror_parameters:\n   xi: 1.0\n")
+    with pytest.raises(ValueError):
+        abi.load_camera_calibration(str(p))
+
+
+def _host():
+    L = C.CDLL(os.path.join(ROOT, "uv-slam_amd", "libuvs_host.so"))
+    L.uvs_host_ft_create_model.restype = C.c_void_p
+    L.uvs_host_ft_create_model.argtypes = [C.c_int, C.c_int, C.c_int, abi.c_double_p] + [C.c_int] * 4
+    L.uvs_host_ft_destroy.argtypes = [C.c_void_p]; L.uvs_host_ft_destroy.restype = None
+    L.uvs_host_ft_read_flow.argtypes = [C.c_void_p, C.c_double, C.c_int, abi.c_double_p, abi.c_i32_p, abi.c_double_p, C.c_int, abi.c_double_p]
+    L.uvs_host_ft_update_ids.argtypes = [C.c_void_p]
+    L.uvs_host_ft_get.argtypes = [C.c_void_p, C.c_int, abi.c_double_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p, abi.c_double_p]
+    return L
+
+
+@pytest.mark.parametrize("name", ("tum", "black_box", "pinhole"))
+def test_host_mirror_lifts_through_the_model(name):
+    """uvs::FeatureTrackerBook constructed from a camera model (no device): the points a frame adds are lifted by the header's own function, so
+    cur_un_pts are cm_ref's normalized points (bit for bit for MEI and the pinhole; Kannala-Brandt within the device's allowance, since sin and
+    cos are the C library's here) and pts_velocity is their difference over dt."""
+    L = _host()
+    model, params, _, _ = cc.models()[name]
+    pr = np.array(params, np.float64)
+    h = L.uvs_host_ft_create_model(-1, model, len(pr), abi._dp(pr), 0, 0, 0, 0)
+    assert h
+    a = np.ascontiguousarray(cc.points(name)[[0, 2, 5, 9, 10, 11, 12]])
+    want = cc.lifted(name)[1][[0, 2, 5, 9, 10, 11, 12]]
+    assert L.uvs_host_ft_read_flow(h, 0.0, 0, None, None, None, len(a), abi._dp(a)) == 0 and L.uvs_host_ft_update_ids(h) == len(a)
+
+    def get():
+        n = L.uvs_host_ft_get(h, 0, None, None, None, None, None)
+        o = [np.zeros((n, 2)), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 2)), np.zeros((n, 2))]
+        L.uvs_host_ft_get(h, n, abi._dp(o[0]), o[1].ctypes.data_as(abi.c_i32_p), o[2].ctypes.data_as(abi.c_i32_p), abi._dp(o[3]), abi._dp(o[4]))
+        return o
+
+    un = get()[3]
+    if model == cc.KB:
+        assert (np.abs(un - want) <= cc.KB_ALLOWANCE * (1 + (want ** 2).sum(1))[:, None]).all()
+    else:
+        assert np.array_equal(bits(un), bits(want))
+    # the next frame: the flow moves every point one pixel right, the device's normalized points are given (here cm_ref's)
+    b = a + np.array([1.0, 0.0])
+    nb = cm_ref.lift(model, params, b)[1]
+    st = np.zeros(len(a), np.int32)
+    assert L.uvs_host_ft_read_flow(h, 0.5, len(a), abi._dp(b), st.ctypes.data_as(abi.c_i32_p), abi._dp(nb), 0, None) == 0
+    assert np.array_equal(bits(get()[3]), bits(nb))
+    c = b + np.array([0.0, 1.0])                              # (the first frame's points had no ids yet: velocities start with the third)
+    nc = cm_ref.lift(model, params, c)[1]
+    assert L.uvs_host_ft_read_flow(h, 1.0, len(a), abi._dp(c), st.ctypes.data_as(abi.c_i32_p), abi._dp(nc), 0, None) == 0
+    o = get()
+    assert np.array_equal(bits(o[3]), bits(nc)) and np.array_equal(bits(o[4]), bits((nc - nb) / 0.5)) and o[4].any()
+    L.uvs_host_ft_destroy(h)
+    # a model the library would reject makes no tracker
+    bad = pr.copy(); bad[{cc.KB: 4, cc.MEI: 5, cc.PINHOLE: 0}[model]] = 0.0
+    assert not L.uvs_host_ft_create_model(-1, model, len(bad), abi._dp(bad), 0, 0, 0, 0)
+    assert not L.uvs_host_ft_create_model(-1, 7, len(pr), abi._dp(pr), 0, 0, 0, 0)
+
+
+def test_fisheye_bars_recovered_by_the_numpy_chain():
+    """The bars of ld_cases through a Kannala-Brandt camera of 150 degrees (cm_cases.BAR_KB): cm_ref's map, ud_ref's remap, then ld_ref finds
+    both long edges of every bar under test_line_undistort's thresholds for its barrel camera (cover >= 0.9, offset <= 1.0 px).  The raw frame
+    loses all six.  No word of the map is within the Kannala-Brandt slack of a half-integer, so the device must give these bytes."""
+    sc = cc.bar_scene()
+    fits = ud_cases.edge_fits(cc.bar_ref("undistorted")["seg"], sc["edges"])
+    assert all(f is not None and f[1] >= 0.9 and f[0] <= 1.0 for f in fits), fits
+    bent = ud_cases.edge_fits(cc.bar_ref("raw")["seg"], sc["edges"])
+    lost = sum(f is None or f[1] < 0.9 or f[0] > 1.0 for f in bent)
+    print(f"raw fisheye frame: {lost} of {len(bent)} edges lost")
+    assert lost == len(bent) == 6
+    assert not (sc["undistorted"] == 0).any()
+    assert not sc["near"].any() and sc["near"].mean() < 0.01
+    P = cm_ref.pack(sc["model"], sc["params"])                # the field of view: the corners look 75 degrees off the axis
+    corner = np.hypot((0 - P.u0) / P.sx, (0 - P.v0) / P.sy)
+    assert 145.0 < 2 * np.degrees(cm_ref.kb_theta(P, np.array([corner]))[0]) < 155.0
+
+
+def test_map_cases_have_few_words_near_a_half():
+    """The map cases of the GPU test, checked here with cm_ref alone: under 1 % of the Kannala-Brandt words may round the other way."""
+    for name in ("tum",):
+        model, params = _small_camera(name)
+        _, near = cm_ref.build_map(model, params, 131, 97, _small_out(name), 5, 3, slack=params[4] * cc.KB_ALLOWANCE)
+        assert near.mean() < 0.01, (name, near.mean())
+
+
+def _small_camera(name):
+    """A fixture's camera for an image of 131 x 97: the scales and the centre shrunk by 131 / width."""
+    model, p, W, _ = cc.models()[name]
+    s = 131.0 / W
+    k = len(p) - 4
+    return model, tuple(p[:k]) + tuple(v * s for v in p[k:])
+
+
+def _small_out(name):
+    _, p = _small_camera(name)
+    return (0.7 * p[-4], 0.7 * p[-3], p[-2], p[-1])
+
+
+# ================================================================ GPU
+@pytest.fixture(scope="module")
+def ft():
+    t = uvs.api.FeatureTracker(device=0, max_streams=1, max_width=96, max_height=80, levels=2, max_points=64)
+    yield t
+    t.close()
+
+
+@pytest.fixture(scope="module")
+def lt():
+    t = uvs.api.LineTracker(device=0, max_streams=1, max_width=ud_cases.MAX_W, max_height=ud_cases.MAX_H, max_lines=ld_cases.MAX_LINES,
+                            max_length=lt_cases.MAX_LENGTH)
+    yield t
+    t.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", EXACT_MODELS)
+def test_gpu_lift_project_pinhole_and_mei_bit_for_bit(ft, name):
+    m = model_of(name)
+    pts = cc.points(name)
+    want_ray, want_norm = cc.lifted(name)
+    for n in cc.BATCHES:
+        ray, norm = ft.lift(m, pts[:n])
+        assert np.array_equal(bits(ray), bits(want_ray[:n])) and np.array_equal(bits(norm), bits(want_norm[:n])), (name, n)
+        xy = ft.project(m, want_ray[:n])
+        model, params, _, _ = cc.models()[name]
+        assert np.array_equal(bits(xy), bits(cm_ref.project(model, params, want_ray[:n]))), (name, n)
+    only_norm = ft.lift_raw(m, pts[:5], null=("ray",)); only_ray = ft.lift_raw(m, pts[:5], null=("norm",))
+    assert only_norm[0] == only_ray[0] == abi.UVS_OK
+    assert np.array_equal(bits(only_norm[2]), bits(want_norm[:5])) and np.array_equal(bits(only_ray[1]), bits(want_ray[:5]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", KB_MODELS)
+def test_gpu_lift_project_kannala_brandt(ft, name):
+    """Rays within max(4 E_ref, 8 * 2^-52) of the 60-digit reference, absolutely; normalized points within that times 1 + mx^2 + my^2, the
+    conditioning of the division by z.  A batch gives every point the bits it gets alone.  Measured on the device: rays 1.165e-15
+    (realsense_fisheye, the restatement's own worst pixel), normalized points 1.163e-15."""
+    m = model_of(name)
+    model, params, _, _ = cc.models()[name]
+    pts = cc.points(name)
+    hp, _ = cc.lifted_hp(name)
+    got = {n: ft.lift(m, pts[:n]) for n in cc.BATCHES}
+    ray, norm = got[65]
+    e_ray = cm_ref.ray_error(ray, hp)
+    print(f"device ray error {name}: {e_ray.max():.3e} (allowance {cc.KB_ALLOWANCE:.3e})")
+    assert e_ray.max() <= cc.KB_ALLOWANCE, (name, int(e_ray.argmax()), e_ray.max())
+    worst = 0.0
+    for i, h in enumerate(hp):
+        if abs(h[2]) < 1e-3:
+            continue
+        nh = (h[0] / h[2], h[1] / h[2])
+        cond = float(1 + nh[0] ** 2 + nh[1] ** 2)
+        e = max(abs(float(mpmath.mpf(float(norm[i, k])) - nh[k])) for k in range(2)) / cond
+        worst = max(worst, e)
+        assert e <= cc.KB_ALLOWANCE, (name, i, e)
+    print(f"device normalized-point error / conditioning {name}: {worst:.3e}")
+    for n in cc.BATCHES:                                      # the first n points of every batch are the same points
+        k = min(n, 65)
+        assert np.array_equal(bits(got[n][0][:k]), bits(ray[:k])) and np.array_equal(bits(got[n][1][:k]), bits(norm[:k])), (name, n)
+    # all 1000 points against the FP64 restatement (itself within E_ref of the 60 digits on the first 65), under the same allowance
+    ref_ray, ref_norm = cc.lifted(name)
+    big_ray, big_norm = got[1000]
+    e_all = np.abs(big_ray - ref_ray).max()
+    cond = 1 + (ref_norm ** 2).sum(1)
+    print(f"device against cm_ref over 1000 points {name}: rays {e_all:.3e}, normalized / conditioning {(np.abs(big_norm - ref_norm).max(1) / cond).max():.3e}")
+    assert e_all <= cc.KB_ALLOWANCE and (np.abs(big_norm - ref_norm) <= cc.KB_ALLOWANCE * cond[:, None]).all(), name
+    for i in (63, 64, 65, 255, 256, 999):                     # ... and points beyond the first waves, alone against the batch of 1000
+        r1, n1 = ft.lift(m, pts[i:i + 1])
+        assert np.array_equal(bits(r1[0]), bits(got[1000][0][i])) and np.array_equal(bits(n1[0]), bits(got[1000][1][i])), (name, i)
+    # z <= 0 above pi / 2, the fallback beyond the branch
+    P = cm_ref.pack(model, params)
+    assert ray[6, 2] > 0 >= ray[7, 2]
+    if P.flag and 1.1 * P.r_max < cc.BEYOND_LIMIT:
+        assert abs(ray[8, 2] - np.cos(1.1 * P.r_max)) <= cc.KB_ALLOWANCE
+    # project: the pixel within scale * allowance * |pixel| of cm_ref's (atan2 and the polynomial; the 60-digit round trip is test_round_trip's)
+    want_ray = cc.lifted(name)[0]
+    xy = ft.project(m, want_ray)
+    ref = cm_ref.project(model, params, want_ray)
+    tol = float(max(P.sx, P.sy)) * cc.KB_ALLOWANCE * np.maximum(1.0, np.abs(ref))
+    assert (np.abs(xy - ref) <= tol).all(), (name, float(np.abs(xy - ref).max()))
+    for i in (0, 64, 999):
+        assert np.array_equal(bits(ft.project(m, want_ray[i:i + 1])[0]), bits(xy[i])), (name, i)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("tum", "black_box"))
+def test_gpu_lift_inside_track_detect_and_extract(name):
+    """With a model on the handle, positions, statuses, corners and descriptors are those of the numpy pins (the model does not touch them) and
+    the normalized points are uvs_ft_lift of the returned pixels, bit for bit: one device function.  After set_camera_model(None) the calls
+    with a uvs_kf_camera return what they returned before."""
+    m = model_of(name)
+    sc = ft_cases.scene("shift_48x40_L1"); want = ft_cases.scene_ref("shift_48x40_L1")
+    t = uvs.api.FeatureTracker(device=0, max_streams=1, max_width=48, max_height=40, levels=1, max_points=len(sc["pts"]))
+
+    def run(camera):
+        t.reset(0)
+        t.track([dict(stream=0, image=sc["prev"])], camera)
+        tr = t.track([dict(stream=0, image=sc["next"], points=sc["pts"])], camera)[0]
+        c = fd_cases.case("scene_48x40")
+        t.reset(0)
+        t.track([dict(stream=0, image=c["image"])], camera)
+        de = t.detect([dict(stream=0, occupied=c["occupied"], max_new=c["max_new"])], camera, quality_level=0.01, min_distance=c["R"])[0]
+        return tr, de
+
+    before = run(ft_cases.CAM)
+    t.set_camera_model(m)
+    t.reset(0)                                                # the model is the handle's: it survives
+    for camera in (None, ft_cases.CAM):                       # `camera` may be NULL and is ignored if given
+        tr, de = run(camera)
+        for k in ("status", "iterations"):
+            assert np.array_equal(tr[k], want[k]), k
+        assert np.array_equal(bits(tr["next_xy"]), bits(want["next_xy"])) and tr["n_tracked"] == want["n_tracked"] > 5
+        ok = tr["status"] == 0
+        _, nm = t.lift(m, tr["next_xy"][ok])
+        assert np.array_equal(bits(tr["next_norm"][ok]), bits(nm)) and not tr["next_norm"][~ok].any()
+        ref = fd_cases.ref("scene_48x40")
+        assert de["n_new"] == ref["n_new"] > 3 and np.array_equal(de["xy"], ref["xy"]) and np.array_equal(bits(de["score"]), bits(ref["score"]))
+        _, nm = t.lift(m, de["xy"].astype(np.float64))
+        assert np.array_equal(bits(de["norm"]), bits(nm))
+        assert not np.array_equal(bits(de["norm"]), bits(ref["norm"]))
+    t.set_camera_model(None)
+    after = run(ft_cases.CAM)
+    for a, b in zip(before, after):
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(bits(after[0]["next_norm"]), bits(want["next_norm"]))
+    assert t.track_raw([dict(stream=0, image=sc["prev"])], None)[0] == INV      # without a model the camera is required again
+    # the extractor
+    img = kf_cases.texture(40, 96, 72, 20); uv = kf_cases.window_points(40, 8, 96, 72)
+    kf = uvs.api.KeyframeExtractor(kf_cases.pattern(), device=0, max_frames=1, max_width=96, max_height=72, max_keypoints=256, max_window=16)
+    ref = kf_ref.extract(img, uv, kf_cases.CAM_DIST, kf_cases.pattern(), max_keypoints=256)
+    before = kf.extract([dict(image=img, window_uv=uv)], kf_cases.CAM_DIST)[0]
+    kf.set_camera_model(m)
+    for camera in (None, kf_cases.CAM_DIST):
+        got = kf.extract([dict(image=img, window_uv=uv)], camera)[0]
+        assert got["n_keypoints"] == ref["n_keypoints"] > 5
+        for k in ("xy", "score", "desc", "window_desc"):
+            assert np.array_equal(got[k], ref[k]), k
+        _, nm = t.lift(m, got["xy"].astype(np.float64))
+        assert np.array_equal(bits(got["norm"]), bits(nm)) and not np.array_equal(bits(got["norm"]), bits(ref["norm"]))
+    dbg = kf.debug_frame(dict(image=img, window_uv=uv), None)
+    assert np.array_equal(bits(dbg["norm"]), bits(got["norm"]))
+    kf.set_camera_model(None)
+    after = kf.extract([dict(image=img, window_uv=uv)], kf_cases.CAM_DIST)[0]
+    for k in ("xy", "score", "desc", "window_desc", "norm"):
+        assert np.array_equal(before[k], after[k]), k
+    assert np.array_equal(bits(after["norm"]), bits(ref["norm"]))
+    assert kf.extract_raw([dict(image=img, window_uv=uv)], None)[0] == INV
+    kf.close(); t.close()
+
+
+@pytest.mark.gpu
+def test_gpu_undistort_model_map(lt):
+    W, H = 131, 97
+    # MEI and PINHOLE: word for word
+    model, params = cc.bar_mei_model()
+    out = (0.5 * params[5], 0.5 * params[6], params[7], params[8])
+    for cm, rm in ((0, 0), (5, 3)):
+        lt.set_undistort_model(0, abi.camera_model(model, params), W, H, out, cm, rm)
+        assert np.array_equal(lt.get_remap(0), cm_ref.build_map(model, params, W, H, out, cm, rm)), (cm, rm)
+    # a PINHOLE model whose output pinhole is its own gives uvs_lt_set_undistort's map
+    for cname in ("96x80_m5_pincushion", "131x97_m0_barrel"):
+        c = ud_cases.CASES[cname]
+        lt.set_undistort(0, c["cam"], c["W"], c["H"], c["cm"], c["rm"])
+        want = lt.get_remap(0)
+        lt.set_undistort_model(0, abi.camera_model(abi.CAM_PINHOLE, c["cam"]), c["W"], c["H"], c["cam"][:4], c["cm"], c["rm"])
+        assert np.array_equal(lt.get_remap(0), want) and np.array_equal(want, ud_cases.ref_map(cname)), cname
+    # Kannala-Brandt: equal but where 32 m is within the slack of a half-integer, and there off by one at most
+    model, params = _small_camera("tum")
+    want, near = cm_ref.build_map(model, params, W, H, _small_out("tum"), 5, 3, slack=params[4] * cc.KB_ALLOWANCE)
+    lt.set_undistort_model(0, abi.camera_model(model, params), W, H, _small_out("tum"), 5, 3)
+    got = lt.get_remap(0)
+    diff = got.astype(np.int64) - want
+    print(f"Kannala-Brandt map: {int((diff != 0).sum())} of {diff.size} words differ, {int(near.sum())} within the slack")
+    assert got.shape == (H - 6, W - 10, 2) and not diff[~near].any() and np.abs(diff).max() <= 1
+    lt.set_undistort_model(0, None, 0, 0, (1, 1, 0, 0))
+    assert lt.get_remap_raw(0)[0] == INV
+
+
+@pytest.mark.gpu
+def test_gpu_fisheye_bars_through_detect_track(lt):
+    """The fisheye bars frame through uvs_lt_detect_track on the model's map equals the numpy chain of the CPU recovery test: no word of this
+    map is within the slack of a half-integer (test_fisheye_bars_recovered_by_the_numpy_chain), so the map, the image and the detection agree
+    to the last bit."""
+    sc = cc.bar_scene()
+    lt.reset(0)
+    lt.set_undistort_model(0, abi.camera_model(sc["model"], sc["params"]), sc["W"], sc["H"], sc["out_cam"])
+    assert np.array_equal(lt.get_remap(0), sc["map"])
+    assert np.array_equal(lt.undistort([dict(stream=0, image=sc["raw"])])[0], sc["undistorted"])
+    got = lt.detect_track([dict(stream=0, image=sc["raw"])], **ld_cases.PARAMS)[0]
+    want = cc.bar_ref("undistorted")
+    assert got["n_found"] == want["n_found"] == got["n_returned"] and np.array_equal(got["info"], want["info"])
+    assert np.array_equal(bits(got["seg"]), bits(want["seg"])) and np.array_equal(bits(got["width2"]), bits(want["width2"]))
+    slot = lt_ref.Slot(lt_cases.MAX_LENGTH)
+    wt = slot.track(sc["undistorted"], want["seg"])
+    assert np.array_equal(got["desc"], wt["desc"]) and np.array_equal(got["status"], wt["status"])
+    fits = ud_cases.edge_fits(got["seg"], sc["edges"])
+    assert all(f is not None and f[1] >= 0.9 and f[0] <= 1.0 for f in fits)
+    lt.set_undistort_model(0, None, 0, 0, (1, 1, 0, 0))
+    lt.reset(0)
+
+
+@pytest.mark.gpu
+def test_gpu_host_mirror_line_tracker_on_a_fisheye_frame():
+    """uvs::LineFeatureTracker::setUndistortion(model, output pinhole): readImage4Line(raw fisheye frame) finds the segments of the numpy chain."""
+    from test_line_detect import HostDetect, same_detection
+    sc = cc.bar_scene(); P = ld_cases.PARAMS
+    h = HostDetect(0, cam=sc["out_cam"], max_width=sc["W"], max_height=sc["H"], max_lines=ld_cases.MAX_LINES, margins=(0, 0))
+    h.L.uvs_host_lt_set_undistortion_model.argtypes = [C.c_void_p, C.c_int, C.c_int, abi.c_double_p, abi.c_double_p]
+    assert h.L.uvs_host_lt_set_detect(h.h, P["grad_threshold"], P["min_pixels"], P["min_length"]) == 0
+    pr = np.array(sc["params"], np.float64); out = np.array(sc["out_cam"], np.float64)
+    assert h.L.uvs_host_lt_set_undistortion_model(h.h, sc["model"], len(pr), abi._dp(pr), abi._dp(out)) == 0
+    assert h.read_image_detect(sc["raw"], 0.1) == 0
+    same_detection(h.last_detect(), cc.bar_ref("undistorted"), "host mirror on the fisheye frame")
+    bad = pr.copy(); bad[4] = 0.0                             # a rejected model reports the error and leaves the map
+    assert h.L.uvs_host_lt_set_undistortion_model(h.h, sc["model"], len(bad), abi._dp(bad), abi._dp(out)) == INV
+    assert h.read_image_detect(sc["raw"], 0.2) == 0 and h.last_detect()["n_returned"] == cc.bar_ref("undistorted")["n_returned"]
+    h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("tum", "black_box"))
+def test_gpu_host_mirror_feature_tracker_and_keyframe_with_a_model(ft, name):
+    """uvs::FeatureTracker(model): two frames through the device, cur_un_pts are uvs_ft_lift of the tracked pixels.  The online KeyFrame
+    constructors on one extractor: with the model keypoints_norm are uvs_ft_lift of the keypoints, and a keyframe built with a uvs_kf_camera
+    afterwards is lifted through that camera again."""
+    L = _host()
+    L.uvs_host_ft_read_image.argtypes = [C.c_void_p, abi.c_u8_p, C.c_int, C.c_int, C.c_double, C.c_int, abi.c_double_p]
+    model, params, _, _ = cc.models()[name]
+    m = model_of(name)
+    pr = np.array(params, np.float64)
+    sc = ft_cases.scene("shift_48x40_L1"); want = ft_cases.scene_ref("shift_48x40_L1")
+    pts = np.ascontiguousarray(sc["pts"], np.float64)
+    h = L.uvs_host_ft_create_model(0, model, len(pr), abi._dp(pr), 48, 40, 1, len(pts))
+    assert h
+    for t, img, new in ((0.0, sc["prev"], pts), (0.1, sc["next"], pts[:0])):
+        img = np.ascontiguousarray(img, np.uint8)
+        assert L.uvs_host_ft_read_image(h, img.ctypes.data_as(abi.c_u8_p), img.shape[1], img.shape[0], t, len(new), abi._dp(new) if len(new) else None) == 0
+        L.uvs_host_ft_update_ids(h)
+    n = L.uvs_host_ft_get(h, 0, None, None, None, None, None)
+    o = [np.zeros((n, 2)), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 2)), np.zeros((n, 2))]
+    L.uvs_host_ft_get(h, n, abi._dp(o[0]), o[1].ctypes.data_as(abi.c_i32_p), o[2].ctypes.data_as(abi.c_i32_p), abi._dp(o[3]), abi._dp(o[4]))
+    L.uvs_host_ft_destroy(h)
+    ok = want["status"] == 0
+    assert n == ok.sum() > 5 and np.array_equal(bits(o[0]), bits(want["next_xy"][ok])) and (o[2] == 2).all()
+    assert np.array_equal(bits(o[3]), bits(ft.lift(m, o[0])[1]))
+    # the keyframes: model, pinhole, model on one extractor
+    L.uvs_host_keyframe_online.argtypes = [C.c_int, C.POINTER(abi.KfCamera), C.c_int, C.c_int, abi.c_double_p, abi.c_i32_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           abi.c_u8_p, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p]
+    img = kf_cases.texture(40, 96, 72, 20)
+    images = np.ascontiguousarray(np.stack([img, img, img]), np.uint8)
+    pat = np.ascontiguousarray(kf_cases.pattern(), np.int32)
+    use = np.array([1, 0, 1], np.int32)
+    K = 256
+    n_kp = np.zeros(3, np.int32); xy = np.zeros((3, K, 2), np.int32); nm = np.zeros((3, K, 2))
+    cam = abi.kf_camera(kf_cases.CAM_DIST)
+    assert L.uvs_host_keyframe_online(0, C.byref(cam), model, len(pr), abi._dp(pr), pat.ctypes.data_as(abi.c_i32_p), K, 96, 72, 3,
+                                      images.ctypes.data_as(abi.c_u8_p), use.ctypes.data_as(abi.c_i32_p), n_kp.ctypes.data_as(abi.c_i32_p),
+                                      xy.ctypes.data_as(abi.c_i32_p), abi._dp(nm)) == 0
+    ref = kf_ref.extract(img, np.zeros((0, 2), np.float32), kf_cases.CAM_DIST, kf_cases.pattern(), max_keypoints=K)
+    k = ref["n_returned"]
+    assert (n_kp == k).all() and k > 5
+    lifted = ft.lift(m, ref["xy"].astype(np.float64))[1]
+    for f in range(3):
+        assert np.array_equal(xy[f, :k], ref["xy"])
+        assert np.array_equal(bits(nm[f, :k]), bits(lifted if use[f] else ref["norm"])), f
+
+
+@pytest.mark.gpu
+def test_gpu_errors_leave_the_handles_usable(ft, lt):
+    tum = cc.models()["tum"]; bb = cc.models()["black_box"]; ph = cc.models()["pinhole"]
+    pts = cc.points("tum")[:5]
+    want = cc.lifted("black_box")
+
+    def changed(m, i, v):
+        p = list(m[1]); p[i] = v
+        return abi.camera_model(m[0], p)
+
+    bad = [abi.camera_model(3, tum[1]), abi.camera_model(-1, tum[1]), changed(tum, 0, np.nan), changed(tum, 7, np.inf), changed(bb, 8, np.nan),
+           changed(tum, 4, 0.0), changed(tum, 5, -1.0), changed(bb, 5, 0.0), changed(bb, 6, -2.0), changed(ph, 0, 0.0), changed(ph, 1, -1.0),
+           changed(bb, 0, -0.5)]
+    good = model_of("black_box")
+    for b in bad:
+        assert ft.lift_raw(b, pts)[0] == INV and ft.project_raw(b, np.ones((2, 3)))[0] == INV
+        assert ft.set_camera_model_raw(b) == INV
+        assert lt.set_undistort_model_raw(0, b, 131, 97, (60, 60, 65, 48)) == INV
+        assert "uvs_" in ft.last_error()
+        ray, norm = ft.lift(good, cc.points("black_box")[:5])      # a successful call on the same handle
+        assert np.array_equal(bits(ray), bits(want[0][:5]))
+    kf = uvs.api.KeyframeExtractor(kf_cases.pattern(), device=0, max_frames=1, max_width=96, max_height=72, max_keypoints=64, max_window=16)
+    assert kf.set_camera_model_raw(bad[0]) == INV and kf.set_camera_model_raw(bad[2]) == INV and kf.set_camera_model_raw(good) == abi.UVS_OK
+    kf.close()
+    # an unused parameter slot is not looked at
+    m = model_of("tum"); m.p[8] = np.nan
+    assert ft.lift_raw(m, pts)[0] == abi.UVS_OK
+    # null pointers, n < 0, n = 0
+    for null in (("model",), ("xy",)):
+        assert ft.lift_raw(good, pts, null=null)[0] == INV
+    for null in (("model",), ("ray",), ("xy",)):
+        assert ft.project_raw(good, np.ones((2, 3)), null=null)[0] == INV
+    assert ft.lift_raw(good, pts, n=-1)[0] == INV and ft.project_raw(good, np.ones((2, 3)), n=-1)[0] == INV
+    assert ft.lift_raw(good, pts, n=0)[0] == abi.UVS_OK and ft.project_raw(good, np.ones((2, 3)), n=0)[0] == abi.UVS_OK
+    assert ft.lift_raw(good, pts, null=("ray", "norm"))[0] == abi.UVS_OK
+    # the map's own checks: the output pinhole, the margins, the sizes, the stream; a rejected call keeps the slot's map
+    lt.set_undistort_model(0, good, 131, 97, (60, 60, 65, 48))
+    keep = lt.get_remap(0)
+    for out in ((0, 60, 65, 48), (60, -1, 65, 48), (60, 60, np.nan, 48), (np.inf, 60, 65, 48)):
+        assert lt.set_undistort_model_raw(0, good, 131, 97, out) == INV
+    assert lt.set_undistort_model_raw(0, good, 131, 97, (60, 60, 65, 48), -1, 0) == INV
+    assert lt.set_undistort_model_raw(0, good, 131, 97, (60, 60, 65, 48), 0, 49) == INV
+    assert lt.set_undistort_model_raw(0, good, 7, 97, (60, 60, 65, 48)) == INV
+    assert lt.set_undistort_model_raw(1, good, 131, 97, (60, 60, 65, 48)) == INV
+    assert lt.set_undistort_model_raw(0, good, 132, 97, (60, 60, 65, 48)) == abi.UVS_ERR_CAPACITY
+    assert np.array_equal(lt.get_remap(0), keep)
+    lt.set_undistort_model(0, None, 0, 0, (1, 1, 0, 0))

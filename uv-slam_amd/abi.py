@@ -815,6 +815,76 @@ def lt_det_items(items):
 LT_UD_FRACTION_BITS = 5                  # a map word is a position in 1 / 32 px of the raw image
 LT_UD_LIMIT = 1 << 24                    # |X|, |Y| of a map word; uvs_lt_set_remap clamps to it
 
+# ---- camera models of the front ends (uvs_camera_model, uvs_ft_set_camera_model, uvs_ft_lift, uvs_lt_set_undistort_model, include/uvs_solver.h) ----
+CAM_PINHOLE, CAM_MEI, CAM_KANNALA_BRANDT = 0, 1, 2
+CAM_KB_ITERATIONS = 32
+# the order of uvs_camera_model.p, and the sections of camodocal's YAML that hold the names
+CAM_PARAMS = {CAM_PINHOLE: ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2"),
+              CAM_MEI: ("xi", "k1", "k2", "p1", "p2", "gamma1", "gamma2", "u0", "v0"),
+              CAM_KANNALA_BRANDT: ("k2", "k3", "k4", "k5", "mu", "mv", "u0", "v0")}
+CAM_MODEL_TYPES = {"PINHOLE": CAM_PINHOLE, "MEI": CAM_MEI, "KANNALA_BRANDT": CAM_KANNALA_BRANDT}
+_CAM_SECTIONS = ("mirror_parameters", "distortion_parameters", "projection_parameters")
+
+
+class CameraModel(C.Structure):
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 12)]
+
+    def as_tuple(self):
+        return int(self.model), tuple(self.p[:len(CAM_PARAMS.get(int(self.model), ()))])
+
+
+def camera_model(model, params=None):
+    """A CameraModel from (model id, parameters in the order of CAM_PARAMS), from a dict of load_camera_calibration, or a CameraModel itself.
+    The id is not checked here: the library rejects an unknown one."""
+    if isinstance(model, CameraModel):
+        return model
+    if isinstance(model, dict):
+        model, params = model["model"], model["params"]
+    m = CameraModel()
+    m.model = int(model)
+    v = [float(x) for x in params]
+    if len(v) > 12:
+        raise ValueError("a camera model has at most 12 parameters")
+    for i, x in enumerate(v):
+        m.p[i] = x
+    return m
+
+
+def load_camera_calibration(path):
+    """camodocal's camera YAML (CameraFactory::generateCameraFromYamlFile; the reference's configuration files carry it at their top level) ->
+    dict(model: CAM_*, model_type, params: tuple in the order of CAM_PARAMS[model], camera_name, width, height).  The part read is flat OpenCV YAML
+    (`key: value` lines and one level of `section:` with indented `key: value` lines), parsed here like load_brief_pattern, without a YAML library."""
+    top, sections, section = {}, {}, None
+    with open(path) as f:
+        for line in f:
+            s = line.split("#", 1)[0].rstrip()
+            if not s.strip() or s.startswith("%") or s.strip() == "---" or ":" not in s:
+                continue
+            key, rest = (t.strip() for t in s.split(":", 1))
+            if s[0] in " \t":
+                if section in _CAM_SECTIONS and rest:
+                    sections[section][key] = rest
+            else:
+                section = key if not rest else None
+                if section in _CAM_SECTIONS:
+                    sections[section] = {}
+                elif rest:
+                    top[key] = rest.strip('"')
+    kind = top.get("model_type", "").upper()            # (a file without model_type is a pinhole to the reference, too)
+    kind = kind or "PINHOLE"
+    if kind not in CAM_MODEL_TYPES:
+        raise ValueError(f"{path}: model_type {kind!r} is none of {sorted(CAM_MODEL_TYPES)}")
+    model = CAM_MODEL_TYPES[kind]
+    flat = {}
+    for sec in _CAM_SECTIONS:
+        flat.update(sections.get(sec, {}))
+    try:
+        params = tuple(float(flat[k]) for k in CAM_PARAMS[model])
+    except (KeyError, ValueError) as e:
+        raise ValueError(f"{path}: a {kind} camera needs {', '.join(CAM_PARAMS[model])}") from e
+    return dict(model=model, model_type=kind, params=params, camera_name=top.get("camera_name", ""),
+                width=int(top.get("image_width", 0)), height=int(top.get("image_height", 0)))
+
 # ---- place recognition of loop closure (uvs_pr_*, include/uvs_solver.h) -------------------------------------------------
 PR_MAX_K = 16
 PR_MAX_L = 16

@@ -31,6 +31,7 @@ EXPORTS = [
     "uvs_lt_gauss_tables",
     "uvs_lt_detect", "uvs_lt_detect_track", "uvs_lt_last_detect_device_ms", "uvs_lt_debug_detect",
     "uvs_lt_set_undistort", "uvs_lt_set_remap", "uvs_lt_get_remap", "uvs_lt_undistort", "uvs_lt_last_undistort_device_ms",
+    "uvs_ft_set_camera_model", "uvs_kf_set_camera_model", "uvs_ft_lift", "uvs_ft_project", "uvs_lt_set_undistort_model",
     "uvs_pr_check_vocabulary", "uvs_pr_create", "uvs_pr_destroy", "uvs_pr_last_error", "uvs_pr_size", "uvs_pr_clear", "uvs_pr_transform", "uvs_pr_add",
     "uvs_pr_query", "uvs_pr_detect", "uvs_pr_last_device_ms",
 ]
@@ -182,6 +183,13 @@ def lib():
         L.uvs_lt_get_remap.argtypes = [C.c_void_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p]; L.uvs_lt_get_remap.restype = C.c_int
         L.uvs_lt_undistort.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.LtDetItem), abi.c_u8_p]; L.uvs_lt_undistort.restype = C.c_int
         L.uvs_lt_last_undistort_device_ms.argtypes = [C.c_void_p]; L.uvs_lt_last_undistort_device_ms.restype = C.c_double
+        cam_p = C.POINTER(abi.CameraModel)
+        L.uvs_ft_set_camera_model.argtypes = [C.c_void_p, cam_p]; L.uvs_ft_set_camera_model.restype = C.c_int
+        L.uvs_kf_set_camera_model.argtypes = [C.c_void_p, cam_p]; L.uvs_kf_set_camera_model.restype = C.c_int
+        L.uvs_ft_lift.argtypes = [C.c_void_p, cam_p, C.c_int, abi.c_double_p, abi.c_double_p, abi.c_double_p]; L.uvs_ft_lift.restype = C.c_int
+        L.uvs_ft_project.argtypes = [C.c_void_p, cam_p, C.c_int, abi.c_double_p, abi.c_double_p]; L.uvs_ft_project.restype = C.c_int
+        L.uvs_lt_set_undistort_model.argtypes = [C.c_void_p, C.c_int, cam_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_double] * 4
+        L.uvs_lt_set_undistort_model.restype = C.c_int
         voc_args = [C.c_int] * 5 + [abi.c_i32_p, abi.c_i32_p, abi.c_double_p, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p]
         L.uvs_pr_check_vocabulary.argtypes = voc_args + [C.c_char_p, C.c_int]; L.uvs_pr_check_vocabulary.restype = C.c_int
         L.uvs_pr_create.argtypes = [C.c_int] + voc_args + [C.c_int, C.c_int, C.POINTER(C.c_void_p)]; L.uvs_pr_create.restype = C.c_int
@@ -199,6 +207,15 @@ def lib():
         L.uvs_pr_last_device_ms.argtypes = [C.c_void_p, C.c_int]; L.uvs_pr_last_device_ms.restype = C.c_double
         _lib = L
     return _lib
+
+
+def _camera_arg(camera):
+    """The `camera` argument of the calls that lift: a pointer to a uvs_kf_camera, or NULL for None (a handle that holds a camera model)."""
+    return None if camera is None else C.pointer(abi.kf_camera(camera))
+
+
+def _model_arg(model):
+    return None if model is None else C.pointer(abi.camera_model(model))
 
 
 class _DevPtr:
@@ -722,10 +739,10 @@ class KeyframeExtractor(_Handle):
         `null` names arguments passed as NULL ("frames", "camera", "xy", "score", "norm", "desc", "wdesc", "results")."""
         arr, keep = abi.kf_frames(frames)
         nw = [int(arr[b].n_window) for b in range(len(frames))]
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         o = self._outputs(len(frames), sum(nw))
         res = (abi.KfResult * max(len(frames), 1))()
-        args = dict(frames=C.cast(arr, C.POINTER(abi.KfFrame)), camera=C.byref(cam), xy=o["xy"].ctypes.data_as(abi.c_i32_p),
+        args = dict(frames=C.cast(arr, C.POINTER(abi.KfFrame)), camera=cam, xy=o["xy"].ctypes.data_as(abi.c_i32_p),
                     score=o["score"].ctypes.data_as(abi.c_u8_p), norm=abi._dp(o["norm"]), desc=o["desc"].ctypes.data_as(abi.c_u64_p),
                     wdesc=o["wdesc"].ctypes.data_as(abi.c_u64_p), results=C.cast(res, C.POINTER(abi.KfResult)))
         for k in null:
@@ -747,15 +764,25 @@ class KeyframeExtractor(_Handle):
             raise self._error("uvs_kf_extract", rc)
         return out
 
+    def set_camera_model_raw(self, model):
+        return lib().uvs_kf_set_camera_model(self._h, _model_arg(model))
+
+    def set_camera_model(self, model):
+        """model: an abi.CameraModel, a dict of abi.load_camera_calibration or None.  While one is set, extract() and debug_frame() lift the
+        keypoints through it and their `camera` may be None."""
+        rc = self.set_camera_model_raw(model)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_kf_set_camera_model", rc)
+
     def debug_frame(self, frame, camera):
         """ONE frame with the whole blurred image and the whole score map (tests only) -> the frame's dict of extract() plus blur, score_map."""
         arr, keep = abi.kf_frames([frame])
         H, W, nw = int(arr[0].height), int(arr[0].width), int(arr[0].n_window)
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         o = self._outputs(1, nw)
         blur = np.zeros((H, W), np.uint8); smap = np.zeros((H, W), np.uint8)
         res = abi.KfResult()
-        rc = lib().uvs_kf_debug_frame(self._h, C.cast(arr, C.POINTER(abi.KfFrame)), C.byref(cam), blur.ctypes.data_as(abi.c_u8_p),
+        rc = lib().uvs_kf_debug_frame(self._h, C.cast(arr, C.POINTER(abi.KfFrame)), cam, blur.ctypes.data_as(abi.c_u8_p),
                                       smap.ctypes.data_as(abi.c_u8_p), o["xy"].ctypes.data_as(abi.c_i32_p), o["score"].ctypes.data_as(abi.c_u8_p),
                                       abi._dp(o["norm"]), o["desc"].ctypes.data_as(abi.c_u64_p), o["wdesc"].ctypes.data_as(abi.c_u64_p), C.byref(res))
         if rc != abi.UVS_OK:
@@ -785,11 +812,11 @@ class FeatureTracker(_Handle):
         names arguments passed as NULL ("items", "camera", "next_xy", "status", "iterations", "next_norm", "results")."""
         arr, keep = abi.ft_items(items)
         npt = [int(arr[b].n_points) for b in range(len(items))]
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         N = max(sum(npt), 1)
         o = dict(next_xy=np.zeros((N, 2)), status=np.zeros(N, np.int32), iterations=np.zeros(N, np.int32), next_norm=np.zeros((N, 2)),
                  results=np.zeros(max(len(items), 1), np.int32))
-        args = dict(items=C.cast(arr, C.POINTER(abi.FtItem)), camera=C.byref(cam), next_xy=abi._dp(o["next_xy"]),
+        args = dict(items=C.cast(arr, C.POINTER(abi.FtItem)), camera=cam, next_xy=abi._dp(o["next_xy"]),
                     status=o["status"].ctypes.data_as(abi.c_i32_p), iterations=o["iterations"].ctypes.data_as(abi.c_i32_p),
                     next_norm=abi._dp(o["next_norm"]), results=o["results"].ctypes.data_as(abi.c_i32_p))
         for k in null:
@@ -823,6 +850,52 @@ class FeatureTracker(_Handle):
         if rc != abi.UVS_OK:
             raise self._error("uvs_ft_reset", rc)
 
+    # ---- camera models: the handle's model (uvs_ft_set_camera_model) and loose points through a model (uvs_ft_lift, uvs_ft_project)
+    def set_camera_model_raw(self, model):
+        return lib().uvs_ft_set_camera_model(self._h, _model_arg(model))
+
+    def set_camera_model(self, model):
+        """model: an abi.CameraModel, a dict of abi.load_camera_calibration or None.  While one is set, track(), detect() and their debug forms
+        lift through it and their `camera` may be None; reset() keeps it."""
+        rc = self.set_camera_model_raw(model)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_set_camera_model", rc)
+
+    def lift_raw(self, model, xy, n=None, null=()):
+        """-> (return code, ray [n, 3], norm [n, 2]) without raising; `null` names arguments passed as NULL ("model", "xy", "ray", "norm")."""
+        p = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        N = max(len(p), 1)
+        ray = np.zeros((N, 3)); norm = np.zeros((N, 2))
+        args = dict(model=_model_arg(model), xy=abi._dp(p), ray=abi._dp(ray), norm=abi._dp(norm))
+        for k in null:
+            args[k] = None
+        rc = lib().uvs_ft_lift(self._h, args["model"], len(p) if n is None else int(n), args["xy"], args["ray"], args["norm"])
+        return rc, ray[:len(p)], norm[:len(p)]
+
+    def lift(self, model, xy):
+        """xy [n, 2] float64 pixels -> (ray [n, 3], norm [n, 2]) through the model, on the device."""
+        rc, ray, norm = self.lift_raw(model, xy)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_lift", rc)
+        return ray, norm
+
+    def project_raw(self, model, ray, n=None, null=()):
+        """-> (return code, xy [n, 2]) without raising; `null` names arguments passed as NULL ("model", "ray", "xy")."""
+        r = np.ascontiguousarray(ray, np.float64).reshape(-1, 3)
+        xy = np.zeros((max(len(r), 1), 2))
+        args = dict(model=_model_arg(model), ray=abi._dp(r), xy=abi._dp(xy))
+        for k in null:
+            args[k] = None
+        rc = lib().uvs_ft_project(self._h, args["model"], len(r) if n is None else int(n), args["ray"], args["xy"])
+        return rc, xy[:len(r)]
+
+    def project(self, model, ray):
+        """ray [n, 3] float64 -> xy [n, 2] pixels through the model (spaceToPlane), on the device."""
+        rc, xy = self.project_raw(model, ray)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_ft_project", rc)
+        return xy
+
     def debug_pyramid(self, stream):
         """The stored pyramid of a slot (tests only) -> [level 0, level 1, ..] uint8 arrays."""
         sizes = np.zeros((abi.FT_MAX_LEVELS, 2), np.int32)
@@ -841,10 +914,10 @@ class FeatureTracker(_Handle):
         """ONE item with ONE point (tests only) -> the item's dict of track() plus trace [4, 320] float64 (include/uvs_solver.h lists its
         entries)."""
         arr, keep = abi.ft_items([item])
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         trace = np.zeros((abi.FT_MAX_LEVELS, abi.FT_TRACE_LEVEL)); xy = np.zeros((1, 2)); nm = np.zeros((1, 2))
         st = np.zeros(1, np.int32); it = np.zeros(1, np.int32)
-        rc = lib().uvs_ft_debug_point(self._h, C.cast(arr, C.POINTER(abi.FtItem)), C.byref(cam), abi._dp(trace), abi._dp(xy),
+        rc = lib().uvs_ft_debug_point(self._h, C.cast(arr, C.POINTER(abi.FtItem)), cam, abi._dp(trace), abi._dp(xy),
                                       st.ctypes.data_as(abi.c_i32_p), it.ctypes.data_as(abi.c_i32_p), abi._dp(nm))
         if rc != abi.UVS_OK:
             raise self._error("uvs_ft_debug_point", rc)
@@ -882,11 +955,11 @@ class FeatureTracker(_Handle):
         names arguments passed as NULL ("items", "camera", "new_xy", "new_score", "new_norm", "results")."""
         arr, keep = abi.ft_detect_items(items)
         max_new = [max(int(arr[b].max_new), 0) for b in range(len(items))]
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         N = max(sum(max_new), 1)
         o = dict(xy=np.zeros((N, 2), np.int32), score=np.zeros(N), norm=np.zeros((N, 2)))
         res = (abi.FtDetectResult * max(len(items), 1))()
-        args = dict(items=C.cast(arr, C.POINTER(abi.FtDetectItem)), camera=C.byref(cam), new_xy=o["xy"].ctypes.data_as(abi.c_i32_p),
+        args = dict(items=C.cast(arr, C.POINTER(abi.FtDetectItem)), camera=cam, new_xy=o["xy"].ctypes.data_as(abi.c_i32_p),
                     new_score=abi._dp(o["score"]), new_norm=abi._dp(o["norm"]), results=C.cast(res, C.POINTER(abi.FtDetectResult)))
         for k in null:
             args[k] = None
@@ -916,14 +989,14 @@ class FeatureTracker(_Handle):
         """ONE item (tests only); shape = (H, W) of the slot's image -> the item's dict of detect() plus score_map [H, W] float64, allowed [H, W]
         uint8, cand_index and cand_score: the ranked candidates (min(n_candidates, max_candidates) of them)."""
         arr, keep = abi.ft_detect_items([item])
-        cam = abi.kf_camera(camera)
+        cam = _camera_arg(camera)
         H, W = int(shape[0]), int(shape[1])
         M = max(int(arr[0].max_new), 1)
         o = dict(xy=np.zeros((M, 2), np.int32), score=np.zeros(M), norm=np.zeros((M, 2)))
         smap = np.zeros((H, W)); allowed = np.zeros((H, W), np.uint8)
         ci = np.zeros(self.max_candidates, np.int32); cs = np.zeros(self.max_candidates)
         res = abi.FtDetectResult()
-        rc = lib().uvs_ft_debug_detect(self._h, C.cast(arr, C.POINTER(abi.FtDetectItem)), float(quality_level), int(min_distance), C.byref(cam),
+        rc = lib().uvs_ft_debug_detect(self._h, C.cast(arr, C.POINTER(abi.FtDetectItem)), float(quality_level), int(min_distance), cam,
                                        abi._dp(smap), allowed.ctypes.data_as(abi.c_u8_p), ci.ctypes.data_as(abi.c_i32_p), abi._dp(cs),
                                        o["xy"].ctypes.data_as(abi.c_i32_p), abi._dp(o["score"]), abi._dp(o["norm"]), C.byref(res))
         if rc != abi.UVS_OK:
@@ -1236,6 +1309,19 @@ class LineTracker(_Handle):
         rc = self.set_undistort_raw(stream, camera, width, height, col_margin, row_margin)
         if rc != abi.UVS_OK:
             raise self._error("uvs_lt_set_undistort", rc)
+
+    def set_undistort_model_raw(self, stream, model, width, height, out_camera, col_margin=0, row_margin=0):
+        fx, fy, cx, cy = (float(v) for v in out_camera)
+        return lib().uvs_lt_set_undistort_model(self._h, int(stream), _model_arg(model), int(width), int(height), int(col_margin), int(row_margin),
+                                                fx, fy, cx, cy)
+
+    def set_undistort_model(self, stream, model, width, height, out_camera, col_margin=0, row_margin=0):
+        """The slot's map for any camera model (abi.CameraModel or a dict of abi.load_camera_calibration) of the raw image width x height:
+        output pixel (u, v) of the pinhole out_camera = (fx, fy, cx, cy) reads the raw image where the model projects its ray.  model = None
+        switches the slot's map off."""
+        rc = self.set_undistort_model_raw(stream, model, width, height, out_camera, col_margin, row_margin)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_lt_set_undistort_model", rc)
 
     def set_remap_raw(self, stream, src_width, src_height, map_xy, out_width=None, out_height=None, null=False):
         m = np.ascontiguousarray(map_xy, np.int32)

@@ -1,7 +1,8 @@
 // uvs_ft_handle.h -- the handle behind the uvs_ft_* calls, shared by the four units of the point front end: csrc/uvs_feature_track.hip (creates
 // and destroys it, builds the pyramids, tracks), csrc/uvs_feature_detect.hip (detects new points in level 0 of a slot's stored pyramid),
 // csrc/uvs_feature_reject.hip (rejects outlier tracks by a fundamental-matrix RANSAC; it reads no slot) and csrc/uvs_feature_equalize.hip (CLAHE:
-// of an equalized slot's raw image into level 0 of its new pyramid, on the tracking unit's behalf, and of loose images).  Device, stream, events
+// of an equalized slot's raw image into level 0 of its new pyramid, on the tracking unit's behalf, and of loose images); csrc/uvs_camera_models.hip
+// keeps the handle's camera model and lifts and projects loose points on its stream.  Device, stream, events
 // and error text are the base's (uvs_handle.h, which also has align_up, pitch_of, the arena and the camera check the units use).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_camera_models.h"
 #include "uvs_handle.h"
 
 struct uvs_ft_tracker : UvsHandle {
@@ -45,6 +47,13 @@ struct uvs_ft_tracker : UvsHandle {
     DevBuf<char> d_eq_out;                      // uvs_ft_equalize: the equalized images (pitch_of rows), then the debug call's bins
     PinnedBuf<char> h_eq_out;
     float equalize_ms = 0.f;                    // uvs_ft_last_equalize_device_ms
+    // camera model (uvs_camera_models.hip): uvs_ft_set_camera_model's, which uvs_ft_track and uvs_ft_detect lift through while it is set
+    // (model.model < 0: none; uvs_ft_reset keeps it), and the buffers of uvs_ft_lift / uvs_ft_project, allocated by the first call
+    UvsCamDev model = uvs_cam_none();
+    DevBuf<UvsCamDev> d_model;                  // its copy on the device, which k_ft_track and k_ft_detect_select read
+    UvsCamDev model_on_device = uvs_cam_none(); // what d_model holds: the same model set again is not uploaded again
+    DevBuf<char> d_cm;                          // one call's points: (xy | ray | norm)
+    PinnedBuf<char> h_cm;
 };
 
 namespace uvsft {

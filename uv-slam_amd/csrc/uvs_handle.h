@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <string>
 
 #include "../../include/uvs_solver.h"
@@ -53,3 +54,15 @@ struct UvsHandle {
         if (st) (void)hipStreamSynchronize(st);
     }
 };
+
+// a handle's copy of a small struct on the device (a camera model, which the kernels read through a pointer only where one is set): allocated by
+// the first call, written on the handle's stream, which is idle between the calls
+template <class T>
+inline int uvs_cam_upload(UvsHandle* h, DevBuf<T>& dst, const T& value, const T& held) {
+    if (dst.get() && std::memcmp(&value, &held, sizeof(T)) == 0) return UVS_OK;      // the copy on the device is this one already
+    UVS_HIP(h->err, hipSetDevice(h->device));
+    if (const int rc = dst.ensure(sizeof(T), h->err)) return rc;
+    UVS_HIP(h->err, hipMemcpyAsync(dst.get(), &value, sizeof(T), hipMemcpyHostToDevice, h->st));
+    UVS_HIP(h->err, hipStreamSynchronize(h->st));
+    return UVS_OK;
+}

@@ -27,17 +27,9 @@
 namespace uvslt {
 
 constexpr int kUdThreads = 256;
-constexpr int kUdLimit = 1 << 24;              // |X|, |Y| of a map word
-
 struct UdMapArgs { double fx, fy, cx, cy, k1, k2, p1, p2; int Wo, Ho, cm, rm; };
 
-// ---- the map: the header's chain, one rounding per operation
-__device__ __forceinline__ int32_t ud_fix(double m) {
-    const double v = rint(32.0 * m);
-    if (!isfinite(v)) return -kUdLimit;
-    return (int32_t)fmin(fmax(v, (double)-kUdLimit), (double)kUdLimit);
-}
-
+// ---- the map: the header's chain, one rounding per operation (ud_fix: uvs_lt_handle.h)
 __global__ void __launch_bounds__(kUdThreads) k_lt_ud_map(UdMapArgs A, int32_t* __restrict__ map) {
     const int t = blockIdx.x * kUdThreads + threadIdx.x;
     if (t >= A.Wo * A.Ho) return;
@@ -90,18 +82,6 @@ int ud_launch(uvs_lt_tracker* h, int n, const UdItem* items, const uint8_t* src,
 
 namespace {
 
-// the checks the two set calls share; a slot's map memory is allocated here, when everything else has passed
-int ud_check_sizes(uvs_lt_tracker* h, const std::string& fn, int stream, int W, int H, int Wo, int Ho) {
-    if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
-    if (W < UVS_LT_MIN_SIZE || H < UVS_LT_MIN_SIZE || Wo < UVS_LT_MIN_SIZE || Ho < UVS_LT_MIN_SIZE) {
-        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
-    }
-    if (W > h->max_width || H > h->max_height || Wo > h->max_width || Ho > h->max_height) {
-        h->err = fn + " exceeds the capacity given to uvs_lt_create"; return UVS_ERR_CAPACITY;
-    }
-    return UVS_OK;
-}
-
 struct UdLayout { size_t o_img, in_used, o_out, used; };
 
 // uvs_lt_undistort's one buffer: items | raw images (uploaded up to in_used) | outputs (downloaded from o_out)
@@ -133,24 +113,13 @@ int uvs_lt_set_undistort(uvs_lt_tracker* h, int stream, const uvs_kf_camera* cam
     if (!camera) { h->ud[stream].on = false; return UVS_OK; }
     int rc = check_camera(camera, fn, h->err);
     if (rc != UVS_OK) return rc;
-    if (col_margin < 0 || row_margin < 0) { h->err = fn + ": negative margin"; return UVS_ERR_INVALID_ARG; }
-    if (width < UVS_LT_MIN_SIZE || height < UVS_LT_MIN_SIZE || col_margin > width / 2 || row_margin > height / 2) {      // before W - 2 cm is formed
-        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
-    }
-    const int Wo = width - 2 * col_margin, Ho = height - 2 * row_margin;
-    if ((rc = ud_check_sizes(h, fn, stream, width, height, Wo, Ho)) != UVS_OK) return rc;
-    LtUndistort& U = h->ud[stream];
     UdMapArgs A;
     A.fx = camera->fx; A.fy = camera->fy; A.cx = camera->cx; A.cy = camera->cy; A.k1 = camera->k1; A.k2 = camera->k2; A.p1 = camera->p1; A.p2 = camera->p2;
-    A.Wo = Wo; A.Ho = Ho; A.cm = col_margin; A.rm = row_margin;
-    UVS_HIP(h->err, hipSetDevice(h->device));
-    U.on = false;                               // every argument has passed: a HIP failure below leaves the slot without a map, not with half of one
-    if ((rc = U.map.ensure(8 * (size_t)Wo * Ho, h->err)) != UVS_OK) return rc;
-    k_lt_ud_map<<<(Wo * Ho + kUdThreads - 1) / kUdThreads, kUdThreads, 0, h->st>>>(A, U.map);
-    UVS_HIP(h->err, hipGetLastError());
-    UVS_HIP(h->err, hipStreamSynchronize(h->st));
-    U.W = width; U.H = height; U.Wo = Wo; U.Ho = Ho; U.on = true;
-    return UVS_OK;
+    A.cm = col_margin; A.rm = row_margin;
+    return ud_build_map(h, fn, stream, width, height, col_margin, row_margin, [&](int Wo, int Ho, int32_t* map) {
+        A.Wo = Wo; A.Ho = Ho;
+        k_lt_ud_map<<<(Wo * Ho + kUdThreads - 1) / kUdThreads, kUdThreads, 0, h->st>>>(A, map);
+    });
 }
 
 int uvs_lt_set_remap(uvs_lt_tracker* h, int stream, int src_width, int src_height, int out_width, int out_height, const int32_t* map_xy) {

@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
-#include "../csrc/uvs_camera_lift.h"
+#include "../csrc/uvs_camera_models.h"
 
 namespace uvs {
 
@@ -38,6 +38,13 @@ inline void reduceVector(std::vector<T>& v, const std::vector<uint8_t>& status) 
 class FeatureTrackerBook {
 public:
     explicit FeatureTrackerBook(const uvs_kf_camera& camera) : camera_(camera), lift_(uvs_lift_camera(camera)) {}
+    // any camera model (MEI, Kannala-Brandt, or the pinhole given as one): the points are lifted through uvs_cam_lift, the device function of
+    // uvs_ft_lift.  Throws std::invalid_argument for a model the library would reject.
+    explicit FeatureTrackerBook(const uvs_camera_model& model) : camera_{}, lift_{}, has_model_(true), model_(model) {
+        std::string err;
+        if (uvs_cam_check(&model, "FeatureTrackerBook", err) != UVS_OK) throw std::invalid_argument(err);
+        model_dev_ = uvs_cam_pack(model);
+    }
 
     // :81-107 after the flow: forw_pts = next_xy, status[i] = (ft_status[i] == UVS_FT_TRACKED) (the device has applied inBorder), the six
     // reduceVector calls, track_cnt++.  next_norm: liftProjective of next_xy from the device.
@@ -113,12 +120,13 @@ public:
     }
 
     // :240-288.  The normalized coordinates of the tracked points are the device's; a point added in this frame is lifted here by the same
-    // function (uvs_camera_lift.h).  std::map::insert keeps the first entry of a key, as the reference's does for the ids still -1.
+    // function (uvs_camera_lift.h; with a camera model, uvs_camera_models.h).  std::map::insert keeps the first entry of a key, as the reference's does for the ids still -1.
     void undistortedPoints() {
         cur_un_pts.clear(); cur_un_pts_map.clear();
         for (size_t i = 0; i < cur_pts.size(); ++i) {
             Point2d b;
             if (i < forw_norm_.size()) b = forw_norm_[i];
+            else if (has_model_) { double ray[3]; uvs_cam_lift(model_dev_, cur_pts[i].x, cur_pts[i].y, ray, b.x, b.y); }
             else uvs_lift_projective(lift_, cur_pts[i].x, cur_pts[i].y, b.x, b.y);
             cur_un_pts.push_back(b);
             cur_un_pts_map.insert(std::make_pair(ids[i], b));
@@ -161,6 +169,10 @@ public:
 protected:
     uvs_kf_camera camera_;
     UvsLiftCam lift_;
+    bool has_model_ = false;          // constructed from a uvs_camera_model: camera_ and lift_ are not used
+    uvs_camera_model model_ = {};
+    UvsCamDev model_dev_ = uvs_cam_none();
+    const uvs_kf_camera* cameraArg() const { return has_model_ ? nullptr : &camera_; }      // the `camera` of uvs_ft_track / uvs_ft_detect
     std::vector<Point2d> forw_norm_;
 
 private:
@@ -179,6 +191,18 @@ public:
         : FeatureTrackerBook(camera), max_points_(max_points) {
         const int rc = uvs_ft_create(device, 1, max_width, max_height, levels, max_points, &ft_);
         if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_ft_create: ") + uvs_status_string(rc));
+    }
+    // the same with a camera model on the device handle (uvs_ft_set_camera_model): undistortedPoints, pts_velocity, rejectWithF and the
+    // tracker's own detection then run on model-lifted points
+    FeatureTracker(const uvs_camera_model& model, int device = 0, int max_width = 752, int max_height = 480, int levels = 4, int max_points = 1024)
+        : FeatureTrackerBook(model), max_points_(max_points) {
+        int rc = uvs_ft_create(device, 1, max_width, max_height, levels, max_points, &ft_);
+        if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_ft_create: ") + uvs_status_string(rc));
+        if ((rc = uvs_ft_set_camera_model(ft_, &model_)) != UVS_OK) {
+            const std::string text = uvs_ft_last_error(ft_);
+            uvs_ft_destroy(ft_);
+            throw std::runtime_error("uvs_ft_set_camera_model: " + text);
+        }
     }
     ~FeatureTracker() { uvs_ft_destroy(ft_); }
     FeatureTracker(const FeatureTracker&) = delete;
@@ -206,7 +230,7 @@ public:
         uvs_ft_item item;
         item.image = image; item.stream = 0; item.width = width; item.height = height; item.n_points = (int32_t)n; item.points_xy = n ? xy_.data() : nullptr;
         int32_t n_tracked = 0;
-        const int rc = uvs_ft_track(ft_, 1, &item, &camera_, nxt_.data(), st_.data(), it_.data(), nrm_.data(), &n_tracked);
+        const int rc = uvs_ft_track(ft_, 1, &item, cameraArg(), nxt_.data(), st_.data(), it_.data(), nrm_.data(), &n_tracked);
         if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
         std::vector<Point2d> next(n), norm(n);
         for (size_t i = 0; i < n; ++i) { next[i].x = nxt_[2 * i]; next[i].y = nxt_[2 * i + 1]; norm[i].x = nrm_[2 * i]; norm[i].y = nrm_[2 * i + 1]; }
@@ -287,7 +311,7 @@ private:
         item.stream = 0; item.n_occupied = (int32_t)n; item.max_new = n_max_cnt; item.reserved = 0; item.occupied_xy = n ? xy_.data() : nullptr;
         new_xy_.resize(2 * (size_t)n_max_cnt); new_score_.resize(n_max_cnt); new_norm_.resize(2 * (size_t)n_max_cnt);
         uvs_ft_detect_result res;
-        const int rc = uvs_ft_detect(ft_, 1, &item, quality_level, min_dist, &camera_, new_xy_.data(), new_score_.data(), new_norm_.data(), &res);
+        const int rc = uvs_ft_detect(ft_, 1, &item, quality_level, min_dist, cameraArg(), new_xy_.data(), new_score_.data(), new_norm_.data(), &res);
         if (rc != UVS_OK) { last_error = uvs_ft_last_error(ft_); return rc; }
         const bool with_norm = forw_norm_.size() == n;
         for (int i = 0; i < res.n_new; ++i) {

@@ -1,7 +1,7 @@
 // feature_tracker_capi.cpp -- test hooks for uvs::FeatureTracker (feature_tracker.h): a tracker behind a handle, fed with images (the device
 // path) or with a frame's flow results by hand (the bookkeeping alone, no device), and its vectors read back.  Apart from host_capi.cpp for the
 // reason vanishing_points_capi.cpp gives: the CPU oracle has no uvs_ft_*.
-//   camera[8] = fx, fy, cx, cy, k1, k2, p1, p2; new_xy[n_new][2]: the points the caller's detector adds in this frame.
+//   camera[8] = fx, fy, cx, cy, k1, k2, p1, p2 (uvs_host_ft_create_model: any camera model instead); new_xy[n_new][2]: the points the caller's detector adds in this frame.
 // uvs_host_ft_set_detection turns the tracker's own detection on (max_cnt > 0): uvs_host_ft_read_image_detect then runs a frame without a
 // Detector, and uvs_host_ft_apply_set_mask a frame of the bookkeeping with setMask between the flow and addPoints.
 // uvs_host_ft_set_rejection turns rejectWithF on (f_threshold > 0) for the frames that follow, and uvs_host_ft_apply_reject is a frame of the
@@ -36,6 +36,23 @@ void* uvs_host_ft_create(int device, const double* camera, int max_width, int ma
         else h->dev.reset(new uvs::FeatureTracker(cam, device, max_width, max_height, levels, max_points));
         return h;
     } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return nullptr;
+    }
+}
+
+// the same from a camera model: model_id = UVS_CAM_*, params[n_params] in the order of uvs_camera_model.p
+void* uvs_host_ft_create_model(int device, int model_id, int n_params, const double* params, int max_width, int max_height, int levels, int max_points) {
+    if (!params || n_params < 0 || n_params > 12) return nullptr;
+    uvs_camera_model model = {};
+    model.model = model_id;
+    for (int i = 0; i < n_params; ++i) model.p[i] = params[i];
+    try {
+        HostFt* h = new HostFt();
+        if (device < 0) h->book.reset(new uvs::FeatureTrackerBook(model));
+        else h->dev.reset(new uvs::FeatureTracker(model, device, max_width, max_height, levels, max_points));
+        return h;
+    } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return nullptr;
     }

@@ -152,6 +152,16 @@ public:
         if (rc != UVS_OK) last_error = uvs_lt_last_error(lt_);
         return rc;
     }
+    // The same for a raw frame of any camera model (a fisheye: MEI, Kannala-Brandt): the device builds the map that takes the output pinhole
+    // (fx_out, fy_out, cx_out, cy_out) of the uncropped undistorted image to the model's raw pixels (uvs_lt_set_undistort_model), cropped by the
+    // constructor's margins.  The tracker itself should have been constructed with that output pinhole: it is the camera of the image the
+    // lines are found in.  Nothing is rounded through float here: the reference has no such path to follow.
+    int setUndistortion(const uvs_camera_model& model, double fx_out, double fy_out, double cx_out, double cy_out, int width = 0, int height = 0) {
+        const int rc = uvs_lt_set_undistort_model(lt_, 0, &model, width > 0 ? width : max_width_, height > 0 ? height : max_height_, col_margin_,
+                                                  row_margin_, fx_out, fy_out, cx_out, cy_out);
+        if (rc != UVS_OK) last_error = uvs_lt_last_error(lt_);
+        return rc;
+    }
 
     // One frame: img[height][width] (undistorted, 8 bit), segments[n][4] = sx, sy, ex, ey of the caller's detector.  Returns UVS_OK or the
     // error of uvs_lt_track (its text in last_error; the frame changes nothing) or of uvs_vp_estimate (the lines are tracked, `vps` stays empty).

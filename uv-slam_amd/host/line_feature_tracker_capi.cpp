@@ -108,6 +108,16 @@ int uvs_host_lt_set_undistortion(void* p, double k1, double k2, double p1, doubl
     return h->tracker->setUndistortion(k1, k2, p1, p2);
 }
 
+// setUndistortion(model, output pinhole) of a tracker: model_id = UVS_CAM_*, params[n_params] in the order of uvs_camera_model.p, out[4] = fx, fy, cx, cy
+int uvs_host_lt_set_undistortion_model(void* p, int model_id, int n_params, const double* params, const double* out) {
+    LtHook* h = static_cast<LtHook*>(p);
+    if (!h || !h->tracker || !params || !out || n_params < 0 || n_params > 12) return UVS_ERR_INVALID_ARG;
+    uvs_camera_model model = {};
+    model.model = model_id;
+    for (int i = 0; i < n_params; ++i) model.p[i] = params[i];
+    return h->tracker->setUndistortion(model, out[0], out[1], out[2], out[3]);
+}
+
 // readImage4Line(img, width, height, time): the segments are detected (a tracker) or injected (a stub)
 int uvs_host_lt_read_image_detect(void* p, const uint8_t* img, int width, int height, double time) {
     LtHook* h = static_cast<LtHook*>(p);

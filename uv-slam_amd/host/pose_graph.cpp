@@ -19,6 +19,23 @@ KeyFrame::KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const
     : KeyFrame(stamp, sequence_, vio_T, vio_R) {             // keyframe.cpp:14-41
     index = index_;
     point_3d = point_3d_; point_2d_uv = point_2d_uv_; point_2d_norm = point_2d_norm_; point_id = point_id_;
+    (void)uvs_kf_set_camera_model(extractor, nullptr);      // a model an earlier keyframe left on the extractor would lift this one's keypoints
+    extractOnline(image, width, height, extractor, &camera);
+}
+
+KeyFrame::KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R, const uint8_t* image, int width, int height,
+                   const std::vector<Eigen::Vector3d>& point_3d_, const std::vector<std::array<float, 2>>& point_2d_uv_,
+                   const std::vector<std::array<double, 2>>& point_2d_norm_, const std::vector<double>& point_id_, int sequence_,
+                   uvs_kf_extractor* extractor, const uvs_camera_model& model)
+    : KeyFrame(stamp, sequence_, vio_T, vio_R) {
+    index = index_;
+    point_3d = point_3d_; point_2d_uv = point_2d_uv_; point_2d_norm = point_2d_norm_; point_id = point_id_;
+    const int rc = uvs_kf_set_camera_model(extractor, &model);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_kf_set_camera_model: ") + uvs_status_string(rc) + " / " + uvs_kf_last_error(extractor));
+    extractOnline(image, width, height, extractor, nullptr);
+}
+
+void KeyFrame::extractOnline(const uint8_t* image, int width, int height, uvs_kf_extractor* extractor, const uvs_kf_camera* camera) {
     uvs_kf_frame fr;
     fr.image = image; fr.width = width; fr.height = height; fr.n_window = (int)point_2d_uv.size(); fr.reserved = 0;
     fr.window_uv = point_2d_uv.empty() ? nullptr : point_2d_uv[0].data();
@@ -28,7 +45,7 @@ KeyFrame::KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const
     std::vector<std::array<double, 2>> norm(UVS_LC_MAX_OLD);
     std::vector<std::array<uint64_t, 4>> desc(UVS_LC_MAX_OLD);
     window_brief_descriptors.resize(std::max<size_t>(point_2d_uv.size(), 1));
-    const int rc = uvs_kf_extract(extractor, 1, &fr, &camera, xy[0].data(), score.data(), norm[0].data(), desc[0].data(),
+    const int rc = uvs_kf_extract(extractor, 1, &fr, camera, xy[0].data(), score.data(), norm[0].data(), desc[0].data(),
                                   window_brief_descriptors[0].data(), &last_extract);
     if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_kf_extract: ") + uvs_status_string(rc) + " / " + uvs_kf_last_error(extractor));
     window_brief_descriptors.resize(point_2d_uv.size());

@@ -55,7 +55,15 @@ struct KeyFrame {
              const std::vector<Eigen::Vector3d>& point_3d_, const std::vector<std::array<float, 2>>& point_2d_uv_,
              const std::vector<std::array<double, 2>>& point_2d_norm_, const std::vector<double>& point_id_, int sequence_,
              uvs_kf_extractor* extractor, const uvs_kf_camera& camera);
+    // the same for any camera model (a fisheye: MEI, Kannala-Brandt): the model is put on the extractor (uvs_kf_set_camera_model; a model the
+    // extractor already holds is not uploaded again) and keypoints_norm are lifted through it.  The constructor above takes it off again
+    KeyFrame(double stamp, int index_, const Eigen::Vector3d& vio_T, const Eigen::Matrix3d& vio_R, const uint8_t* image, int width, int height,
+             const std::vector<Eigen::Vector3d>& point_3d_, const std::vector<std::array<float, 2>>& point_2d_uv_,
+             const std::vector<std::array<double, 2>>& point_2d_norm_, const std::vector<double>& point_id_, int sequence_,
+             uvs_kf_extractor* extractor, const uvs_camera_model& model);
     void getVioPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = vio_T_w_i; R = vio_R_w_i; }
+    // the body of the two online constructors; camera == nullptr: the extractor holds a camera model
+    void extractOnline(const uint8_t* image, int width, int height, uvs_kf_extractor* extractor, const uvs_kf_camera* camera);
     void getPose(Eigen::Vector3d& P, Eigen::Matrix3d& R) const { P = T_w_i; R = R_w_i; }
     void updatePose(const Eigen::Vector3d& P, const Eigen::Matrix3d& R) { T_w_i = P; R_w_i = R; }
     void updateVioPose(const Eigen::Vector3d& P, const Eigen::Matrix3d& R) { vio_T_w_i = P; vio_R_w_i = R; T_w_i = P; R_w_i = R; }

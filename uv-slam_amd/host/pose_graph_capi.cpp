@@ -6,6 +6,7 @@
 // uvs_host_pose_graph_image_run: the same again from IMAGES: every keyframe extracts its own descriptors and keypoints on the GPU.
 // uvs_host_pose_graph_detect_run (last): the verify run WITHOUT candidates: place recognition finds them on the GPU (addKeyFrameDetectLoop).
 #include <cstdio>
+#include <memory>
 #include <stdexcept>
 #include "pose_graph.h"
 
@@ -161,6 +162,42 @@ extern "C" int uvs_host_pose_graph_image_run(int device, int n, const double* st
     } catch (const std::runtime_error& e) {
         std::fprintf(stderr, "%s\n", e.what());
         rc = UVS_ERR_NO_DEVICE;
+    }
+    uvs_kf_destroy(kf);
+    return rc;
+}
+
+// Test hook: the two online KeyFrame constructors on ONE extractor.  Keyframe k of n is built from images[k] (width x height) without window
+// points, through the camera model (model_id = UVS_CAM_*, params[n_params] in the order of uvs_camera_model.p) where use_model[k] != 0 and
+// through `camera` otherwise.  out_n_kp[n]; out_kp_xy[n][max_keypoints][2], out_kp_norm[n][max_keypoints][2] = its keypoints / keypoints_norm.
+extern "C" int uvs_host_keyframe_online(int device, const uvs_kf_camera* camera, int model_id, int n_params, const double* params, const int32_t* pattern,
+                                        int max_keypoints, int width, int height, int n, const uint8_t* images, const int* use_model, int* out_n_kp,
+                                        int32_t* out_kp_xy, double* out_kp_norm) {
+    if (n < 1 || !camera || !params || n_params < 0 || n_params > 12 || !pattern || !images || !use_model || !out_n_kp || !out_kp_xy || !out_kp_norm)
+        return UVS_ERR_INVALID_ARG;
+    uvs_camera_model model = {};
+    model.model = model_id;
+    for (int i = 0; i < n_params; ++i) model.p[i] = params[i];
+    uvs_kf_extractor* kf = nullptr;
+    int rc = uvs_kf_create(device, 1, width, height, max_keypoints, UVS_LC_MAX_QUERY, pattern, pattern + UVS_KF_PATTERN_BITS,
+                           pattern + 2 * UVS_KF_PATTERN_BITS, pattern + 3 * UVS_KF_PATTERN_BITS, &kf);
+    if (rc != UVS_OK) return rc;
+    try {
+        for (int k = 0; k < n; ++k) {
+            const uint8_t* img = images + (size_t)k * width * height;
+            const Eigen::Vector3d T(0.0, 0.0, 0.0);
+            const Eigen::Matrix3d R = Eigen::Matrix3d::Identity();
+            std::unique_ptr<KeyFrame> f(use_model[k] ? new KeyFrame((double)k, k, T, R, img, width, height, {}, {}, {}, {}, 0, kf, model)
+                                                     : new KeyFrame((double)k, k, T, R, img, width, height, {}, {}, {}, {}, 0, kf, *camera));
+            out_n_kp[k] = (int)f->keypoints_norm.size();
+            for (size_t i = 0; i < f->keypoints_norm.size(); ++i) {
+                const size_t o = (size_t)k * max_keypoints + i;
+                for (int c = 0; c < 2; ++c) { out_kp_xy[2 * o + c] = f->keypoints[i][c]; out_kp_norm[2 * o + c] = f->keypoints_norm[i][c]; }
+            }
+        }
+    } catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        rc = UVS_ERR_INVALID_ARG;
     }
     uvs_kf_destroy(kf);
     return rc;
