@@ -392,6 +392,19 @@ def test_gpu_lift_project_kannala_brandt(ft, name):
         assert np.array_equal(bits(ft.project(m, want_ray[i:i + 1])[0]), bits(xy[i])), (name, i)
 
 
+def _track_and_detect(t, camera):
+    """The scene shift_48x40_L1 tracked and the case scene_48x40 detected on slot 0 of the tracker t (48 x 40, one level)."""
+    sc = ft_cases.scene("shift_48x40_L1")
+    t.reset(0)
+    t.track([dict(stream=0, image=sc["prev"])], camera)
+    tr = t.track([dict(stream=0, image=sc["next"], points=sc["pts"])], camera)[0]
+    c = fd_cases.case("scene_48x40")
+    t.reset(0)
+    t.track([dict(stream=0, image=c["image"])], camera)
+    de = t.detect([dict(stream=0, occupied=c["occupied"], max_new=c["max_new"])], camera, quality_level=0.01, min_distance=c["R"])[0]
+    return tr, de
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ("tum", "black_box"))
 def test_gpu_lift_inside_track_detect_and_extract(name):
@@ -403,14 +416,7 @@ def test_gpu_lift_inside_track_detect_and_extract(name):
     t = uvs.api.FeatureTracker(device=0, max_streams=1, max_width=48, max_height=40, levels=1, max_points=len(sc["pts"]))
 
     def run(camera):
-        t.reset(0)
-        t.track([dict(stream=0, image=sc["prev"])], camera)
-        tr = t.track([dict(stream=0, image=sc["next"], points=sc["pts"])], camera)[0]
-        c = fd_cases.case("scene_48x40")
-        t.reset(0)
-        t.track([dict(stream=0, image=c["image"])], camera)
-        de = t.detect([dict(stream=0, occupied=c["occupied"], max_new=c["max_new"])], camera, quality_level=0.01, min_distance=c["R"])[0]
-        return tr, de
+        return _track_and_detect(t, camera)
 
     before = run(ft_cases.CAM)
     t.set_camera_model(m)
@@ -456,6 +462,30 @@ def test_gpu_lift_inside_track_detect_and_extract(name):
         assert np.array_equal(before[k], after[k]), k
     assert np.array_equal(bits(after["norm"]), bits(ref["norm"]))
     assert kf.extract_raw([dict(image=img, window_uv=uv)], None)[0] == INV
+    kf.close(); t.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cam", (kf_cases.CAM_DIST, kf_cases.CAM), ids=("distorted", "plain"))
+def test_gpu_pinhole_model_on_the_handle_equals_the_camera_of_the_call(cam):
+    """A PINHOLE model set on the handle (camera = None) gives track, detect and extract every array the same camera gives as the call's
+    uvs_kf_camera, bit for bit, with distortion (flag = 1: the eight passes) and without (flag = 0): one kernel argument, one device function."""
+    def same(a, b):
+        a, b = np.asarray(a), np.asarray(b)
+        return np.array_equal(bits(a), bits(b)) if a.dtype == np.float64 else np.array_equal(a, b)
+
+    m = abi.camera_model(abi.CAM_PINHOLE, cam)
+    t = uvs.api.FeatureTracker(device=0, max_streams=1, max_width=48, max_height=40, levels=1, max_points=len(ft_cases.scene("shift_48x40_L1")["pts"]))
+    img = kf_cases.texture(40, 96, 72, 20); uv = kf_cases.window_points(40, 8, 96, 72)
+    kf = uvs.api.KeyframeExtractor(kf_cases.pattern(), device=0, max_frames=1, max_width=96, max_height=72, max_keypoints=256, max_window=16)
+    per_call = _track_and_detect(t, cam) + (kf.extract([dict(image=img, window_uv=uv)], cam)[0],)
+    t.set_camera_model(m); kf.set_camera_model(m)
+    held = _track_and_detect(t, None) + (kf.extract([dict(image=img, window_uv=uv)], None)[0],)
+    assert per_call[0]["n_tracked"] > 5 and per_call[1]["n_new"] > 3 and per_call[2]["n_keypoints"] > 5
+    for a, b in zip(per_call, held):
+        assert a.keys() == b.keys()
+        for k in a:
+            assert same(a[k], b[k]), k
     kf.close(); t.close()
 
 

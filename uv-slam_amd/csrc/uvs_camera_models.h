@@ -1,21 +1,26 @@
 // uvs_camera_models.h -- the three camera models of the front ends in FP64, one statement for the device and the host: the radial-tangential
-// pinhole (uvs_camera_lift.h, unchanged), MEI (reference camera_models/CataCamera.cc:556-659 liftProjective / spaceToPlane, :766-782 distortion)
-// and Kannala-Brandt (EquidistantCamera.cc:428-461, backprojectSymmetric :716-818).  lift: pixel -> ray and normalized point; project: ray ->
-// pixel; the check and the packing of a uvs_camera_model (with the Kannala-Brandt th_max search) on the host.  include/uvs_solver.h states the
-// operation order; IEEE multiplies, adds, divides and square roots in that order: the units that include this are compiled with
-// -ffp-contract=off, and tests/cm_ref.py restates it.  Shared by csrc/uvs_camera_models.hip (uvs_ft_lift, uvs_ft_project, the map of
-// uvs_lt_set_undistort_model), the three units that lift in a kernel (uvs_feature_track, uvs_feature_detect, uvs_keyframe_features) and the
-// host mirror.
+// pinhole (reference camera_models/PinholeCamera.cc:450-510 liftProjective, 678-694 distortion), MEI (CataCamera.cc:556-659 liftProjective /
+// spaceToPlane, :766-782 distortion) and Kannala-Brandt (EquidistantCamera.cc:428-461, backprojectSymmetric :716-818).  lift: pixel -> ray and
+// normalized point; project: ray -> pixel; the check and the packing of a uvs_camera_model (with the Kannala-Brandt th_max search) and of a
+// uvs_kf_camera on the host.  include/uvs_solver.h states the operation order; IEEE multiplies, adds, divides and square roots in that order:
+// the units that include this are compiled with -ffp-contract=off, and tests/cm_ref.py and tests/kf_ref.py (lift) restate it.  Shared by
+// csrc/uvs_camera_models.hip (uvs_ft_lift, uvs_ft_project), csrc/uvs_line_undistort.hip (the map), the three units that lift in a kernel
+// (uvs_feature_track, uvs_feature_detect, uvs_keyframe_features) and the host mirror.
 #pragma once
 #include <cmath>
 #include <string>
 
 #include "../../include/uvs_solver.h"
-#include "uvs_camera_lift.h"
 
-// A uvs_camera_model as the kernels take it, 120 bytes: a kernel argument of the k_cm_* kernels; the kernels that lift in place beside a
-// UvsLiftCam take a pointer to the handle's device copy instead (null: no model), so that they read it, by scalar loads, only on the branch
-// that uses it.  model < 0 on the host: the handle holds no model.
+#if defined(__HIPCC__)
+#define UVS_LIFT_HD __host__ __device__ __forceinline__
+#else
+#define UVS_LIFT_HD inline
+#endif
+
+// The camera as every kernel takes it, 120 bytes, by value as a kernel argument: wave-uniform, so the branch on the model id is a scalar
+// branch.  It is the handle's model where one is set, else the call's uvs_kf_camera packed as a PINHOLE.  model < 0 on the host: the handle
+// holds no model.
 //   PINHOLE          (sx, sy, u0, v0) = (fx, fy, cx, cy), c = k1 k2 p1 p2 -,      flag: some coefficient is not 0
 //   MEI              (sx, sy, u0, v0) = (gamma1, gamma2, u0, v0), c = k1 k2 p1 p2 xi, flag: some coefficient is not 0 (!m_noDistortion)
 //   KANNALA_BRANDT   (sx, sy, u0, v0) = (mu, mv, u0, v0), c = k2 k3 k4 k5 th_max, flag: some k is not 0; r_max = r(th_max)
@@ -64,12 +69,19 @@ UVS_LIFT_HD void uvs_cam_lift(const UvsCamDev& m, double x, double y, double* ra
         const double s = sin(th), c = cos(th);
         if (rr < 1e-10) { ray[0] = s; ray[1] = 0.0; } else { ray[0] = (s * px) / rr; ray[1] = (s * py) / rr; }
         ray[2] = c;
-    } else {                                                  // PINHOLE and MEI: the recursive distortion model of uvs_camera_lift.h
-        UvsLiftCam cam;
-        cam.inv_K11 = m.inv_K11; cam.inv_K13 = m.inv_K13; cam.inv_K22 = m.inv_K22; cam.inv_K23 = m.inv_K23;
-        cam.k1 = m.c[0]; cam.k2 = m.c[1]; cam.p1 = m.c[2]; cam.p2 = m.c[3]; cam.distort = m.flag; cam.pad = 0;
-        double mx, my;
-        uvs_lift_projective(cam, x, y, mx, my);
+    } else {                                                  // PINHOLE and MEI: the recursive distortion model
+        const double mx_d = m.inv_K11 * x + m.inv_K13, my_d = m.inv_K22 * y + m.inv_K23;
+        double mx = mx_d, my = my_d;
+        if (m.flag) {                                         // distortion() at (mx_d, my_d), then 7 times at the running estimate
+            const double k1 = m.c[0], k2 = m.c[1], p1 = m.c[2], p2 = m.c[3];
+            for (int it = 0; it < 8; ++it) {
+                const double mx2 = mx * mx, my2 = my * my, mxy = mx * my, rho2 = mx2 + my2;
+                const double rad = k1 * rho2 + k2 * rho2 * rho2;
+                const double dx = mx * rad + 2.0 * p1 * mxy + p2 * (rho2 + 2.0 * mx2);
+                const double dy = my * rad + 2.0 * p2 * mxy + p1 * (rho2 + 2.0 * my2);
+                mx = mx_d - dx; my = my_d - dy;
+            }
+        }
         ray[0] = mx; ray[1] = my;
         if (m.model == UVS_CAM_PINHOLE) { ray[2] = 1.0; nx = mx; ny = my; return; }
         const double xi = m.c[4];
@@ -114,14 +126,18 @@ UVS_LIFT_HD void uvs_cam_project(const UvsCamDev& m, double X, double Y, double 
 // ---- host: the check of a uvs_camera_model and its packing; `fn` prefixes the error text
 inline int uvs_cam_param_count(int model) { return model == UVS_CAM_PINHOLE ? 8 : model == UVS_CAM_MEI ? 9 : model == UVS_CAM_KANNALA_BRANDT ? 8 : 0; }
 
-inline int uvs_cam_check(const uvs_camera_model* model, const std::string& fn, std::string& err) {
+// `kf`: the model is a call's uvs_kf_camera (uvs_cam_pinhole), whose two texts are older than the models'
+inline int uvs_cam_check(const uvs_camera_model* model, const std::string& fn, std::string& err, bool kf = false) {
     const int n = uvs_cam_param_count(model->model);
     if (!n) { err = fn + ": unknown camera model"; return UVS_ERR_INVALID_ARG; }
-    for (int i = 0; i < n; ++i) if (!std::isfinite(model->p[i])) { err = fn + ": the camera model must be finite"; return UVS_ERR_INVALID_ARG; }
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(model->p[i])) { err = fn + (kf ? ": the camera must be finite" : ": the camera model must be finite"); return UVS_ERR_INVALID_ARG; }
     const double* p = model->p;
     const double sx = model->model == UVS_CAM_PINHOLE ? p[0] : model->model == UVS_CAM_MEI ? p[5] : p[4];
     const double sy = model->model == UVS_CAM_PINHOLE ? p[1] : model->model == UVS_CAM_MEI ? p[6] : p[5];
-    if (!(sx > 0.0) || !(sy > 0.0)) { err = fn + ": the camera model's scales (fx fy, gamma1 gamma2, mu mv) must be positive"; return UVS_ERR_INVALID_ARG; }
+    if (!(sx > 0.0) || !(sy > 0.0)) {
+        err = fn + (kf ? ": fx and fy must be positive" : ": the camera model's scales (fx fy, gamma1 gamma2, mu mv) must be positive"); return UVS_ERR_INVALID_ARG;
+    }
     if (model->model == UVS_CAM_MEI && p[0] < 0.0) { err = fn + ": xi must not be negative"; return UVS_ERR_INVALID_ARG; }
     return UVS_OK;
 }
@@ -157,8 +173,23 @@ inline UvsCamDev uvs_cam_pack(const uvs_camera_model& model) {
 }
 
 // the model argument of a set call or a batch call: checked and packed into `out`
-inline int uvs_cam_take(const uvs_camera_model* model, const std::string& fn, std::string& err, UvsCamDev* out) {
-    if (const int rc = uvs_cam_check(model, fn, err)) return rc;
+inline int uvs_cam_take(const uvs_camera_model* model, const std::string& fn, std::string& err, UvsCamDev* out, bool kf = false) {
+    if (const int rc = uvs_cam_check(model, fn, err, kf)) return rc;
     *out = uvs_cam_pack(*model);
     return UVS_OK;
+}
+
+// a uvs_kf_camera is p[0 .. 8) of a PINHOLE model
+inline uvs_camera_model uvs_cam_pinhole(const uvs_kf_camera& c) {
+    uvs_camera_model m = {};
+    m.model = UVS_CAM_PINHOLE;
+    m.p[0] = c.fx; m.p[1] = c.fy; m.p[2] = c.cx; m.p[3] = c.cy; m.p[4] = c.k1; m.p[5] = c.k2; m.p[6] = c.p1; m.p[7] = c.p2;
+    return m;
+}
+
+// the camera of a call that lifts: the handle's model where it holds one (`camera` is not looked at), else the call's camera, checked
+inline int uvs_cam_of_call(const UvsCamDev& held, const uvs_kf_camera* camera, const std::string& fn, std::string& err, UvsCamDev* out) {
+    if (held.model >= 0) { *out = held; return UVS_OK; }
+    const uvs_camera_model m = uvs_cam_pinhole(*camera);
+    return uvs_cam_take(&m, fn, err, out, true);
 }

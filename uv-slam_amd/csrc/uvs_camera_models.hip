@@ -1,17 +1,16 @@
 // uvs_camera_models.hip -- the camera models of the front ends beyond the pinhole (MEI, Kannala-Brandt; csrc/uvs_camera_models.h states them)
-// behind uvs_ft_set_camera_model, uvs_ft_lift, uvs_ft_project and uvs_lt_set_undistort_model of include/uvs_solver.h.  The handles are the
-// point tracker's (csrc/uvs_ft_handle.h) and the line tracker's (csrc/uvs_lt_handle.h); uvs_kf_set_camera_model sits with its handle in
-// csrc/uvs_keyframe_features.hip.  The in-kernel lifts of uvs_ft_track, uvs_ft_detect and uvs_kf_extract call the same device function as
+// behind uvs_ft_set_camera_model, uvs_ft_lift and uvs_ft_project of include/uvs_solver.h.  The handle is the point tracker's
+// (csrc/uvs_ft_handle.h); uvs_kf_set_camera_model sits with its handle in csrc/uvs_keyframe_features.hip, uvs_lt_set_undistort_model with
+// the map kernel in csrc/uvs_line_undistort.hip.  The in-kernel lifts of uvs_ft_track, uvs_ft_detect and uvs_kf_extract call the same device function as
 // k_cm_lift, so a point gets the same bits from either.  gfx950, the handle's one stream.
 //
-// This unit is compiled with -ffp-contract=off.  Three kernels, a lane per point or output pixel, no LDS, no atomics, no scratch memory:
+// This unit is compiled with -ffp-contract=off.  Two kernels, a lane per point, no LDS, no atomics, no scratch memory:
 //   k_cm_lift      pixel -> ray and normalized point.  PINHOLE / MEI: multiplies and adds, at most two divides and one sqrt.  KANNALA_BRANDT:
 //                  one sqrt, the root search (at most UVS_CAM_KB_ITERATIONS steps of ~20 FP64 operations and one divide; a lane leaves
 //                  the loop when its step no longer moves, the wave when all have: 2 .. 7 steps inside the shipped images), one sin and
 //                  one cos of an argument in [0, pi], four divides.  FP64 divides and the library's sin / cos are tens of instructions
 //                  each; at one point per lane the kernel is bound by them, not by its 56 bytes of traffic per point.
 //   k_cm_project   ray -> pixel; KANNALA_BRANDT: one sqrt, one atan2, the polynomial, two divides.
-//   k_cm_map       once per uvs_lt_set_undistort_model: the output pinhole's ray through project, two int32 words out (ud_fix).
 // The model is a kernel argument (UvsCamDev, 120 bytes): wave-uniform, so the branch on the model id is a scalar branch.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -22,13 +21,10 @@
 #include "../../include/uvs_solver.h"
 #include "uvs_camera_models.h"
 #include "uvs_ft_handle.h"
-#include "uvs_lt_handle.h"
 
 namespace uvscm {
 
 constexpr int kThreads = 256;
-
-struct CmMapArgs { double fx, fy, cx, cy; int Wo, Ho, cm, rm; };
 
 __global__ void __launch_bounds__(kThreads) k_cm_lift(UvsCamDev m, int n, const double* __restrict__ xy, double* __restrict__ ray,
                                                     double* __restrict__ norm) {
@@ -46,17 +42,6 @@ __global__ void __launch_bounds__(kThreads) k_cm_project(UvsCamDev m, int n, con
     double u, v;
     uvs_cam_project(m, ray[3 * i], ray[3 * i + 1], ray[3 * i + 2], u, v);
     xy[2 * i] = u; xy[2 * i + 1] = v;
-}
-
-__global__ void __launch_bounds__(kThreads) k_cm_map(UvsCamDev m, CmMapArgs A, int32_t* __restrict__ map) {
-    const int t = blockIdx.x * kThreads + threadIdx.x;
-    if (t >= A.Wo * A.Ho) return;
-    const int vo = t / A.Wo, uo = t - vo * A.Wo;
-    const double u = (double)(uo + A.cm), v = (double)(vo + A.rm);
-    const double x = (u - A.cx) / A.fx, y = (v - A.cy) / A.fy;
-    double mx, my;
-    uvs_cam_project(m, x, y, 1.0, mx, my);
-    map[2 * (size_t)t] = uvslt::ud_fix(mx); map[2 * (size_t)t + 1] = uvslt::ud_fix(my);
 }
 
 namespace {
@@ -112,8 +97,7 @@ int uvs_ft_set_camera_model(uvs_ft_tracker* h, const uvs_camera_model* model) {
     if (!model) { h->model = uvs_cam_none(); return UVS_OK; }
     UvsCamDev m;
     if (const int rc = uvs_cam_take(model, "uvs_ft_set_camera_model", h->err, &m)) return rc;
-    if (const int rc = uvs_cam_upload(h, h->d_model, m, h->model_on_device)) return rc;
-    h->model_on_device = m; h->model = m;
+    h->model = m;
     return UVS_OK;
 }
 
@@ -125,27 +109,6 @@ int uvs_ft_lift(uvs_ft_tracker* h, const uvs_camera_model* model, int n, const d
 int uvs_ft_project(uvs_ft_tracker* h, const uvs_camera_model* model, int n, const double* ray, double* xy) {
     if (!h) return UVS_ERR_INVALID_ARG;
     return cm_points(h, "uvs_ft_project", model, n, false, ray, xy, nullptr);
-}
-
-int uvs_lt_set_undistort_model(uvs_lt_tracker* h, int stream, const uvs_camera_model* model, int width, int height, int col_margin, int row_margin,
-                               double fx_out, double fy_out, double cx_out, double cy_out) {
-    if (!h) return UVS_ERR_INVALID_ARG;
-    const std::string fn = "uvs_lt_set_undistort_model";
-    h->err.clear();
-    if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
-    if (!model) { h->ud[stream].on = false; return UVS_OK; }
-    UvsCamDev m;
-    int rc = uvs_cam_take(model, fn, h->err, &m);
-    if (rc != UVS_OK) return rc;
-    if (!std::isfinite(fx_out) || !std::isfinite(fy_out) || !std::isfinite(cx_out) || !std::isfinite(cy_out) || !(fx_out > 0.0) || !(fy_out > 0.0)) {
-        h->err = fn + ": the output pinhole must be finite, fx_out and fy_out positive"; return UVS_ERR_INVALID_ARG;
-    }
-    CmMapArgs A;
-    A.fx = fx_out; A.fy = fy_out; A.cx = cx_out; A.cy = cy_out; A.cm = col_margin; A.rm = row_margin;
-    return uvslt::ud_build_map(h, fn, stream, width, height, col_margin, row_margin, [&](int Wo, int Ho, int32_t* map) {
-        A.Wo = Wo; A.Ho = Ho;
-        k_cm_map<<<(Wo * Ho + kThreads - 1) / kThreads, kThreads, 0, h->st>>>(m, A, map);
-    });
 }
 
 }  // extern "C"

@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_detect_emit(const FdItem* __res
 // key a ranks before key b: the score descending, equal scores by the pixel index descending (padding: score 0, index -1, after every candidate)
 __device__ __forceinline__ bool ranks_before(double sa, int ia, double sb, int ib) { return sa > sb || (sa == sb && ia > ib); }
 
-__global__ void __launch_bounds__(kSelThreads) k_ft_detect_select(const FdItem* __restrict__ items, UvsLiftCam cam, const UvsCamDev* __restrict__ model, int R, double* __restrict__ cand_score,
+__global__ void __launch_bounds__(kSelThreads) k_ft_detect_select(const FdItem* __restrict__ items, UvsCamDev cam, int R, double* __restrict__ cand_score,
                                                                 int* __restrict__ cand_index, uvs_ft_detect_result* __restrict__ results,
                                                                 int32_t* __restrict__ new_xy, double* __restrict__ new_score, double* __restrict__ new_norm) {
     // one LDS block, used twice: a chunk of keys while the ranking is sorted, then the taken list (y << 16 | x) and the round's survivors
@@ -341,21 +341,11 @@ __global__ void __launch_bounds__(kSelThreads) k_ft_detect_select(const FdItem* 
     __syncthreads();
     const int T = sT;
     double* onm = new_norm + 2 * F.out_off;
-    if (!model) {                                             // wave-uniform: a kernel argument; the model is read only where one is set
-        for (int t = tid; t < T; t += kSelThreads) {
-            const int q = sTaken[t];
-            double mx, my;
-            uvs_lift_projective(cam, (double)(q & 0xffff), (double)(q >> 16), mx, my);
-            onm[2 * t] = mx; onm[2 * t + 1] = my;
-        }
-    } else {
-        const UvsCamDev m = *model;
-        for (int t = tid; t < T; t += kSelThreads) {
-            const int q = sTaken[t];
-            double ray[3], mx, my;
-            uvs_cam_lift(m, (double)(q & 0xffff), (double)(q >> 16), ray, mx, my);
-            onm[2 * t] = mx; onm[2 * t + 1] = my;
-        }
+    for (int t = tid; t < T; t += kSelThreads) {
+        const int q = sTaken[t];
+        double ray[3], mx, my;
+        uvs_cam_lift(cam, (double)(q & 0xffff), (double)(q >> 16), ray, mx, my);
+        onm[2 * t] = mx; onm[2 * t + 1] = my;
     }
     if (tid == 0) results[blockIdx.x].n_new = T;
 }
@@ -378,12 +368,12 @@ int fd_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_detect
            int32_t* dbg_cindex, double* dbg_cscore) {
     const std::string fn = who_;
     h->err.clear();
-    const bool modelled = h->model.model >= 0;                // uvs_ft_set_camera_model: `camera` is not looked at
-    if (n_items < 1 || !items || (!camera && !modelled) || !new_xy || !new_score || !new_norm || !results) { h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG; }
+    if (n_items < 1 || !items || (!camera && h->model.model < 0) || !new_xy || !new_score || !new_norm || !results) { h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG; }
     if (n_items > h->max_streams) { h->err = fn + ": more items than the slots given to uvs_ft_create"; return UVS_ERR_CAPACITY; }
     if (!(quality > 0.0 && quality <= 1.0)) { h->err = fn + ": quality_level must be in (0, 1]"; return UVS_ERR_INVALID_ARG; }
     if (min_distance < 1 || min_distance > UVS_FT_MAX_MIN_DISTANCE) { h->err = fn + ": min_distance must be 1 .. UVS_FT_MAX_MIN_DISTANCE"; return UVS_ERR_INVALID_ARG; }
-    if (const int rc = modelled ? UVS_OK : check_camera(camera, fn, h->err)) return rc;
+    UvsCamDev cam;
+    if (const int rc = uvs_cam_of_call(h->model, camera, fn, h->err, &cam)) return rc;
     std::vector<char> seen(h->max_streams, 0);
     for (int i = 0; i < n_items; ++i) {
         const uvs_ft_detect_item& it = items[i];
@@ -452,7 +442,6 @@ int fd_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_detect
     int32_t* dXy = reinterpret_cast<int32_t*>(D + L.xy);
     double* dSc = reinterpret_cast<double*>(D + L.sc);
     double* dNorm = reinterpret_cast<double*>(D + L.norm);
-    const UvsLiftCam cam = modelled ? UvsLiftCam{} : uvs_lift_camera(*camera);
     const unsigned seg_blocks = (unsigned)((top_seg + kThreads / 64 - 1) / (kThreads / 64));
     hipStream_t st = h->st;
     UVS_HIP(h->err, hipEventRecord(h->ev0, st));
@@ -462,7 +451,7 @@ int fd_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_detect
     k_ft_detect_mark<<<dim3(seg_blocks, n_items), kThreads, 0, st>>>(dF, dScore, dAllowed, dRes, dMask, dCnt);
     k_ft_detect_scan<<<n_items, kThreads, 0, st>>>(dF, dCnt, dBase, dRes);
     k_ft_detect_emit<<<dim3(seg_blocks, n_items), kThreads, 0, st>>>(dF, dScore, dMask, dBase, dCs, dCi);
-    k_ft_detect_select<<<n_items, kSelThreads, 0, st>>>(dF, cam, modelled ? h->d_model.get() : nullptr, min_distance, dCs, dCi, dRes, dXy, dSc, dNorm);
+    k_ft_detect_select<<<n_items, kSelThreads, 0, st>>>(dF, cam, min_distance, dCs, dCi, dRes, dXy, dSc, dNorm);
     UVS_HIP(h->err, hipGetLastError());
     UVS_HIP(h->err, hipMemcpyAsync(h->h_det_out, D + L.res, out_bytes, hipMemcpyDeviceToHost, st));
     UVS_HIP(h->err, hipEventRecord(h->ev1, st));

@@ -15,7 +15,7 @@
 //                  registers, where they stay for the level's iterations.  An iteration stages the 22 x 22 footprint of the new pyramid,
 //                  accumulates (J - I) Dx and (J - I) Dy per lane and reduces them across the wave in 64 bits by a butterfly of shuffles, which
 //                  leaves the totals in every lane; every lane then does the same FP64 step, so the loop's branches are wave-uniform.
-//                  Lane 0 writes the point's outputs, its liftProjective (uvs_camera_lift.h) and, for uvs_ft_debug_point, the trace.
+//                  Lane 0 writes the point's outputs, its lift (uvs_cam_lift, uvs_camera_models.h) and, for uvs_ft_debug_point, the trace.
 // The item of a slot that uvs_ft_set_equalize has switched on brings a raw image: it is not copied into level 0 but handed to
 // uvsft::equalize_enqueue (uvs_feature_equalize.hip), which writes level 0 on the same stream before k_ft_pyramid runs.
 // No kernel uses scratch (build() checks it), none indexes a register array at run time, and no atomic is used.
@@ -107,7 +107,7 @@ __device__ __forceinline__ void stage(int* __restrict__ dst, const uint8_t* __re
 }
 
 __global__ void __launch_bounds__(kThreads) k_ft_track(const FtItem* __restrict__ items, const int* __restrict__ pt_item, const double* __restrict__ pts,
-                                                     const uint8_t* __restrict__ pyr, UvsLiftCam cam, const UvsCamDev* __restrict__ model, int levels, int n_total,
+                                                     const uint8_t* __restrict__ pyr, UvsCamDev cam, int levels, int n_total,
                                                      double* __restrict__ next_xy, double* __restrict__ next_norm, int* __restrict__ status,
                                                      int* __restrict__ iterations, double* __restrict__ trace) {
     __shared__ int sPrev[kWaves][kPrevSide * kPrevSide];
@@ -233,10 +233,7 @@ __global__ void __launch_bounds__(kThreads) k_ft_track(const FtItem* __restrict_
     }
     if (lane == 0) {
         double mx = 0.0, my = 0.0;
-        if (st == UVS_FT_TRACKED) {
-            if (!model) uvs_lift_projective(cam, qx, qy, mx, my);      // wave-uniform: a kernel argument; the model is read only where one is set
-            else { const UvsCamDev m = *model; double ray[3]; uvs_cam_lift(m, qx, qy, ray, mx, my); }
-        }
+        if (st == UVS_FT_TRACKED) { double ray[3]; uvs_cam_lift(cam, qx, qy, ray, mx, my); }
         next_xy[2 * g] = qx; next_xy[2 * g + 1] = qy;
         next_norm[2 * g] = mx; next_norm[2 * g + 1] = my;
         status[g] = st; iterations[g] = it0;
@@ -263,12 +260,12 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
            int32_t* iterations, double* next_norm, int32_t* results, double* trace) {
     const std::string fn = who_;
     h->err.clear();
-    const bool modelled = h->model.model >= 0;                // uvs_ft_set_camera_model: `camera` is not looked at
-    if (n_items < 1 || !items || (!camera && !modelled) || !next_xy || !status || !iterations || !next_norm || !results) {
+    if (n_items < 1 || !items || (!camera && h->model.model < 0) || !next_xy || !status || !iterations || !next_norm || !results) {
         h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG;
     }
     if (n_items > h->max_streams) { h->err = fn + ": more items than the slots given to uvs_ft_create"; return UVS_ERR_CAPACITY; }
-    if (const int rc = modelled ? UVS_OK : check_camera(camera, fn, h->err)) return rc;
+    UvsCamDev cam;
+    if (const int rc = uvs_cam_of_call(h->model, camera, fn, h->err, &cam)) return rc;
     const int min_size = UVS_FT_MIN_SIZE << (h->levels - 1);
     std::vector<char> seen(h->max_streams, 0);
     size_t total = 0;
@@ -332,7 +329,6 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
     int* dSt = reinterpret_cast<int*>(h->d_out + L.status);
     int* dIt = reinterpret_cast<int*>(h->d_out + L.iters);
     double* dTrace = reinterpret_cast<double*>(h->d_out + L.trace);
-    const UvsLiftCam cam = modelled ? UvsLiftCam{} : uvs_lift_camera(*camera);
     hipStream_t st = h->st;
     UVS_HIP(h->err, hipSetDevice(h->device));
     UVS_HIP(h->err, hipEventRecord(h->ev0, st));
@@ -347,7 +343,7 @@ int ft_run(uvs_ft_tracker* h, const char* who_, int n_items, const uvs_ft_item* 
         k_ft_pyramid<<<dim3((top_w[l] + kPyrTW - 1) / kPyrTW, (top_h[l] + kPyrTH - 1) / kPyrTH, n_items), kThreads, 0, st>>>(dF, h->d_pyr, l);
     if (total) {
         if (trace) UVS_HIP(h->err, hipMemsetAsync(dTrace, 0, (size_t)kMaxLevels * UVS_FT_TRACE_LEVEL * 8, st));
-        k_ft_track<<<(unsigned)((total + kWaves - 1) / kWaves), kThreads, 0, st>>>(dF, dPi, dPts, h->d_pyr, cam, modelled ? h->d_model.get() : nullptr, h->levels, (int)total, dXy, dNorm, dSt, dIt,
+        k_ft_track<<<(unsigned)((total + kWaves - 1) / kWaves), kThreads, 0, st>>>(dF, dPi, dPts, h->d_pyr, cam, h->levels, (int)total, dXy, dNorm, dSt, dIt,
                                                                                  trace ? dTrace : nullptr);
     }
     UVS_HIP(h->err, hipGetLastError());

@@ -50,8 +50,6 @@ struct uvs_ft_tracker : UvsHandle {
     // camera model (uvs_camera_models.hip): uvs_ft_set_camera_model's, which uvs_ft_track and uvs_ft_detect lift through while it is set
     // (model.model < 0: none; uvs_ft_reset keeps it), and the buffers of uvs_ft_lift / uvs_ft_project, allocated by the first call
     UvsCamDev model = uvs_cam_none();
-    DevBuf<UvsCamDev> d_model;                  // its copy on the device, which k_ft_track and k_ft_detect_select read
-    UvsCamDev model_on_device = uvs_cam_none(); // what d_model holds: the same model set again is not uploaded again
     DevBuf<char> d_cm;                          // one call's points: (xy | ray | norm)
     PinnedBuf<char> h_cm;
 };

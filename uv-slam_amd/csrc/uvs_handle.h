@@ -1,6 +1,6 @@
 // uvs_handle.h -- the host scaffolding the front-end units share, one statement of each: what every handle owns besides its buffers (device,
-// stream, timing events, error text) with the way it is opened and closed, the sizes and the bump arena of the packed call buffers, and the check
-// of a uvs_kf_camera.  Used by uvs_pose_graph, uvs_loop_verify, uvs_vanishing_points, uvs_keyframe_features and, through uvs_ft_handle.h, the
+// stream, timing events, error text) with the way it is opened and closed, and the sizes and the bump arena of the packed call buffers.
+// Used by uvs_pose_graph, uvs_loop_verify, uvs_vanishing_points, uvs_keyframe_features and, through uvs_ft_handle.h, the
 // three units of the point front end.  Nothing here runs on the device.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,14 +20,6 @@ struct UvsArena {
     size_t o = 0;
     size_t take(size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; }
 };
-
-// the camera of the calls that lift pixels to normalized points; `fn` prefixes the error text
-inline int check_camera(const uvs_kf_camera* camera, const std::string& fn, std::string& err) {
-    const double cam_v[8] = {camera->fx, camera->fy, camera->cx, camera->cy, camera->k1, camera->k2, camera->p1, camera->p2};
-    for (double c : cam_v) if (!std::isfinite(c)) { err = fn + ": the camera must be finite"; return UVS_ERR_INVALID_ARG; }
-    if (!(camera->fx > 0.0) || !(camera->fy > 0.0)) { err = fn + ": fx and fy must be positive"; return UVS_ERR_INVALID_ARG; }
-    return UVS_OK;
-}
 
 // Base of every handle struct.  A *_create makes the handle with new, calls open(), allocates; on a failure, and in *_destroy, it calls close()
 // and deletes the handle.  The buffers of the derived struct are freed before the stream is destroyed.
@@ -54,15 +46,3 @@ struct UvsHandle {
         if (st) (void)hipStreamSynchronize(st);
     }
 };
-
-// a handle's copy of a small struct on the device (a camera model, which the kernels read through a pointer only where one is set): allocated by
-// the first call, written on the handle's stream, which is idle between the calls
-template <class T>
-inline int uvs_cam_upload(UvsHandle* h, DevBuf<T>& dst, const T& value, const T& held) {
-    if (dst.get() && std::memcmp(&value, &held, sizeof(T)) == 0) return UVS_OK;      // the copy on the device is this one already
-    UVS_HIP(h->err, hipSetDevice(h->device));
-    if (const int rc = dst.ensure(sizeof(T), h->err)) return rc;
-    UVS_HIP(h->err, hipMemcpyAsync(dst.get(), &value, sizeof(T), hipMemcpyHostToDevice, h->st));
-    UVS_HIP(h->err, hipStreamSynchronize(h->st));
-    return UVS_OK;
-}

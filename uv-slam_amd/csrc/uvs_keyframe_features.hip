@@ -57,7 +57,6 @@ struct KfFrame {                   // device copy of one uvs_kf_frame
     int seg_off;                   // offset of the first segment in the segment arrays
     long long img_off;             // byte offset of the image / blurred image / score map in their buffers
 };
-using KfCam = UvsLiftCam;         // uvs_camera_lift.h: shared with the feature tracker
 
 __device__ __forceinline__ unsigned byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 255u; }
 
@@ -239,7 +238,7 @@ __global__ void __launch_bounds__(kThreads) k_kf_select_emit(const KfFrame* __re
 }
 
 // ---- BRIEF of the keypoints and of the window points, liftProjective of the keypoints: a wave per point
-__global__ void __launch_bounds__(kThreads) k_kf_describe(const KfFrame* __restrict__ frames, KfCam cam, const UvsCamDev* __restrict__ model, const uint8_t* __restrict__ blur,
+__global__ void __launch_bounds__(kThreads) k_kf_describe(const KfFrame* __restrict__ frames, UvsCamDev cam, const uint8_t* __restrict__ blur,
                                                         const int32_t* __restrict__ pattern, const uvs_kf_result* __restrict__ results,
                                                         const int32_t* __restrict__ xy, const float* __restrict__ window_uv, int max_keypoints,
                                                         double* __restrict__ norm, unsigned long long* __restrict__ desc,
@@ -257,10 +256,9 @@ __global__ void __launch_bounds__(kThreads) k_kf_describe(const KfFrame* __restr
         const int x = xy[2 * o], y = xy[2 * o + 1];
         u = (float)x; v = (float)y;
         out = desc + 4 * o;
-        if (lane == 0) {                                      // PinholeCamera::liftProjective
-            double mx_u, my_u;
-            if (!model) uvs_lift_projective(cam, (double)x, (double)y, mx_u, my_u);      // wave-uniform: a kernel argument; the model is read only where one is set
-            else { const UvsCamDev m = *model; double ray[3]; uvs_cam_lift(m, (double)x, (double)y, ray, mx_u, my_u); }
+        if (lane == 0) {                                      // liftProjective of the call's camera or the handle's model
+            double ray[3], mx_u, my_u;
+            uvs_cam_lift(cam, (double)x, (double)y, ray, mx_u, my_u);
             norm[2 * o] = mx_u; norm[2 * o + 1] = my_u;
         }
     } else {
@@ -299,8 +297,6 @@ struct uvs_kf_extractor : UvsHandle {
     DevBuf<int> d_seg_cnt, d_seg_base;          // its count, its exclusive prefix
     DevBuf<int32_t> d_pattern;                  // x1 | y1 | x2 | y2
     UvsCamDev model = uvs_cam_none();           // uvs_kf_set_camera_model: the keypoints are lifted through it while it is set (model.model >= 0)
-    DevBuf<UvsCamDev> d_model;                  // ... and its copy on the device, which k_kf_describe reads
-    UvsCamDev model_on_device = uvs_cam_none(); // what d_model holds: the same model set again (a keyframe each) is not uploaded again
 };
 
 namespace {
@@ -324,12 +320,12 @@ int kf_run(uvs_kf_extractor* h, const char* who_, int n_frames, const uvs_kf_fra
            uint8_t* keypoint_score, double* keypoints_norm, uint64_t* desc, uint64_t* window_desc, uvs_kf_result* results) {
     const std::string fn = who_;
     h->err.clear();
-    const bool modelled = h->model.model >= 0;                // uvs_kf_set_camera_model: `camera` is not looked at
-    if (n_frames < 1 || !frames || (!camera && !modelled) || !keypoints_xy || !keypoint_score || !keypoints_norm || !desc || !window_desc || !results) {
+    if (n_frames < 1 || !frames || (!camera && h->model.model < 0) || !keypoints_xy || !keypoint_score || !keypoints_norm || !desc || !window_desc || !results) {
         h->err = fn + ": null pointer or bad count"; return UVS_ERR_INVALID_ARG;
     }
     if (n_frames > h->max_frames) { h->err = fn + ": more frames than the capacity given to uvs_kf_create"; return UVS_ERR_CAPACITY; }
-    if (const int rc = modelled ? UVS_OK : check_camera(camera, fn, h->err)) return rc;
+    UvsCamDev cam;
+    if (const int rc = uvs_cam_of_call(h->model, camera, fn, h->err, &cam)) return rc;
     size_t tw = 0, img_bytes = 0, n_seg = 0;
     int max_w = 0, max_h = 0, max_nw = 0;
     for (int f = 0; f < n_frames; ++f) {
@@ -374,7 +370,6 @@ int kf_run(uvs_kf_extractor* h, const char* who_, int n_frames, const uvs_kf_fra
     unsigned long long* dWdesc = reinterpret_cast<unsigned long long*>(h->d_out + L.wdesc);
     int32_t* dXy = reinterpret_cast<int32_t*>(h->d_out + L.xy);
     uint8_t* dSc = reinterpret_cast<uint8_t*>(h->d_out + L.score);
-    const KfCam cam = modelled ? KfCam{} : uvs_lift_camera(*camera);
     const int waves = kThreads / 64;
     const unsigned seg_blocks = (unsigned)((max_h * segs_of(max_w) + waves - 1) / waves);
     const unsigned item_blocks = (unsigned)((h->max_keypoints + max_nw + waves - 1) / waves);
@@ -389,7 +384,7 @@ int kf_run(uvs_kf_extractor* h, const char* who_, int n_frames, const uvs_kf_fra
     k_kf_select_mark<<<dim3(seg_blocks, n_frames), kThreads, 0, st>>>(dF, h->d_score, h->d_seg_mask, h->d_seg_cnt);
     k_kf_select_scan<<<n_frames, kThreads, 0, st>>>(dF, h->d_seg_cnt, h->d_seg_base, dRes, h->max_keypoints);
     k_kf_select_emit<<<dim3(seg_blocks, n_frames), kThreads, 0, st>>>(dF, h->d_score, h->d_seg_mask, h->d_seg_base, h->max_keypoints, dXy, dSc);
-    k_kf_describe<<<dim3(item_blocks, n_frames), kThreads, 0, st>>>(dF, cam, modelled ? h->d_model.get() : nullptr, h->d_blur, h->d_pattern, dRes, dXy, dWin, h->max_keypoints, dNorm, dDesc, dWdesc);
+    k_kf_describe<<<dim3(item_blocks, n_frames), kThreads, 0, st>>>(dF, cam, h->d_blur, h->d_pattern, dRes, dXy, dWin, h->max_keypoints, dNorm, dDesc, dWdesc);
     UVS_HIP(h->err, hipGetLastError());
     UVS_HIP(h->err, hipMemcpyAsync(h->h_out, h->d_out, L.total, hipMemcpyDeviceToHost, st));
     UVS_HIP(h->err, hipEventRecord(h->ev1, st));
@@ -463,8 +458,7 @@ int uvs_kf_set_camera_model(uvs_kf_extractor* h, const uvs_camera_model* model) 
     if (!model) { h->model = uvs_cam_none(); return UVS_OK; }
     UvsCamDev m;
     if (const int rc = uvs_cam_take(model, "uvs_kf_set_camera_model", h->err, &m)) return rc;
-    if (const int rc = uvs_cam_upload(h, h->d_model, m, h->model_on_device)) return rc;
-    h->model_on_device = m; h->model = m;
+    h->model = m;
     return UVS_OK;
 }
 

@@ -1,11 +1,12 @@
 // uvs_line_undistort.hip -- undistortion of the line front end's images (the place of imageUndistortion and the margin crop in the reference's
-// readImage4Line) behind uvs_lt_set_undistort, uvs_lt_set_remap, uvs_lt_get_remap and uvs_lt_undistort of include/uvs_solver.h: a fixed-point
+// readImage4Line) behind uvs_lt_set_undistort, uvs_lt_set_undistort_model, uvs_lt_set_remap, uvs_lt_get_remap and uvs_lt_undistort of include/uvs_solver.h: a fixed-point
 // map per slot and a bilinear remap with a zero border, the project's own rule, stated in the header and restated in tests/ud_ref.py, which
 // this unit is held to word for word and byte for byte.  The handle is the line tracker's (csrc/uvs_lt_handle.h); uvs_lt_detect_track calls
 // ud_launch for the items of mapped slots between its upload and its first kernel.  gfx950, the handle's one stream.
 //
 // This unit is compiled with -ffp-contract=off.  Two kernels:
-//   k_lt_ud_map     once per uvs_lt_set_undistort: a lane per output pixel, the header's FP64 chain, two int32 words out
+//   k_lt_ud_map     once per uvs_lt_set_undistort or uvs_lt_set_undistort_model: a lane per output pixel, the output pinhole's ray through
+//                   uvs_cam_project (csrc/uvs_camera_models.h; for a pinhole the header's FP64 chain), two int32 words out
 //   k_lt_ud_remap   one launch for all items of a call (the item in grid.y).  The output image is packed (stride = Wo), so it and its map are
 //                   flat arrays: a lane owns the four consecutive output pixels 4 t .. 4 t + 3, reads their eight map words as two 16-byte
 //                   loads, its sixteen taps as byte loads (a raw frame stays in L2), and stores its four results as one dword; consecutive
@@ -22,25 +23,32 @@
 #include <vector>
 
 #include "../../include/uvs_solver.h"
+#include "uvs_camera_models.h"
 #include "uvs_lt_handle.h"
 
 namespace uvslt {
 
 constexpr int kUdThreads = 256;
-struct UdMapArgs { double fx, fy, cx, cy, k1, k2, p1, p2; int Wo, Ho, cm, rm; };
+constexpr int kUdLimit = 1 << 24;              // |X|, |Y| of a map word
 
-// ---- the map: the header's chain, one rounding per operation (ud_fix: uvs_lt_handle.h)
-__global__ void __launch_bounds__(kUdThreads) k_lt_ud_map(UdMapArgs A, int32_t* __restrict__ map) {
+struct UdOutput { double fx, fy, cx, cy; int Wo, Ho, cm, rm; };      // the pinhole of the undistorted image, its size, the margins
+
+// ---- the map: the header's chain, one rounding per operation
+// a raw position in pixels -> a map word: 5 fractional bits, clamped, a value that is not finite becomes -2^24
+__device__ __forceinline__ int32_t ud_fix(double m) {
+    const double v = rint(32.0 * m);
+    if (!isfinite(v)) return -kUdLimit;
+    return (int32_t)fmin(fmax(v, (double)-kUdLimit), (double)kUdLimit);
+}
+
+__global__ void __launch_bounds__(kUdThreads) k_lt_ud_map(UvsCamDev cam, UdOutput A, int32_t* __restrict__ map) {
     const int t = blockIdx.x * kUdThreads + threadIdx.x;
     if (t >= A.Wo * A.Ho) return;
     const int vo = t / A.Wo, uo = t - vo * A.Wo;
     const double u = (double)(uo + A.cm), v = (double)(vo + A.rm);
     const double x = (u - A.cx) / A.fx, y = (v - A.cy) / A.fy;
-    const double x2 = x * x, y2 = y * y, xy = x * y, r2 = x2 + y2;
-    const double kr = 1.0 + (A.k1 * r2 + A.k2 * (r2 * r2));
-    const double xd = x * kr + ((2.0 * A.p1) * xy + A.p2 * (r2 + 2.0 * x2));
-    const double yd = y * kr + (A.p1 * (r2 + 2.0 * y2) + (2.0 * A.p2) * xy);
-    const double mx = A.fx * xd + A.cx, my = A.fy * yd + A.cy;
+    double mx, my;
+    uvs_cam_project(cam, x, y, 1.0, mx, my);
     map[2 * (size_t)t] = ud_fix(mx); map[2 * (size_t)t + 1] = ud_fix(my);
 }
 
@@ -97,6 +105,40 @@ UdLayout ud_layout(size_t n, const std::vector<size_t>& src_bytes, const std::ve
     return Y;
 }
 
+// the size checks of the set calls
+int ud_check_sizes(uvs_lt_tracker* h, const std::string& fn, int stream, int W, int H, int Wo, int Ho) {
+    if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
+    if (W < UVS_LT_MIN_SIZE || H < UVS_LT_MIN_SIZE || Wo < UVS_LT_MIN_SIZE || Ho < UVS_LT_MIN_SIZE) {
+        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
+    }
+    if (W > h->max_width || H > h->max_height || Wo > h->max_width || Ho > h->max_height) {
+        h->err = fn + " exceeds the capacity given to uvs_lt_create"; return UVS_ERR_CAPACITY;
+    }
+    return UVS_OK;
+}
+
+// What the two calls that build a slot's map on the device share once their camera has passed: the checks of the margins and the sizes, the
+// slot's map memory, the kernel and the wait.  A holds the output pinhole; its sizes and margins are filled in here.
+int ud_build_map(uvs_lt_tracker* h, const std::string& fn, int stream, const UvsCamDev& cam, UdOutput A, int width, int height, int col_margin, int row_margin) {
+    if (col_margin < 0 || row_margin < 0) { h->err = fn + ": negative margin"; return UVS_ERR_INVALID_ARG; }
+    if (width < UVS_LT_MIN_SIZE || height < UVS_LT_MIN_SIZE || col_margin > width / 2 || row_margin > height / 2) {      // before W - 2 cm is formed
+        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
+    }
+    const int Wo = width - 2 * col_margin, Ho = height - 2 * row_margin;
+    int rc = ud_check_sizes(h, fn, stream, width, height, Wo, Ho);
+    if (rc != UVS_OK) return rc;
+    LtUndistort& U = h->ud[stream];
+    UVS_HIP(h->err, hipSetDevice(h->device));
+    U.on = false;                               // every argument has passed: a HIP failure below leaves the slot without a map, not with half of one
+    if ((rc = U.map.ensure(8 * (size_t)Wo * Ho, h->err)) != UVS_OK) return rc;
+    A.Wo = Wo; A.Ho = Ho; A.cm = col_margin; A.rm = row_margin;
+    k_lt_ud_map<<<(Wo * Ho + kUdThreads - 1) / kUdThreads, kUdThreads, 0, h->st>>>(cam, A, U.map.get());
+    UVS_HIP(h->err, hipGetLastError());
+    UVS_HIP(h->err, hipStreamSynchronize(h->st));
+    U.W = width; U.H = height; U.Wo = Wo; U.Ho = Ho; U.on = true;
+    return UVS_OK;
+}
+
 }  // namespace
 
 }  // namespace uvslt
@@ -111,15 +153,29 @@ int uvs_lt_set_undistort(uvs_lt_tracker* h, int stream, const uvs_kf_camera* cam
     h->err.clear();
     if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
     if (!camera) { h->ud[stream].on = false; return UVS_OK; }
-    int rc = check_camera(camera, fn, h->err);
-    if (rc != UVS_OK) return rc;
-    UdMapArgs A;
-    A.fx = camera->fx; A.fy = camera->fy; A.cx = camera->cx; A.cy = camera->cy; A.k1 = camera->k1; A.k2 = camera->k2; A.p1 = camera->p1; A.p2 = camera->p2;
-    A.cm = col_margin; A.rm = row_margin;
-    return ud_build_map(h, fn, stream, width, height, col_margin, row_margin, [&](int Wo, int Ho, int32_t* map) {
-        A.Wo = Wo; A.Ho = Ho;
-        k_lt_ud_map<<<(Wo * Ho + kUdThreads - 1) / kUdThreads, kUdThreads, 0, h->st>>>(A, map);
-    });
+    const uvs_camera_model model = uvs_cam_pinhole(*camera);
+    UvsCamDev cam;
+    if (const int rc = uvs_cam_take(&model, fn, h->err, &cam, true)) return rc;
+    UdOutput A = {};
+    A.fx = camera->fx; A.fy = camera->fy; A.cx = camera->cx; A.cy = camera->cy;      // the output pinhole is the camera's own
+    return ud_build_map(h, fn, stream, cam, A, width, height, col_margin, row_margin);
+}
+
+int uvs_lt_set_undistort_model(uvs_lt_tracker* h, int stream, const uvs_camera_model* model, int width, int height, int col_margin, int row_margin,
+                               double fx_out, double fy_out, double cx_out, double cy_out) {
+    if (!h) return UVS_ERR_INVALID_ARG;
+    const std::string fn = "uvs_lt_set_undistort_model";
+    h->err.clear();
+    if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
+    if (!model) { h->ud[stream].on = false; return UVS_OK; }
+    UvsCamDev cam;
+    if (const int rc = uvs_cam_take(model, fn, h->err, &cam)) return rc;
+    if (!std::isfinite(fx_out) || !std::isfinite(fy_out) || !std::isfinite(cx_out) || !std::isfinite(cy_out) || !(fx_out > 0.0) || !(fy_out > 0.0)) {
+        h->err = fn + ": the output pinhole must be finite, fx_out and fy_out positive"; return UVS_ERR_INVALID_ARG;
+    }
+    UdOutput A = {};
+    A.fx = fx_out; A.fy = fy_out; A.cx = cx_out; A.cy = cy_out;
+    return ud_build_map(h, fn, stream, cam, A, width, height, col_margin, row_margin);
 }
 
 int uvs_lt_set_remap(uvs_lt_tracker* h, int stream, int src_width, int src_height, int out_width, int out_height, const int32_t* map_xy) {

@@ -2,8 +2,7 @@
 // destroys it, describes and matches segments, keeps the slots' previous lines), csrc/uvs_line_detect.hip (detects the segments of an image
 // and hands them to the tracking unit without a second upload of the image) and csrc/uvs_line_undistort.hip (the slots' undistortion maps and
 // the remap of a raw image, which the detection unit calls in front of its own kernels).  Device, stream, events and error text are the base's
-// (uvs_handle.h).  csrc/uvs_camera_models.hip builds a slot's map for a camera model into the same state.  Host only, but for the three structs
-// the kernels read and ud_fix, the quantisation of a map word.
+// (uvs_handle.h).  Host only, but for the three structs the kernels read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -141,49 +140,5 @@ int lt_run(uvs_lt_tracker* h, int n_items, const uvs_lt_item* items, const std::
 // The remap kernel of uvs_line_undistort.hip on the handle's stream: n items (the device array `items`) of at most max_out output pixels, the raw
 // images at src + src_off, the outputs at dst + dst_off.  uvs_lt_detect_track launches it between its upload and its first kernel.
 int ud_launch(uvs_lt_tracker* h, int n, const UdItem* items, const uint8_t* src, uint8_t* dst, int max_out);
-
-// ---- what the builders of a slot's map share (uvs_line_undistort.hip: the pinhole's and the caller's own; uvs_camera_models.hip: any model's)
-constexpr int kUdLimit = 1 << 24;              // |X|, |Y| of a map word
-
-// a raw position in pixels -> a map word: 5 fractional bits, clamped, a value that is not finite becomes -2^24
-__device__ __forceinline__ int32_t ud_fix(double m) {
-    const double v = rint(32.0 * m);
-    if (!isfinite(v)) return -kUdLimit;
-    return (int32_t)fmin(fmax(v, (double)-kUdLimit), (double)kUdLimit);
-}
-
-// the size checks of the set calls
-inline int ud_check_sizes(uvs_lt_tracker* h, const std::string& fn, int stream, int W, int H, int Wo, int Ho) {
-    if (stream < 0 || stream >= h->max_streams) { h->err = fn + ": stream outside the handle's slots"; return UVS_ERR_INVALID_ARG; }
-    if (W < UVS_LT_MIN_SIZE || H < UVS_LT_MIN_SIZE || Wo < UVS_LT_MIN_SIZE || Ho < UVS_LT_MIN_SIZE) {
-        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
-    }
-    if (W > h->max_width || H > h->max_height || Wo > h->max_width || Ho > h->max_height) {
-        h->err = fn + " exceeds the capacity given to uvs_lt_create"; return UVS_ERR_CAPACITY;
-    }
-    return UVS_OK;
-}
-
-// What the two calls that build a slot's map on the device share once their camera has passed: the checks of the margins and the sizes, the
-// slot's map memory, the kernel and the wait.  launch(Wo, Ho, map) enqueues the kernel on h->st.
-template <class Launch>
-inline int ud_build_map(uvs_lt_tracker* h, const std::string& fn, int stream, int width, int height, int col_margin, int row_margin, Launch launch) {
-    if (col_margin < 0 || row_margin < 0) { h->err = fn + ": negative margin"; return UVS_ERR_INVALID_ARG; }
-    if (width < UVS_LT_MIN_SIZE || height < UVS_LT_MIN_SIZE || col_margin > width / 2 || row_margin > height / 2) {      // before W - 2 cm is formed
-        h->err = fn + ": a source or output width or height below UVS_LT_MIN_SIZE"; return UVS_ERR_INVALID_ARG;
-    }
-    const int Wo = width - 2 * col_margin, Ho = height - 2 * row_margin;
-    int rc = ud_check_sizes(h, fn, stream, width, height, Wo, Ho);
-    if (rc != UVS_OK) return rc;
-    LtUndistort& U = h->ud[stream];
-    UVS_HIP(h->err, hipSetDevice(h->device));
-    U.on = false;                               // every argument has passed: a HIP failure below leaves the slot without a map, not with half of one
-    if ((rc = U.map.ensure(8 * (size_t)Wo * Ho, h->err)) != UVS_OK) return rc;
-    launch(Wo, Ho, U.map.get());
-    UVS_HIP(h->err, hipGetLastError());
-    UVS_HIP(h->err, hipStreamSynchronize(h->st));
-    U.W = width; U.H = height; U.Wo = Wo; U.Ho = Ho; U.on = true;
-    return UVS_OK;
-}
 
 }  // namespace uvslt

@@ -37,13 +37,12 @@ inline void reduceVector(std::vector<T>& v, const std::vector<uint8_t>& status) 
 // it from uvs_ft_track; a test may feed it by hand.
 class FeatureTrackerBook {
 public:
-    explicit FeatureTrackerBook(const uvs_kf_camera& camera) : camera_(camera), lift_(uvs_lift_camera(camera)) {}
+    explicit FeatureTrackerBook(const uvs_kf_camera& camera) : camera_(camera), lift_(uvs_cam_pack(uvs_cam_pinhole(camera))) {}
     // any camera model (MEI, Kannala-Brandt, or the pinhole given as one): the points are lifted through uvs_cam_lift, the device function of
     // uvs_ft_lift.  Throws std::invalid_argument for a model the library would reject.
-    explicit FeatureTrackerBook(const uvs_camera_model& model) : camera_{}, lift_{}, has_model_(true), model_(model) {
+    explicit FeatureTrackerBook(const uvs_camera_model& model) : camera_{}, has_model_(true) {
         std::string err;
-        if (uvs_cam_check(&model, "FeatureTrackerBook", err) != UVS_OK) throw std::invalid_argument(err);
-        model_dev_ = uvs_cam_pack(model);
+        if (uvs_cam_take(&model, "FeatureTrackerBook", err, &lift_) != UVS_OK) throw std::invalid_argument(err);
     }
 
     // :81-107 after the flow: forw_pts = next_xy, status[i] = (ft_status[i] == UVS_FT_TRACKED) (the device has applied inBorder), the six
@@ -120,14 +119,13 @@ public:
     }
 
     // :240-288.  The normalized coordinates of the tracked points are the device's; a point added in this frame is lifted here by the same
-    // function (uvs_camera_lift.h; with a camera model, uvs_camera_models.h).  std::map::insert keeps the first entry of a key, as the reference's does for the ids still -1.
+    // function (uvs_cam_lift of uvs_camera_models.h).  std::map::insert keeps the first entry of a key, as the reference's does for the ids still -1.
     void undistortedPoints() {
         cur_un_pts.clear(); cur_un_pts_map.clear();
         for (size_t i = 0; i < cur_pts.size(); ++i) {
             Point2d b;
             if (i < forw_norm_.size()) b = forw_norm_[i];
-            else if (has_model_) { double ray[3]; uvs_cam_lift(model_dev_, cur_pts[i].x, cur_pts[i].y, ray, b.x, b.y); }
-            else uvs_lift_projective(lift_, cur_pts[i].x, cur_pts[i].y, b.x, b.y);
+            else { double ray[3]; uvs_cam_lift(lift_, cur_pts[i].x, cur_pts[i].y, ray, b.x, b.y); }
             cur_un_pts.push_back(b);
             cur_un_pts_map.insert(std::make_pair(ids[i], b));
         }
@@ -168,10 +166,8 @@ public:
 
 protected:
     uvs_kf_camera camera_;
-    UvsLiftCam lift_;
-    bool has_model_ = false;          // constructed from a uvs_camera_model: camera_ and lift_ are not used
-    uvs_camera_model model_ = {};
-    UvsCamDev model_dev_ = uvs_cam_none();
+    UvsCamDev lift_ = uvs_cam_none(); // the camera or the model, packed: what undistortedPoints lifts through
+    bool has_model_ = false;          // constructed from a uvs_camera_model: camera_ is not used
     const uvs_kf_camera* cameraArg() const { return has_model_ ? nullptr : &camera_; }      // the `camera` of uvs_ft_track / uvs_ft_detect
     std::vector<Point2d> forw_norm_;
 
@@ -198,7 +194,7 @@ public:
         : FeatureTrackerBook(model), max_points_(max_points) {
         int rc = uvs_ft_create(device, 1, max_width, max_height, levels, max_points, &ft_);
         if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_ft_create: ") + uvs_status_string(rc));
-        if ((rc = uvs_ft_set_camera_model(ft_, &model_)) != UVS_OK) {
+        if ((rc = uvs_ft_set_camera_model(ft_, &model)) != UVS_OK) {
             const std::string text = uvs_ft_last_error(ft_);
             uvs_ft_destroy(ft_);
             throw std::runtime_error("uvs_ft_set_camera_model: " + text);
