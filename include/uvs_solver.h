@@ -1380,6 +1380,70 @@ int uvs_pr_detect(uvs_place_recognizer *pr, int n_features, const uint64_t *desc
  * vector), 2 the query (scoring, download); a part the call did not run is 0. */
 double uvs_pr_last_device_ms(const uvs_place_recognizer *pr, int part);
 
+/* ---- triangulation of landmarks: the state a solve starts from (uvs_tri_*, csrc/uvs_triangulate.hip; additions only, the ABI version stays 7) ----
+ * FeatureManager::triangulate (feature_manager.cpp:427-481), triangulateLine (:504-589, calcPluckerLine :827-902), the validity rule of
+ * setLineOrtho (:352-416) and the re-anchoring of removeBackShiftDepth (:627-634) for whole batches of landmarks, one lane per landmark, FP64.
+ * The caller lists only the landmarks to be worked on: the reference's selection rules (used_num >= 2 && start_frame < WINDOW_SIZE - 2,
+ * estimated_depth <= 0, orthonormal_vec[3] == 0 with at least two views) stay host bookkeeping.
+ *   point       camera k of a track is frame pt_start + k, the start frame's own view included; its pose relative to the start camera gives
+ *               P = [R^T | -R^T t]; with f = obs / |obs| the rows f0 P.row(2) - f2 P.row(0) and f1 P.row(2) - f2 P.row(1) make the 2n x 4 matrix
+ *               svd_A; depth = V[2] / V[3] of its smallest right singular vector (of svd_A itself, never of svd_A^T svd_A).
+ *               pt_flag 0: kept.  1: the value was < 0.1, init_depth is returned (:475-478).  2: the value was not finite, init_depth is
+ *               returned -- a stated deviation, the reference lets a NaN through into para_Feature.
+ *   line        a = sp_i x ep_i; b = (R_rel sp_j) x (R_rel ep_j); beta = -b . t_rel; d_l = b x a; n_l = a beta; d_w = R_left d_l;
+ *               n_w = R_left n_l + t_left x d_w; U = [n_w / |n_w|, d_w / |d_w|, (n_w x d_w) / |n_w x d_w|];
+ *               orth = (Eigen 3.3 eulerAngles(0, 1, 2) of U with the first angle in [0, pi], atan2(|d_w|, |n_w|)).
+ *               ln_flag 0: ok.  2: |d_w|, |n_w| or |n_w x d_w| is zero or not finite; orth is four zeros ("no parameters yet" to the caller's
+ *               own rule) -- the second stated deviation, the reference stores NaN.
+ *   check       with orth_old, the line in the start camera, cut by the two planes through the first observation's end points (each spanned by
+ *               the end point and the end point moved by (1, -(ep_x - sp_x) / (ep_y - sp_y)); the division and what follows from it are the
+ *               reference's); flag 2 where D_s(2) / w_s < 0 or D_e(2) / w_e < 0, else 1.
+ *   shift       depth_out = (new_R^T (marg_R (uv0 depth) + marg_P - new_P)).z, flag 0; where that is not > 0: the handle's init_depth, flag 1.
+ * No CPU path: uvs_tri_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_TRI_MAX_WINDOWS 4096              /* largest max_windows uvs_tri_create takes */
+#define UVS_TRI_MAX_LANDMARKS (1 << 22)       /* largest max_points / max_lines; max_point_obs up to UVS_NUM_FRAMES times as many */
+typedef struct uvs_tri uvs_tri;               /* opaque: device buffers, pinned staging, stream */
+
+typedef struct uvs_tri_batch {
+    int32_t n_windows, n_points, n_lines, reserved;
+    const double *pose;                /* [n_windows][UVS_NUM_FRAMES][7], as uvs_window.pose */
+    const double *ex_pose;             /* [n_windows][7], as uvs_window.ex_pose */
+    const int32_t *pt_window;          /* [n_points], non-decreasing */
+    const int32_t *pt_start;           /* [n_points] start frame */
+    const int32_t *pt_obs_begin;       /* [n_points + 1]: track k owns observations pt_obs_begin[k] .. pt_obs_begin[k + 1] - 1; [0] = 0 */
+    const double *pt_obs;              /* [n_obs][3]: observation k of a track belongs to frame pt_start + k */
+    const int32_t *ln_window;          /* [n_lines], non-decreasing */
+    const int32_t *ln_fi, *ln_fj;      /* [n_lines] frame of the first / of the last observation */
+    const double *ln_sp_i, *ln_ep_i;   /* [n_lines][3] end points of the first observation */
+    const double *ln_sp_j, *ln_ep_j;   /* [n_lines][3] end points of the last observation */
+} uvs_tri_batch;
+
+/* UVS_ERR_INVALID_ARG: null out or a capacity < 1 (max_point_obs < 2); UVS_ERR_CAPACITY: a capacity above its bound. */
+int uvs_tri_create(int device, int max_windows, int max_points, int max_point_obs, int max_lines, uvs_tri **out);
+void uvs_tri_destroy(uvs_tri *t);
+const char *uvs_tri_last_error(const uvs_tri *t);
+/* The init_depth of uvs_tri_shift_depth (uvs_tri_triangulate takes its own as an argument): a setter, not a create argument.  A new
+ * handle holds 5.0, INIT_DEPTH of the reference's configurations.  UVS_ERR_INVALID_ARG unless positive and finite. */
+int uvs_tri_set_init_depth(uvs_tri *t, double init_depth);
+/* One upload, the kernels, one download.  depth[n_points], pt_flag[n_points], orth[n_lines][4], ln_flag[n_lines].  n_points == 0, n_lines == 0
+ * or both are valid (both: UVS_OK with nothing launched; the arrays of an empty kind may be NULL).  Every refusal is UVS_ERR_INVALID_ARG and
+ * happens before anything is launched: a null pointer, a negative count, n_windows < 1, init_depth not positive and finite, a track with
+ * fewer than 2 or more than UVS_NUM_FRAMES views, pt_start < 0 or pt_start + views > UVS_NUM_FRAMES, pt_obs_begin[0] != 0, ln_fi < 0,
+ * ln_fj > UVS_WINDOW_SIZE or ln_fj <= ln_fi, a window index outside 0 .. n_windows - 1 or decreasing, or a count (windows, points,
+ * observations, lines) above the handle's capacity.  A refused call changes nothing and the handle stays usable. */
+int uvs_tri_triangulate(uvs_tri *t, const uvs_tri_batch *batch, double init_depth, double *depth, int32_t *pt_flag, double *orth,
+                        int32_t *ln_flag);
+/* pose / ex_pose / ln_window as in uvs_tri_batch; ln_start[n_lines] in 0 .. UVS_WINDOW_SIZE; ln_sp0 / ln_ep0 [n_lines][3] the first
+ * observation; orth_old[n_lines][4]; flag[n_lines] = 1 (valid) or 2.  n_lines == 0: UVS_OK, nothing launched.  Refusals as above. */
+int uvs_tri_check_lines(uvs_tri *t, int n_windows, const double *pose, const double *ex_pose, int n_lines, const int32_t *ln_window,
+                        const int32_t *ln_start, const double *ln_sp0, const double *ln_ep0, const double *orth_old, int32_t *flag);
+/* uv0[n_points][3], depth[n_points]; marg_R / new_R [3][3] row-major, marg_P / new_P [3]: the camera poses of the departed and of the new
+ * oldest frame.  depth_out[n_points], flag[n_points].  n_points == 0: UVS_OK, nothing launched.  Refusals as above. */
+int uvs_tri_shift_depth(uvs_tri *t, int n_points, const double *uv0, const double *depth, const double *marg_R, const double *marg_P,
+                        const double *new_R, const double *new_P, double *depth_out, int32_t *flag);
+/* HIP-event time of the kernels of the last successful call on the handle's stream, upload and download excluded (milliseconds). */
+double uvs_tri_last_device_ms(const uvs_tri *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -949,3 +949,35 @@ def pr_frames(frames):
     if len(desc) == 0:
         desc = np.zeros((1, 4), np.uint64)
     return nf, desc
+
+
+# ---- triangulation of landmarks (uvs_tri_*, include/uvs_solver.h) ------------------------------------------------
+TRI_MAX_WINDOWS = 4096
+TRI_MAX_LANDMARKS = 1 << 22
+TRI_POINT_FIELDS = ("pt_window", "pt_start", "pt_obs_begin", "pt_obs")
+TRI_LINE_FIELDS = ("ln_window", "ln_fi", "ln_fj", "ln_sp_i", "ln_ep_i", "ln_sp_j", "ln_ep_j")
+
+
+class TriBatch(C.Structure):
+    _fields_ = [("n_windows", C.c_int32), ("n_points", C.c_int32), ("n_lines", C.c_int32), ("reserved", C.c_int32),
+                ("pose", c_double_p), ("ex_pose", c_double_p),
+                ("pt_window", c_i32_p), ("pt_start", c_i32_p), ("pt_obs_begin", c_i32_p), ("pt_obs", c_double_p),
+                ("ln_window", c_i32_p), ("ln_fi", c_i32_p), ("ln_fj", c_i32_p),
+                ("ln_sp_i", c_double_p), ("ln_ep_i", c_double_p), ("ln_sp_j", c_double_p), ("ln_ep_j", c_double_p)]
+
+
+def tri_batch(batch, null=()):
+    """(TriBatch, keepalive) from a dict with the fields of uvs_tri_batch as arrays: pose [n_windows, 11, 7], ex_pose [n_windows, 7] and
+    TRI_POINT_FIELDS / TRI_LINE_FIELDS (a kind that is absent or empty passes a count of 0).  `null` names fields passed as NULL."""
+    b = TriBatch(); keep = {}
+    keep["pose"] = np.ascontiguousarray(batch["pose"], np.float64).reshape(-1, NUM_FRAMES, 7)
+    keep["ex_pose"] = np.ascontiguousarray(batch["ex_pose"], np.float64).reshape(-1, 7)
+    b.n_windows = len(keep["pose"])
+    for name in TRI_POINT_FIELDS + TRI_LINE_FIELDS:
+        dt = np.float64 if name in ("pt_obs", "ln_sp_i", "ln_ep_i", "ln_sp_j", "ln_ep_j") else np.int32
+        keep[name] = np.ascontiguousarray(batch.get(name, np.zeros(0)), dt)
+    b.n_points = len(keep["pt_window"]); b.n_lines = len(keep["ln_window"])
+    for name, a in keep.items():
+        if name not in null and a.size:
+            setattr(b, name, a.ctypes.data_as(c_double_p if a.dtype == np.float64 else c_i32_p))
+    return b, keep

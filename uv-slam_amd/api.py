@@ -34,6 +34,8 @@ EXPORTS = [
     "uvs_ft_set_camera_model", "uvs_kf_set_camera_model", "uvs_ft_lift", "uvs_ft_project", "uvs_lt_set_undistort_model",
     "uvs_pr_check_vocabulary", "uvs_pr_create", "uvs_pr_destroy", "uvs_pr_last_error", "uvs_pr_size", "uvs_pr_clear", "uvs_pr_transform", "uvs_pr_add",
     "uvs_pr_query", "uvs_pr_detect", "uvs_pr_last_device_ms",
+    "uvs_tri_create", "uvs_tri_destroy", "uvs_tri_last_error", "uvs_tri_set_init_depth", "uvs_tri_triangulate", "uvs_tri_check_lines", "uvs_tri_shift_depth",
+    "uvs_tri_last_device_ms",
 ]
 
 
@@ -205,6 +207,17 @@ def lib():
         L.uvs_pr_detect.argtypes = [C.c_void_p, C.c_int, abi.c_u64_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_i32_p, abi.c_double_p]
         L.uvs_pr_detect.restype = C.c_int
         L.uvs_pr_last_device_ms.argtypes = [C.c_void_p, C.c_int]; L.uvs_pr_last_device_ms.restype = C.c_double
+        L.uvs_tri_create.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_void_p)]; L.uvs_tri_create.restype = C.c_int
+        L.uvs_tri_destroy.argtypes = [C.c_void_p]; L.uvs_tri_destroy.restype = None
+        L.uvs_tri_last_error.argtypes = [C.c_void_p]; L.uvs_tri_last_error.restype = C.c_char_p
+        L.uvs_tri_set_init_depth.argtypes = [C.c_void_p, C.c_double]; L.uvs_tri_set_init_depth.restype = C.c_int
+        L.uvs_tri_triangulate.argtypes = [C.c_void_p, C.POINTER(abi.TriBatch), C.c_double, abi.c_double_p, abi.c_i32_p, abi.c_double_p, abi.c_i32_p]
+        L.uvs_tri_triangulate.restype = C.c_int
+        L.uvs_tri_check_lines.argtypes = [C.c_void_p, C.c_int, abi.c_double_p, abi.c_double_p, C.c_int, abi.c_i32_p, abi.c_i32_p, abi.c_double_p, abi.c_double_p,
+                                          abi.c_double_p, abi.c_i32_p]
+        L.uvs_tri_check_lines.restype = C.c_int
+        L.uvs_tri_shift_depth.argtypes = [C.c_void_p, C.c_int] + [abi.c_double_p] * 7 + [abi.c_i32_p]; L.uvs_tri_shift_depth.restype = C.c_int
+        L.uvs_tri_last_device_ms.argtypes = [C.c_void_p]; L.uvs_tri_last_device_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -1481,3 +1494,135 @@ class PlaceRecognizer(_Handle):
         self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call
         self._check("uvs_pr_detect", rc)
         return int(loop.value), ids[:nres.value].copy(), sc[:nres.value].copy()
+
+
+class Triangulator(_Handle):
+    """Owns one `uvs_tri` handle: the state a solve starts from -- FeatureManager::triangulate, triangulateLine, the validity rule of setLineOrtho
+    and the re-anchoring of removeBackShiftDepth -- for whole batches of landmarks on one GPU, one lane per landmark.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    _UNIT = "uvs_tri"
+    INIT_DEPTH = 5.0
+
+    def __init__(self, device=0, max_windows=256, max_points=40000, max_point_obs=None, max_lines=10000, init_depth=None):
+        self._create(device, max_windows, max_points, max_points * abi.NUM_FRAMES if max_point_obs is None else max_point_obs, max_lines)
+        self.init_depth = self.INIT_DEPTH if init_depth is None else float(init_depth)
+        self.set_init_depth(self.init_depth)
+
+    def set_init_depth_raw(self, init_depth):
+        return lib().uvs_tri_set_init_depth(self._h, float(init_depth))
+
+    def set_init_depth(self, init_depth):
+        """The depth uvs_tri_shift_depth falls back to, and the default of triangulate()."""
+        rc = self.set_init_depth_raw(init_depth)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_tri_set_init_depth", rc)
+        self.init_depth = float(init_depth)
+
+    def _timed(self, fn, *args):
+        t0 = time.perf_counter()
+        rc = fn(self._h, *args)
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: packing, upload, kernels, download
+        self.last_device_ms = float(lib().uvs_tri_last_device_ms(self._h))      # HIP events around the kernels alone
+        return rc
+
+    def triangulate_raw(self, batch, init_depth=None, null=(), n_windows=None):
+        """-> (return code, depth, pt_flag, orth, ln_flag) without raising: for the tests of the argument checks.  `null` names batch fields or
+        outputs ("depth", "pt_flag", "orth", "ln_flag") passed as NULL, or "batch"; n_windows overrides the count passed."""
+        b, keep = abi.tri_batch(batch, null)
+        if n_windows is not None:
+            b.n_windows = int(n_windows)
+        depth = np.zeros(max(b.n_points, 1)); pf = np.full(max(b.n_points, 1), -1, np.int32)
+        orth = np.zeros((max(b.n_lines, 1), 4)); lf = np.full(max(b.n_lines, 1), -1, np.int32)
+        out = dict(depth=abi._dp(depth), pt_flag=pf.ctypes.data_as(abi.c_i32_p), orth=abi._dp(orth), ln_flag=lf.ctypes.data_as(abi.c_i32_p))
+        for k in null:
+            if k in out:
+                out[k] = None
+        rc = self._timed(lib().uvs_tri_triangulate, None if "batch" in null else C.byref(b), self.init_depth if init_depth is None else float(init_depth),
+                         out["depth"], out["pt_flag"], out["orth"], out["ln_flag"])
+        return rc, depth[:b.n_points], pf[:b.n_points], orth[:b.n_lines], lf[:b.n_lines]
+
+    def triangulate(self, batch, init_depth=None):
+        """batch: a dict with the fields of uvs_tri_batch as arrays (abi.tri_batch) -> (depth [n_points], pt_flag, orth [n_lines, 4], ln_flag).
+        pt_flag 0 kept / 1 below 0.1 / 2 not finite (1, 2: init_depth returned); ln_flag 0 ok / 2 degenerate (four zeros returned)."""
+        rc, depth, pf, orth, lf = self.triangulate_raw(batch, init_depth)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_tri_triangulate", rc)
+        return depth, pf, orth, lf
+
+    def check_lines_raw(self, pose, ex_pose, ln_window, ln_start, ln_sp0, ln_ep0, orth_old):
+        f64 = lambda a, *shape: np.ascontiguousarray(a, np.float64).reshape(*shape)
+        pose, ex = f64(pose, -1, abi.NUM_FRAMES, 7), f64(ex_pose, -1, 7)
+        win, start = np.ascontiguousarray(ln_window, np.int32), np.ascontiguousarray(ln_start, np.int32)
+        sp, ep, old = f64(ln_sp0, -1, 3), f64(ln_ep0, -1, 3), f64(orth_old, -1, 4)
+        n = len(win)
+        flag = np.full(max(n, 1), -1, np.int32)
+        ip = lambda a: a.ctypes.data_as(abi.c_i32_p)
+        rc = self._timed(lib().uvs_tri_check_lines, len(pose), abi._dp(pose), abi._dp(ex), n, ip(win), ip(start), abi._dp(sp), abi._dp(ep), abi._dp(old), ip(flag))
+        return rc, flag[:n]
+
+    def check_lines(self, pose, ex_pose, ln_window, ln_start, ln_sp0, ln_ep0, orth_old):
+        """The decision of setLineOrtho with the OLD parameters -> flag [n_lines]: 1 valid, 2 an end point behind the start camera."""
+        rc, flag = self.check_lines_raw(pose, ex_pose, ln_window, ln_start, ln_sp0, ln_ep0, orth_old)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_tri_check_lines", rc)
+        return flag
+
+    def shift_depth_raw(self, uv0, depth, marg_R, marg_P, new_R, new_P):
+        f64 = lambda a, *shape: np.ascontiguousarray(a, np.float64).reshape(*shape)
+        uv0, depth = f64(uv0, -1, 3), f64(depth, -1)
+        mR, mP, nR, nP = f64(marg_R, 3, 3), f64(marg_P, 3), f64(new_R, 3, 3), f64(new_P, 3)
+        n = len(depth)
+        out = np.zeros(max(n, 1)); flag = np.full(max(n, 1), -1, np.int32)
+        rc = self._timed(lib().uvs_tri_shift_depth, n, abi._dp(uv0), abi._dp(depth), abi._dp(mR), abi._dp(mP), abi._dp(nR), abi._dp(nP), abi._dp(out),
+                         flag.ctypes.data_as(abi.c_i32_p))
+        return rc, out[:n], flag[:n]
+
+    def shift_depth(self, uv0, depth, marg_R, marg_P, new_R, new_P):
+        """The re-anchoring of removeBackShiftDepth -> (depth_out [n], flag [n]: 0, or 1 where init_depth was put)."""
+        rc, out, flag = self.shift_depth_raw(uv0, depth, marg_R, marg_P, new_R, new_P)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_tri_shift_depth", rc)
+        return out, flag
+
+    @staticmethod
+    def tracks_of(windows):
+        """The batch dict of a list of abi.Window: a point's track is the anchor's pts_i, then each pts_j, of its observations in order (they must
+        lie in consecutive frames from pt_fi on); a line's two views are the first and the last of its observations."""
+        b = dict(pose=np.stack([w.pose for w in windows]), ex_pose=np.stack([w.ex_pose for w in windows]))
+        pw, ps, pn, po, lw, lfi, lfj, ends = [], [], [], [], [], [], [], [[], [], [], []]
+        for wi, w in enumerate(windows):
+            order = np.argsort(w.pt_lm, kind="stable")
+            lm = np.asarray(w.pt_lm)[order]
+            first = np.flatnonzero(np.r_[True, lm[1:] != lm[:-1]]); count = np.diff(np.r_[first, len(lm)])
+            if len(first) != len(w.inv_depth) or (len(lm) and not np.array_equal(lm[first], np.arange(len(first)))):
+                raise ValueError("triangulate_windows: every point needs at least one observation")
+            k_in_track = np.arange(len(lm)) - np.repeat(first, count)
+            if np.any(np.asarray(w.pt_fj)[order] != np.asarray(w.pt_fi)[order] + 1 + k_in_track):
+                raise ValueError("triangulate_windows: a point's observations must lie in consecutive frames after its start frame")
+            pw += [wi] * len(first); ps += list(np.asarray(w.pt_fi)[order][first]); pn += list(count + 1)
+            for f, c in zip(first, count):
+                po.append(np.asarray(w.pt_pi)[order[f]][None]); po.append(np.asarray(w.pt_pj)[order[f:f + c]])
+            order = np.argsort(w.ln_lm, kind="stable")
+            lm = np.asarray(w.ln_lm)[order]
+            first = np.flatnonzero(np.r_[True, lm[1:] != lm[:-1]]); last = np.r_[first[1:], len(lm)] - 1
+            if len(first) != len(w.line_orth) or (len(lm) and not np.array_equal(lm[first], np.arange(len(first)))):
+                raise ValueError("triangulate_windows: every line needs at least one observation")
+            a, z = order[first], order[last]
+            lw += [wi] * len(first); lfi += list(np.asarray(w.ln_fj)[a]); lfj += list(np.asarray(w.ln_fj)[z])
+            for dst, src in zip(ends, (w.ln_sp[a], w.ln_ep[a], w.ln_sp[z], w.ln_ep[z])):
+                dst.append(np.asarray(src).reshape(-1, 3))
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros((0, 3))
+        b.update(pt_window=np.array(pw, np.int32), pt_start=np.array(ps, np.int32), pt_obs_begin=np.r_[0, np.cumsum(pn)].astype(np.int32), pt_obs=cat(po),
+                 ln_window=np.array(lw, np.int32), ln_fi=np.array(lfi, np.int32), ln_fj=np.array(lfj, np.int32),
+                 ln_sp_i=cat(ends[0]), ln_ep_i=cat(ends[1]), ln_sp_j=cat(ends[2]), ln_ep_j=cat(ends[3]))
+        return b
+
+    def triangulate_windows(self, windows, init_depth=None):
+        """Every landmark of every window in one call -> (inv_depth: list of [n_points] arrays, line_orth: list of [n_lines, 4] arrays, pt_flag,
+        ln_flag), ready to be put into the windows that go to the batch or the large-window entry points."""
+        b = self.tracks_of(windows)
+        depth, pf, orth, lf = self.triangulate(b, init_depth)
+        pcut = np.cumsum([len(w.inv_depth) for w in windows])[:-1]; lcut = np.cumsum([len(w.line_orth) for w in windows])[:-1]
+        return np.split(1.0 / depth, pcut), np.split(orth, lcut), np.split(pf, pcut), np.split(lf, lcut)

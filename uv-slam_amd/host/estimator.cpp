@@ -37,7 +37,18 @@ Estimator::Estimator() : frame_count(0), first_imu(false), sum_of_back(0), sum_o
 Estimator::~Estimator() {
     if (eval_solver) { if (uvs::evaluation_solver() == eval_solver) uvs::set_evaluation_solver(nullptr); uvs_destroy(eval_solver); }
     finishMarginalization();
+    setDeviceTriangulation(false);
     uvs_destroy(solver); delete last_marginalization_info; for (auto* p : pre_integrations) delete p;
+}
+
+void Estimator::setDeviceTriangulation(bool on) {
+    if (on == (tri != nullptr)) return;
+    if (!on) { f_manager.tri = nullptr; uvs_tri_destroy(tri); tri = nullptr; return; }
+    if (!uvs_tri_create) throw std::runtime_error("setDeviceTriangulation: this back end has no uvs_tri_*");
+    int rc = uvs_tri_create(0, 1, NUM_OF_F, NUM_OF_F * (WINDOW_SIZE + 1), NUM_OF_LF, &tri);
+    if (rc == UVS_OK && (rc = uvs_tri_set_init_depth(tri, INIT_DEPTH)) != UVS_OK) { uvs_tri_destroy(tri); tri = nullptr; }
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_tri_create: ") + uvs_status_string(rc));     // no CPU fallback once asked for
+    f_manager.tri = tri;
 }
 
 // ---- small helpers of this file: a 7-double parameter block (px py pz qx qy qz qw, estimator.cpp:530-537) <-> (translation, rotation)

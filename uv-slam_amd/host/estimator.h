@@ -97,6 +97,11 @@ class Estimator {
     uvs_solver* eval_solver;     // second, small handle for the factor classes' per-block Evaluate() (registered with uvs::set_evaluation_solver unless one is registered already)
     uvs::Summary last_summary;   // kept for diagnostics (the reference discards ceres::Solver::Summary)
     uvs::SolverPath solver_path = uvs::AUTO;      // which single-window form optimization() calls (window_assembly.h)
+    // Triangulation on the device (uvs_tri_*): OFF by default -- f_manager then runs the host loops it always ran.  On: the estimator owns a uvs_tri handle
+    // (one window, NUM_OF_F points, NUM_OF_LF lines, init_depth = INIT_DEPTH) and f_manager makes one device call per triangulate / triangulateLine /
+    // setLineOrtho / removeBackShiftDepth.  Throws when the handle cannot be made (no GPU, or a back end without uvs_tri_*).
+    void setDeviceTriangulation(bool on);
+    uvs_tri* tri = nullptr;
     // wall-clock spent inside optimization() (sums over the calls): whole call, uvs::Solve() alone, marginalization alone
     double optimization_ms = 0, solve_ms = 0, marginalize_ms = 0; int optimization_calls = 0;
 };

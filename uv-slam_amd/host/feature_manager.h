@@ -10,9 +10,23 @@
 #include <cmath>
 #include <list>
 #include <map>
+#include <stdexcept>
+#include <string>
 #include <vector>
 #include "parameters.h"
 #include "utility.h"
+#include "../../include/uvs_solver.h"
+
+// The device route below (uvs_tri_*, csrc/uvs_triangulate.hip) is taken only by a FeatureManager that was handed a handle.  Its calls are weak
+// references, so that a build of this mirror against a back end without them (the CPU oracle of oracle/Makefile) still links and loads;
+// Estimator::setDeviceTriangulation refuses to make a handle there.
+#pragma weak uvs_tri_create
+#pragma weak uvs_tri_destroy
+#pragma weak uvs_tri_last_error
+#pragma weak uvs_tri_set_init_depth
+#pragma weak uvs_tri_triangulate
+#pragma weak uvs_tri_check_lines
+#pragma weak uvs_tri_shift_depth
 
 class FeaturePerFrame {      // feature_manager.h:18-43: point = normalised (x, y, 1), uv = pixel, velocity = image-plane velocity, cur_td = td at capture
   public:
@@ -66,12 +80,17 @@ class FeatureManager {
     std::list<FeaturePerId> feature;
     std::list<LineFeaturePerId> line_feature;
     const Eigen::Matrix3d* Rs = nullptr;            // the estimator's Rs[] (feature_manager.h: `const Matrix3d *Rs`, set by the constructor)
+    // Optional device route (Estimator::setDeviceTriangulation owns the handle): when set, triangulate, triangulateLine, the flag decision of
+    // setLineOrtho and the depth update of removeBackShiftDepth gather their landmarks into flat arrays, make ONE uvs_tri_* call each and
+    // scatter the results; selection and list surgery stay the code below.  Null (the default): every member runs its host loop.
+    uvs_tri* tri = nullptr;
     FeatureManager() {}
     explicit FeatureManager(Eigen::Matrix3d _Rs[]) : Rs(_Rs) {}
 
     // feature_manager.cpp:427-481 -- linear (DLT) triangulation of every used point that has no depth yet, in its start frame
     void triangulate(Eigen::Vector3d Ps[], Eigen::Vector3d tic[], Eigen::Matrix3d ric[]) {
         using namespace Eigen;
+        if (tri) { triangulateOnDevice(Ps, tic[0], ric[0]); return; }
         for (auto& it : feature) {
             if (!usedPoint(it)) continue;
             if (it.estimated_depth > 0) continue;
@@ -128,6 +147,7 @@ class FeatureManager {
     // (orthonormal_vec[3] == 0).  The reference's cv::Mat argument only feeds a debug drawing and is dropped.
     void triangulateLine(Eigen::Vector3d Ps[], Eigen::Matrix3d /*Rs_estimate*/[], Eigen::Vector3d tic[], Eigen::Matrix3d ric[]) {
         using namespace Eigen;
+        if (tri) { triangulateLineOnDevice(Ps, tic[0], ric[0]); return; }
         for (auto& it : line_feature) {
             it.used_num = (int)it.line_feature_per_frame.size();
             if (it.orthonormal_vec[3] != 0 || it.line_feature_per_frame.size() < 2) continue;
@@ -228,6 +248,7 @@ class FeatureManager {
     // :607-645 -- after initialization a point's depth lives in its anchor camera: moving the anchor re-expresses it in the next view's
     // camera (camera poses of the departed / new oldest frame given), falling back to INIT_DEPTH when it lands behind that camera
     void removeBackShiftDepth(const Eigen::Matrix3d& marg_R, const Eigen::Vector3d& marg_P, const Eigen::Matrix3d& new_R, const Eigen::Vector3d& new_P) {
+        if (tri) { shiftDepthOnDevice(marg_R, marg_P, new_R, new_P); return; }
         oldestFrameLeft(feature, 2, [&](FeaturePerId& t, const FeaturePerFrame& lost) {
             const Eigen::Vector3d in_world = marg_R * (lost.point * t.estimated_depth) + marg_P;
             const double depth = (new_R.transpose() * (in_world - new_P))(2);
@@ -254,6 +275,7 @@ class FeatureManager {
     // setLineOrtho (:333-423): the endpoint-depth validity test uses the PRE-update orthonormal_vec with the post-update poses (Appendix D11)
     void setLineOrtho(std::vector<Eigen::Vector4d>& ortho, Eigen::Vector3d Ps[], Eigen::Matrix3d Rs[], Eigen::Vector3d tic, Eigen::Matrix3d ric) {
         using namespace Eigen;
+        if (tri) { setLineOrthoOnDevice(ortho, Ps, Rs, tic, ric); return; }
         int idx = -1;
         for (auto& it : line_feature) {
             if (!usedLine(it)) continue;
@@ -277,5 +299,95 @@ class FeatureManager {
             it.solve_flag = 1;
             it.orthonormal_vec = ortho.at(idx);
         }
+    }
+
+    // ---------------------------------------------------------------- the device route (tri != nullptr)
+  private:
+    void deviceFailed(const char* call, int rc) const {
+        throw std::runtime_error(std::string(call) + ": " + uvs_status_string(rc) + " / " + uvs_tri_last_error(tri));
+    }
+    // the window's frames as uvs_window states them: pose[11][7] = (p, q xyzw), ex_pose[7]
+    struct DeviceFrames { double pose[WINDOW_SIZE + 1][7], ex[7]; };
+    static void putPose(double* blk, const Eigen::Vector3d& t, const Eigen::Matrix3d& R) {
+        const Eigen::Quaterniond q(R);
+        const double v[7] = {t.x(), t.y(), t.z(), q.x(), q.y(), q.z(), q.w()};
+        std::copy(v, v + 7, blk);
+    }
+    static DeviceFrames deviceFrames(const Eigen::Vector3d Ps[], const Eigen::Matrix3d Rs_[], const Eigen::Vector3d& tic, const Eigen::Matrix3d& ric) {
+        DeviceFrames f;
+        for (int i = 0; i <= WINDOW_SIZE; ++i) putPose(f.pose[i], Ps[i], Rs_[i]);
+        putPose(f.ex, tic, ric);
+        return f;
+    }
+    static void push3(std::vector<double>& v, const Eigen::Vector3d& a) { v.push_back(a.x()); v.push_back(a.y()); v.push_back(a.z()); }
+
+    void triangulateOnDevice(const Eigen::Vector3d Ps[], const Eigen::Vector3d& tic, const Eigen::Matrix3d& ric) {
+        std::vector<FeaturePerId*> todo; std::vector<int32_t> window, start, begin(1, 0); std::vector<double> obs;
+        for (auto& it : feature) {
+            if (!usedPoint(it)) continue;
+            if (it.estimated_depth > 0) continue;
+            todo.push_back(&it); window.push_back(0); start.push_back(it.start_frame);
+            for (auto& pf : it.feature_per_frame) push3(obs, pf.point);
+            begin.push_back((int32_t)(obs.size() / 3));
+        }
+        if (todo.empty()) return;
+        const DeviceFrames f = deviceFrames(Ps, Rs, tic, ric);
+        uvs_tri_batch b{};
+        b.n_windows = 1; b.n_points = (int32_t)todo.size(); b.pose = &f.pose[0][0]; b.ex_pose = f.ex;
+        b.pt_window = window.data(); b.pt_start = start.data(); b.pt_obs_begin = begin.data(); b.pt_obs = obs.data();
+        std::vector<double> depth(todo.size()); std::vector<int32_t> flag(todo.size());
+        const int rc = uvs_tri_triangulate(tri, &b, INIT_DEPTH, depth.data(), flag.data(), nullptr, nullptr);
+        if (rc != UVS_OK) deviceFailed("uvs_tri_triangulate", rc);
+        for (std::size_t k = 0; k < todo.size(); ++k) todo[k]->estimated_depth = depth[k];
+    }
+
+    void triangulateLineOnDevice(const Eigen::Vector3d Ps[], const Eigen::Vector3d& tic, const Eigen::Matrix3d& ric) {
+        std::vector<LineFeaturePerId*> todo; std::vector<int32_t> window, fi, fj; std::vector<double> sp_i, ep_i, sp_j, ep_j;
+        for (auto& it : line_feature) {
+            it.used_num = (int)it.line_feature_per_frame.size();
+            if (it.orthonormal_vec[3] != 0 || it.line_feature_per_frame.size() < 2) continue;
+            todo.push_back(&it); window.push_back(0); fi.push_back(it.start_frame); fj.push_back(it.start_frame + it.used_num - 1);
+            push3(sp_i, it.line_feature_per_frame.front().start_point); push3(ep_i, it.line_feature_per_frame.front().end_point);
+            push3(sp_j, it.line_feature_per_frame.back().start_point); push3(ep_j, it.line_feature_per_frame.back().end_point);
+        }
+        if (todo.empty()) return;
+        const DeviceFrames f = deviceFrames(Ps, Rs, tic, ric);
+        uvs_tri_batch b{};
+        b.n_windows = 1; b.n_lines = (int32_t)todo.size(); b.pose = &f.pose[0][0]; b.ex_pose = f.ex;
+        b.ln_window = window.data(); b.ln_fi = fi.data(); b.ln_fj = fj.data();
+        b.ln_sp_i = sp_i.data(); b.ln_ep_i = ep_i.data(); b.ln_sp_j = sp_j.data(); b.ln_ep_j = ep_j.data();
+        std::vector<double> orth(4 * todo.size()); std::vector<int32_t> flag(todo.size());
+        const int rc = uvs_tri_triangulate(tri, &b, INIT_DEPTH, nullptr, nullptr, orth.data(), flag.data());
+        if (rc != UVS_OK) deviceFailed("uvs_tri_triangulate", rc);
+        for (std::size_t k = 0; k < todo.size(); ++k) todo[k]->orthonormal_vec = Eigen::Vector4d(orth[4 * k], orth[4 * k + 1], orth[4 * k + 2], orth[4 * k + 3]);
+    }
+
+    void setLineOrthoOnDevice(std::vector<Eigen::Vector4d>& ortho, Eigen::Vector3d Ps[], Eigen::Matrix3d Rs_[], const Eigen::Vector3d& tic, const Eigen::Matrix3d& ric) {
+        std::vector<LineFeaturePerId*> used; std::vector<int32_t> window, start; std::vector<double> sp, ep, old;
+        for (auto& it : line_feature) {
+            if (!usedLine(it)) continue;
+            used.push_back(&it); window.push_back(0); start.push_back(it.start_frame);
+            push3(sp, it.line_feature_per_frame[0].start_point); push3(ep, it.line_feature_per_frame[0].end_point);
+            for (int q = 0; q < 4; ++q) old.push_back(it.orthonormal_vec(q));
+        }
+        if (used.empty()) return;
+        const DeviceFrames f = deviceFrames(Ps, Rs_, tic, ric);
+        std::vector<int32_t> flag(used.size());
+        const int rc = uvs_tri_check_lines(tri, 1, &f.pose[0][0], f.ex, (int)used.size(), window.data(), start.data(), sp.data(), ep.data(), old.data(), flag.data());
+        if (rc != UVS_OK) deviceFailed("uvs_tri_check_lines", rc);
+        for (std::size_t idx = 0; idx < used.size(); ++idx) {
+            used[idx]->solve_flag = flag[idx];
+            if (flag[idx] == 1) used[idx]->orthonormal_vec = ortho.at(idx);
+        }
+    }
+
+    void shiftDepthOnDevice(const Eigen::Matrix3d& marg_R, const Eigen::Vector3d& marg_P, const Eigen::Matrix3d& new_R, const Eigen::Vector3d& new_P) {
+        std::vector<FeaturePerId*> moved; std::vector<double> uv0, depth;      // std::list: erasing other tracks leaves these pointers valid
+        oldestFrameLeft(feature, 2, [&](FeaturePerId& t, const FeaturePerFrame& lost) { moved.push_back(&t); push3(uv0, lost.point); depth.push_back(t.estimated_depth); });
+        if (moved.empty()) return;
+        std::vector<double> out(moved.size()); std::vector<int32_t> flag(moved.size());
+        const int rc = uvs_tri_shift_depth(tri, (int)moved.size(), uv0.data(), depth.data(), &marg_R.m[0][0], marg_P.v, &new_R.m[0][0], new_P.v, out.data(), flag.data());
+        if (rc != UVS_OK) deviceFailed("uvs_tri_shift_depth", rc);
+        for (std::size_t k = 0; k < moved.size(); ++k) moved[k]->estimated_depth = out[k];
     }
 };
