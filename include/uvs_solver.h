@@ -305,7 +305,7 @@ int uvs_evaluate(uvs_solver *s, const uvs_window *w, int robust, uvs_eval *out);
 /* Diagnostic (parity tests only): reduced system of the FIRST LM iteration of `w`:
  * S_lower[176*176] row-major = damped, landmark-Schur-reduced frame system in the padded index space
  * (16*frame + dof, dof 15 = dummy pivot), g/hd/dd/step[176], scal[UVS_DEBUG_SCAL_LEN] = {cost, gmax, chol_ok, model_cost_change,
- * step_norm^2, -, -, -, per-phase shader cycles[16], sub-timers[8], -...}: the caller's buffer must hold UVS_DEBUG_SCAL_LEN doubles. */
+ * step_norm^2, line chunks whose pass A ran under the previous gather walk, full linearizations (both counted over the whole solve), -, per-phase shader cycles[16], sub-timers[8], -...}: the caller's buffer must hold UVS_DEBUG_SCAL_LEN doubles. */
 #define UVS_DEBUG_SCAL_LEN 40
 int uvs_debug_first_iteration(uvs_solver *s, const uvs_window *w, double *S_lower, double *g, double *hd, double *dd,
                               double *step, double *scal);

@@ -145,6 +145,36 @@ struct DevWin {
     int32_t redamp_ok;                // 1: k_solve may re-damp the last linearization after a rejected step instead of linearizing again (no pseudo-frame blocks; every line chunk has room for the tables)
 };
 
+// ---- the staging area of one landmark chunk (doubles from the start of the S region), and where a LINE chunk's records may go instead of offset 0.
+// A staged chunk is  records | E | Y (points: E | E / h_ll) | X (lines: 20 per landmark) | gather lists (int32) ; uvs_chunk_end = the doubles it occupies.
+#if defined(__HIPCC__)
+#define UVS_LAYOUT_HD __host__ __device__ inline
+#else
+#define UVS_LAYOUT_HD inline
+#endif
+UVS_LAYOUT_HD int uvs_chunk_end(int type, int nob, int nlm, int nlist, int pt_rec, int pt_xslots) {
+    const int body = type == 0 ? nob * pt_rec + (nob + pt_xslots * nlm) * 12 : nob * (UVS_LN_REC + 2 * UVS_LN_EY) + 20 * nlm;
+    return body + (nlist + 1) / 2;
+}
+// 512-thread solve kernel: pass A of the NEXT chunk (a line chunk) runs while the gather walk of the CURRENT chunk still reads the staging area, if its
+// records -- and only they: its E, Y, X and lists keep the offsets the host's gather lists name -- find a place that intersects
+//   * nothing the current walk reads: the current chunk's records [cur_rec_base, + cur_rec_size) and the rest of it, [cur_rec_size, cur_end) when its own
+//     records were moved (cur_rec_base > 0: a line chunk), all of [0, cur_end) otherwise;
+//   * nothing of the next chunk itself at its nominal place, [next records' size, next_end), which is filled while the records are still read.
+// Two candidates: offset 0 (free when the current chunk's records sit high and the next has no more records than the current had) and the first even offset
+// behind both chunks.  -> the record base of the next chunk, or -1: it does not fit (or the next chunk is a point chunk) and the chunk runs in the plain order.
+// With line chunks of equal size after a point chunk the base alternates high, 0, high, ...
+UVS_LAYOUT_HD int uvs_line_ahead_base(int cur_end, int cur_rec_base, int cur_rec_size, int next_type, int next_nob, int next_nlm, int next_nlist) {
+    if (next_type != 1 || next_nob <= 0) return -1;
+    const int nrec = next_nob * UVS_LN_REC;
+    if (cur_rec_base > 0 && nrec <= cur_rec_size && nrec <= cur_rec_base) return 0;
+    const int next_end = uvs_chunk_end(1, next_nob, next_nlm, next_nlist, 0, 0);
+    int hi = cur_end > next_end ? cur_end : next_end;
+    if (cur_rec_base + cur_rec_size > hi) hi = cur_rec_base + cur_rec_size;
+    hi = (hi + 1) & ~1;      // records hold 16-byte rows
+    return hi + nrec <= UVS_S_DOUBLES ? hi : -1;
+}
+
 #define UVS_PH_G0(n) ((((n) * (n)) + 1) & ~1)
 #define UVS_PH_C0(n) (UVS_PH_G0(n) + UVS_MAX_PRIOR_DIM)
 #define UVS_PH_HD(n) (UVS_PH_C0(n) + 8)

@@ -127,6 +127,7 @@ struct KOpts {   // device copy of uvs_options
     int debug;
     long long max_ticks;      // options.max_solver_time_in_seconds in ticks of the 100 MHz wall clock (wall_clock64); 0 = no cap
     int redamp;      // 1 (default): a rejected step is followed by a re-damping of the stored linearization; 0 (UVS_REDAMP=0 at uvs_create): by a new linearization
+    int line_ahead;  // 1 (default): the 512-thread kernel evaluates a line chunk's pass A under the previous chunk's gather walk where the records fit (linearize_roles); 0 (UVS_LINE_AHEAD=0): the plain order
 };
 
 inline namespace UVS_UNIT {      // (every unit has its own copies, filled by its unit_init below)
@@ -1396,8 +1397,9 @@ UVS_DEV void gather_points(int grp, const int* lists, const double* S0, GAcc& A,
 }
 
 // DELTA: as for the points; the gradient rows are one 6-vector per observation at S0 + goff + (E offset - eoff) / 4 (E rows are 24 doubles per observation)
+// roff: where the chunk's records start (uvs_layout.h: uvs_line_ahead_base; a direct entry is the host's o * UVS_LN_REC, relative to it).  The Schur entries are offsets from S0.
 template <bool DELTA = false>
-UVS_DEV void gather_lines(int grp, const int* lists, const double* S0, GAcc& A, int goff = 0, int eoff = 0) {
+UVS_DEV void gather_lines(int grp, const int* lists, const double* S0, GAcc& A, int goff = 0, int eoff = 0, int roff = 0) {
     const int g = (lane_tid() - GT0) / UVS_GLANES, r0 = GR * (lane_tid() % UVS_GLANES);
     const bool on = grp >= 0;
     const bool diag = on && ((grp >> 8) & 1);
@@ -1441,7 +1443,7 @@ UVS_DEV void gather_lines(int grp, const int* lists, const double* S0, GAcc& A, 
         const int e0 = on ? lists[UVS_NGRP + 1 + g] : 0, e1 = on ? lists[UVS_NGRP + 2 + g] : 0;
         gather_walk<1, Ops>(ent, e0, e1,
             [&](int, const int* w, Ops& o) {
-                const double* R = S0 + w[0];
+                const double* R = S0 + roff + w[0];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
 #pragma unroll
@@ -1834,6 +1836,9 @@ UVS_DEV void copy_lists_gatherers(const Ctx& c, const ChunkDesc& d) {
         for (int u = 0; u < LG_UN; ++u) { const int t = tb + u * UVS_GT; if (t < d.nlist) lists[t] = w[u]; }
     }
 }
+// the two pieces of a line chunk's evaluation half (behind chunk_eval)
+UVS_DEV double line_pass_a(const Ctx& c, const ChunkDesc& d, const double* x, const double* line, int rec_base);
+UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base);
 UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const double* invd, const double* line, bool first, double radius) {
     DevWinK& h = *c.hdr;
     double* sh = c.sh;
@@ -1915,15 +1920,29 @@ UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const
             UVS_TLOG(c, 7);
             lacc_add(sh, cost, gmax_lm);
         } else {
-            const int* beg = c.bi + h.i_ln_beg;
-            const int o0 = d.o0, nob = d.nob, o1 = o0 + nob;
-            double* rec = sh + L_S;                                  // [nob][33]
-            double* Eb = rec + (size_t)nob * UVS_LN_REC;             // [nob][UVS_LN_EY]  E[c][a] = (J_l^T J_p)   (24 used, see uvs_layout.h)
-            double* Yb = Eb + (size_t)nob * UVS_LN_EY;               // [nob][UVS_LN_EY]  Y = Hinv E
-            double* Xb = Yb + (size_t)nob * UVS_LN_EY;               // [nlm][20] : Hinv[16], Hinv*g[4]
-            int* lists = (int*)(Xb + 20 * nlm);
-            if (!LISTS_BY_GATHERERS) for (int t = tid; t < nlist; t += ET) lists[t] = glists[t];
-            // pass A
+            if (!LISTS_BY_GATHERERS) { int* lists = chunk_lists(c, d); for (int t = tid; t < nlist; t += ET) lists[t] = glists[t]; }
+            cost = line_pass_a(c, d, x, line, 0);
+            UVS_TLOG(c, 3);
+            __syncthreads();
+            UVS_PROF(c, P_OBS);
+            UVS_TLOG(c, 4);
+            line_pass_b(c, d, first, radius, cost, 0);
+        }
+    }
+}
+// ---- a line chunk's evaluation half in two pieces, so that the 512-thread build can run the first one early (linearize_roles).  rec_base: where the chunk's records
+// go in the staging area (0 = their nominal place; uvs_layout.h: uvs_line_ahead_base); E, Y, X and the lists always sit where the host's gather lists expect them.
+// Pass A: one lane per observation, residual and Jacobians -> the record.  It reads global inputs and x, L_RF, L_EX only -- nothing a previous chunk produces -- and
+// writes nothing but its records; -> this lane's share of the cost.
+UVS_DEV double line_pass_a(const Ctx& c, const ChunkDesc& d, const double* x, const double* line, int rec_base) {
+    DevWinK& h = *c.hdr;
+    const int tid = lane_tid();
+    const double* RF = c.sh + L_RF; const double* ric = c.sh + L_EX; const double* tic = c.sh + L_EX + 9;
+    double cost = 0.0;
+    {
+        {
+            const int k0 = d.k0, o0 = d.o0, o1 = o0 + d.nob;
+            double* rec = c.sh + L_S + rec_base;                     // [nob][UVS_LN_REC]
             const double* ltrig = line_trig_of(c, line);
             for (int o = o0 + tid; o < o1; o += ET) {
                 const int lm = c.bi[h.i_ln_lm + o], fj = c.bi[h.i_ln_fj + o], hv = c.bi[h.i_ln_vp + o];
@@ -1958,10 +1977,25 @@ UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const
                     for (int q = 0; q < 4; ++q) R[UVS_LN_JL + 8 + q] = 0.0;
                 }
             }
-            UVS_TLOG(c, 3);
-            __syncthreads();
-            UVS_PROF(c, P_OBS);
-            UVS_TLOG(c, 4);
+        }
+    }
+    return cost;
+}
+// Passes B1 and B2 (two workgroup barriers: behind B1, behind B2), then the lane's shares into the per-lane accumulators.  Between the barrier that ends pass A
+// and this function nothing is held in registers but `cost`.
+UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base) {
+    DevWinK& h = *c.hdr;
+    double* sh = c.sh;
+    const int tid = lane_tid();
+    double gmax_lm = 0.0;
+    {
+        {
+            const int* beg = c.bi + h.i_ln_beg;
+            const int k0 = d.k0, nlm = d.nlm, o0 = d.o0, nob = d.nob;
+            double* rec = sh + L_S + rec_base;                       // [nob][UVS_LN_REC]
+            double* Eb = sh + L_S + (size_t)nob * UVS_LN_REC;        // [nob][UVS_LN_EY]  E[c][a] = (J_l^T J_p)   (24 used, see uvs_layout.h)
+            double* Yb = Eb + (size_t)nob * UVS_LN_EY;               // [nob][UVS_LN_EY]  Y = Hinv E
+            double* Xb = Yb + (size_t)nob * UVS_LN_EY;               // [nlm][20] : Hinv[16], Hinv*g[4]
             // pass B1: one lane per line: H_ll, g_l, damping, 4x4 inverse
             for (int li = tid; li < nlm; li += ET) {
                 const int k = k0 + li, b0 = beg[k] - o0, b1 = beg[k + 1] - o0;
@@ -2039,7 +2073,8 @@ UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const
     }
 }
 UVS_DEV int chunk_eval_barriers(const ChunkDesc& d) { return d.type == 0 ? 3 : 4; }      // workgroup barriers inside chunk_eval
-UVS_DEV void chunk_gather(const Ctx& c, const ChunkDesc& d, int grp, GAcc& acc) {
+// rec_base: where a line chunk's records sit (line_pass_a; 0 everywhere but in linearize_roles)
+UVS_DEV void chunk_gather(const Ctx& c, const ChunkDesc& d, int grp, GAcc& acc, int rec_base = 0) {
     DevWinK& h = *c.hdr;
     const double* rec = c.sh + L_S;
     const int* lists = chunk_lists(c, d);
@@ -2048,7 +2083,7 @@ UVS_DEV void chunk_gather(const Ctx& c, const ChunkDesc& d, int grp, GAcc& acc) 
         const long long tg0_ = clock64();
         if (h.td_on | h.ex_on) gather_points<true>(grp, lists, rec, acc, 0, h.ex_on != 0); else gather_points<false>(grp, lists, rec, acc);
         if (c.o.debug == 2 && (lane_tid() & 63) == 0) c.sh[L_WPROF + 4 + ((lane_tid() >> 6) & 3)] += (double)(clock64() - tg0_);
-    } else gather_lines(grp, lists, rec, acc);
+    } else gather_lines(grp, lists, rec, acc, 0, 0, rec_base);
     UVS_TLOG(c, 10);
 }
 UVS_DEV void lin_chunk(const Ctx& c, int ch, const double* x, const double* invd, const double* line, bool first, double radius,
@@ -2592,6 +2627,32 @@ UVS_DEV void gacc_load(const Ctx& c, GAcc& A) {
 #pragma unroll
     for (int q = 0; q < GR; ++q) { A.g[q] = W[(6 * GR + q) * UVS_GT]; A.hd[q] = W[(7 * GR + q) * UVS_GT]; }
 }
+// ---- pass A of a line chunk under the previous chunk's gather walk.  The evaluators of chunk t are idle from its last barrier to the entry barrier of chunk t + 1,
+// which waits for the gatherers' walk of chunk t.  Pass A of a line chunk needs nothing that walk produces (line_pass_a), so where its records find a place the walk
+// does not read (uvs_layout.h: uvs_line_ahead_base -- the benchmark's W10-P150-L40 window: behind the chunk, at 12 920, for the first line chunk, at 0 for the second)
+// the evaluators run it at once and enter chunk t + 1 with pass B1.  Both roles decide by the same function of the same workgroup-uniform descriptor words, and the
+// gatherers' code does not change but for the record base they hand to the walk.  Workgroup barriers per chunk (E = evaluators, G = gatherers; every row balances):
+//     chunk, path            E                                                                              G
+//     point                  entry | A | bar | B | bar                                              = 3     entry | lists, anchor pre | bar | anchor pass | bar           = 3
+//     line, plain order      entry | A | bar | B1 | bar | B2 | bar                                  = 4     entry | lists | bar | bar | bar                               = 4
+//     line, pass A ahead     entry | B1 | bar | B2 | bar | bar                                      = 4     entry | lists | bar | bar | bar                               = 4
+//     re-damping (never ahead)  redamp_prep: 2 (point) / 3 (line)                                           redamp_barriers: 2 / 3
+// then, in every row, the gatherers walk and the evaluators go on: to pass A of chunk t + 1 if it runs ahead (no barrier inside), else to chunk_touch (none).  The
+// first chunk of a linearization never runs ahead (nothing walks before it), a re-damping never does.  UVS_LINE_AHEAD=0 (KOpts::line_ahead) and
+// -DUVS_X_NO_LINE_AHEAD (A/B builds) give the plain order everywhere.
+#ifndef UVS_X_NO_LINE_AHEAD
+static constexpr bool LINE_AHEAD = ROLES;
+#else
+static constexpr bool LINE_AHEAD = false;
+#endif
+static constexpr int DBG_N_LIN = 21, DBG_N_AHEAD = 22;      // debug launches, free slots of L_PROF: full linearizations of the solve, line chunks whose pass A ran ahead (DebugOut::scal[6], [5])
+// the record base of chunk `dn` if its pass A may run under the walk of chunk `d`, whose own records sit at rb; else -1
+UVS_DEV int line_ahead_base(const Ctx& c, const ChunkDesc& d, int rb, const ChunkDesc& dn) {
+    if (!LINE_AHEAD || !c.o.line_ahead || dn.type != 1) return -1;
+    DevWinK& h = *c.hdr;
+    const int rsz = d.nob * (d.type == 0 ? h.pt_rec : UVS_LN_REC);
+    return uvs_line_ahead_base(uvs_chunk_end(d.type, d.nob, d.nlm, d.nlist, h.pt_rec, h.pt_xslots), rb, rsz, dn.type, dn.nob, dn.nlm, dn.nlist);
+}
 UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, const double* line, bool first, double radius, int prep_mode, bool redamp) {
     DevWinK& h = *c.hdr;
     const bool ev = role_eval();
@@ -2602,15 +2663,32 @@ UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, 
     ImuN N;
     if (ev) {
         ChunkDesc d = chunk_desc(c, 0);
+        int rb = -1;            // >= 0: chunk ch is a line chunk whose pass A has run under the walk of chunk ch - 1, its records at rb
+        double acost = 0.0;     // ... and this lane's cost share of that pass: the one value that crosses the entry barrier in a register
         for (int ch = 0; ch < h.n_chunks; ++ch) {
             if (redamp) redamp_prep(c, d, radius);
-            else {
+            else if (rb >= 0) {
+                UVS_TLOG(c, 1);
+                __syncthreads();      // the chunk's entry barrier: the previous walk is done, E / Y / X and the lists' places are free; the records are complete
+                UVS_PROF(c, P_GATHER);
+                UVS_TLOG(c, 2);
+                line_pass_b(c, d, first, radius, acost, rb);      // B1 | barrier | B2 | barrier
+                __syncthreads();      // the fourth barrier of a line chunk (the gatherers count four whichever way pass A ran)
+            } else {
                 chunk_eval(c, d, x, invd, line, first, radius);
             }
             if (ch + 1 < h.n_chunks) {
-                d = chunk_desc(c, ch + 1);
+                const ChunkDesc dn = chunk_desc(c, ch + 1);
+                rb = redamp ? -1 : line_ahead_base(c, d, rb > 0 ? rb : 0, dn);
+                d = dn;
+                if (rb >= 0) {      // the gatherers walk chunk ch; nothing they read is written here (uvs_layout.h: uvs_line_ahead_base)
+                    UVS_TLOG(c, 9);
+                    acost = line_pass_a(c, d, x, line, rb);
+                    UVS_TLOG(c, 3);
+                    if (c.o.debug && lane_tid() == 0) c.sh[L_PROF + DBG_N_AHEAD] += 1.0;
+                }
 #ifdef UVS_CHUNK_TOUCH
-                if (!redamp) chunk_touch(c, d, invd, line);
+                else if (!redamp) chunk_touch(c, d, invd, line);
 #endif
             }
         }
@@ -2634,19 +2712,25 @@ UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, 
         GAcc A;
         if (redamp) gacc_load(c, A); else gacc_zero(A);
         ChunkDesc d = chunk_desc(c, 0);
+        int rb = 0;      // where the records of chunk ch sit: the evaluators' rule on the same descriptor words (0: the nominal place, whichever way pass A ran)
         for (int ch = 0; ch < h.n_chunks; ++ch) {
             if (redamp) { role_barriers(redamp_barriers(d)); redamp_gather(c, d, grp, A); }
             else {
-                __syncthreads();      // the chunk's entry barrier: the staging area is free
+                __syncthreads();      // the chunk's entry barrier: the staging area is free (but for the records of a pass A that ran ahead)
                 if (LISTS_BY_GATHERERS) copy_lists_gatherers(c, d);
                 AnchorPre ap; ap.b0 = 0; ap.b1 = 0; ap.sc = 1.0;
                 if (ANCHOR_BY_GATHERERS && d.type == 0) pt_anchor_pre(c, d, first, ap);
-                __syncthreads();      // pass A is done: the records are complete
+                __syncthreads();      // pass A is done: the records are complete (ahead: pass B1 is done)
                 if (ANCHOR_BY_GATHERERS && d.type == 0) pt_anchor_pass(c, d, first, radius, ap);
                 role_barriers(chunk_eval_barriers(d) - 2);
-                chunk_gather(c, d, grp, A);
+                chunk_gather(c, d, grp, A, rb);
             }
-            if (ch + 1 < h.n_chunks) d = chunk_desc(c, ch + 1);
+            if (ch + 1 < h.n_chunks) {
+                const ChunkDesc dn = chunk_desc(c, ch + 1);
+                const int nb = redamp ? -1 : line_ahead_base(c, d, rb, dn);
+                rb = nb > 0 ? nb : 0;
+                d = dn;
+            }
         }
         __syncthreads();      // (lin_imu's entry barrier: every gather walk is done, the staging area is free)
         if (h.redamp_ok && c.o.redamp) gacc_store(c, A);      // per part: a re-damping continues from these
@@ -2676,6 +2760,7 @@ UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, 
 
 // `A`: the gather accumulators, owned by the caller (k_solve keeps them in registers between a linearization and a possible re-damping)
 UVS_DEV void linearize(const Ctx& c, const double* x, const double* invd, const double* line, bool first, double radius, int prep_mode, GAcc& A) {
+    if (c.o.debug && lane_tid() == 0) c.sh[L_PROF + DBG_N_LIN] += 1.0;
     if (ROLES) { linearize_roles(c, x, invd, line, first, radius, prep_mode, false); return; }
     DevWinK& h = *c.hdr;
     const int grp = gather_group(c);       // this lane's gather group: pose block | flags (uvs_layout.h: i_wblk)
@@ -3076,7 +3161,7 @@ struct DebugOut {   // optional dump of the first linearization (uvs_debug_linea
     double* hd;     // [176]
     double* dd;     // [176]
     double* step;   // [176] solution of S y = -g
-    double* scal;   // [UVS_DEBUG_SCAL_LEN]: cost, gmax, chol_ok, mcc, step2, -, -, -, phase cycles [8..23], sub-timers [24..31]
+    double* scal;   // [UVS_DEBUG_SCAL_LEN]: cost, gmax, chol_ok, mcc, step2, line chunks whose pass A ran ahead, full linearizations (both over the whole solve), -, phase cycles [8..23], sub-timers [24..31]
 };
 
 // uvs_debug_step: the step of every LM iteration of window 0 is stored and then handled as a REJECTED one at the caller's next radius (k_solve re-damps
@@ -3253,6 +3338,7 @@ UVS_DEV void k_solve_body(char* blobs, const long long* blob_off, double* ws_all
     UVS_PROF(c, P_MISC);
     if (o.debug && dbg.scal && tid < P_LAST) dbg.scal[8 + tid] = sh[L_PROF + tid];
     if (o.debug && dbg.scal && tid < 8) dbg.scal[24 + tid] = sh[L_WPROF + tid];
+    if (o.debug && dbg.scal && tid == 0) { dbg.scal[5] = sh[L_PROF + DBG_N_AHEAD]; dbg.scal[6] = sh[L_PROF + DBG_N_LIN]; }
     if (tid < UVS_XDIM) c.ws[h.w_out + tid] = sh[L_X + tid];
     // the accepted landmark parameters follow the frames, so that the host fetches ONE small contiguous block per window
     for (int k = tid; k < h.n_points; k += NT) c.ws[h.w_out + UVS_XDIM + k] = invd[cur][k];

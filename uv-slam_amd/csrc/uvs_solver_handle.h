@@ -166,6 +166,7 @@ inline uvsdev::KOpts make_kopts(const uvs_options& o, int debug) {
     k.max_ticks = o.max_solver_time_in_seconds > 0.0 ? std::max(1LL, (long long)(o.max_solver_time_in_seconds * 1e8)) : 0LL;      // wall_clock64(): 100 MHz
     k.max_invalid = o.max_consecutive_invalid_steps; k.debug = debug;
     { const char* e = std::getenv("UVS_REDAMP"); k.redamp = (e && e[0] == '0') ? 0 : 1; }      // diagnostic switch, read per launch (tests, A/B): 0 = re-linearize after every rejected step
+    { const char* e = std::getenv("UVS_LINE_AHEAD"); k.line_ahead = (e && e[0] == '0') ? 0 : 1; }      // diagnostic switch, read per launch (tests, A/B): 0 = no line chunk's pass A runs ahead of its entry barrier
     return k;
 }
 
