@@ -128,6 +128,7 @@ struct KOpts {   // device copy of uvs_options
     long long max_ticks;      // options.max_solver_time_in_seconds in ticks of the 100 MHz wall clock (wall_clock64); 0 = no cap
     int redamp;      // 1 (default): a rejected step is followed by a re-damping of the stored linearization; 0 (UVS_REDAMP=0 at uvs_create): by a new linearization
     int line_ahead;  // 1 (default): the 512-thread kernel evaluates a line chunk's pass A under the previous chunk's gather walk where the records fit (linearize_roles); 0 (UVS_LINE_AHEAD=0): the plain order
+    int line_b1;     // 1 (default): pass B1 of a line chunk and the line half of a re-damping run on eight lanes per line (ln_lanes_solve); 0 (UVS_LINE_B1=0): on one lane per line.  Bitwise the same results
 };
 
 inline namespace UVS_UNIT {      // (every unit has its own copies, filled by its unit_init below)
@@ -1606,30 +1607,101 @@ UVS_DEV double lin_frames(const Ctx& c, const double* x, ImuN& N) { const double
 // Inverse of a damped 4 x 4 line block (lower packed H) through its Cholesky factor, written to X[4][4] (may be LDS), and hg = H^-1 g.
 // One reciprocal square root per pivot (an FP64 division is ~30 instructions; the factor + explicit inverse had 26 of them on ONE lane per
 // line while the other lanes of the workgroup wait): sqrt and reciprocal sqrt together from the hardware seed + FMA-only refinement.
+// Two parts, so that the lane form of a line chunk's pass B1 (ln_lanes_solve) runs the same arithmetic with a column per lane: the factor (L lower packed, inv[p] = 1 / L_pp) ...
+UVS_DEV void spd4_factor(const double* H, double* L, double* inv) {
+    rsqrt_pair(H[0], &L[0], &inv[0]);
+    L[1] = H[1] * inv[0]; rsqrt_pair(H[2] - L[1] * L[1], &L[2], &inv[1]);
+    L[3] = H[3] * inv[0]; L[4] = (H[4] - L[3] * L[1]) * inv[1]; rsqrt_pair(H[5] - L[3] * L[3] - L[4] * L[4], &L[5], &inv[2]);
+    L[6] = H[6] * inv[0]; L[7] = (H[7] - L[6] * L[1]) * inv[1]; L[8] = (H[8] - L[6] * L[3] - L[7] * L[4]) * inv[2];
+    rsqrt_pair(H[9] - L[6] * L[6] - L[7] * L[7] - L[8] * L[8], &L[9], &inv[3]);
+}
+// ... and column cidx of the inverse: e = L^-T L^-1 e_cidx (cidx a constant of an unrolled loop, or the lane's own)
+UVS_DEV void spd4_column(const double* L, const double* inv, int cidx, double* e) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = q == cidx ? 1.0 : 0.0;
+    e[0] = e[0] * inv[0];
+    e[1] = (e[1] - L[1] * e[0]) * inv[1];
+    e[2] = (e[2] - L[3] * e[0] - L[4] * e[1]) * inv[2];
+    e[3] = (e[3] - L[6] * e[0] - L[7] * e[1] - L[8] * e[2]) * inv[3];
+    e[3] = e[3] * inv[3];
+    e[2] = (e[2] - L[8] * e[3]) * inv[2];
+    e[1] = (e[1] - L[4] * e[2] - L[7] * e[3]) * inv[1];
+    e[0] = (e[0] - L[1] * e[1] - L[3] * e[2] - L[6] * e[3]) * inv[0];
+}
 UVS_DEV void spd4_inverse(const double* H, const double* gl, double* X, double* hg) {
-    double L[10];
-    double i0, i1, i2, i3;
-    rsqrt_pair(H[0], &L[0], &i0);
-    L[1] = H[1] * i0; rsqrt_pair(H[2] - L[1] * L[1], &L[2], &i1);
-    L[3] = H[3] * i0; L[4] = (H[4] - L[3] * L[1]) * i1; rsqrt_pair(H[5] - L[3] * L[3] - L[4] * L[4], &L[5], &i2);
-    L[6] = H[6] * i0; L[7] = (H[7] - L[6] * L[1]) * i1; L[8] = (H[8] - L[6] * L[3] - L[7] * L[4]) * i2;
-    rsqrt_pair(H[9] - L[6] * L[6] - L[7] * L[7] - L[8] * L[8], &L[9], &i3);
+    double L[10], inv[4];
+    spd4_factor(H, L, inv);
     hg[0] = 0.0; hg[1] = 0.0; hg[2] = 0.0; hg[3] = 0.0;
 #pragma unroll
     for (int cidx = 0; cidx < 4; ++cidx) {
-        double e[4] = {0, 0, 0, 0}; e[cidx] = 1.0;
-        e[0] = e[0] * i0;
-        e[1] = (e[1] - L[1] * e[0]) * i1;
-        e[2] = (e[2] - L[3] * e[0] - L[4] * e[1]) * i2;
-        e[3] = (e[3] - L[6] * e[0] - L[7] * e[1] - L[8] * e[2]) * i3;
-        e[3] = e[3] * i3;
-        e[2] = (e[2] - L[8] * e[3]) * i2;
-        e[1] = (e[1] - L[4] * e[2] - L[7] * e[3]) * i1;
-        e[0] = (e[0] - L[1] * e[1] - L[3] * e[2] - L[6] * e[3]) * i0;
+        double e[4];
+        spd4_column(L, inv, cidx, e);
         X[0 * 4 + cidx] = e[0]; X[1 * 4 + cidx] = e[1]; X[2 * 4 + cidx] = e[2]; X[3 * 4 + cidx] = e[3];
 #pragma unroll
         for (int a = 0; a < 4; ++a) hg[a] += e[a] * gl[cidx];
     }
+}
+// ---- a line's 4 x 4 block on eight lanes of one wave (KOpts::line_b1; pass B1 of line_pass_b and the line half of redamp_prep).  With one lane per line a chunk of
+// 20 lines keeps 20 lanes of one wave busy for ~840 instructions while every other lane of the workgroup waits at the barrier behind them, and a wave that has its SIMD
+// alone issues one instruction, of whatever kind, per ~8 cycles: what counts is the length of the longest wave's instruction stream.  Lane j of a line's group owns
+//     s0:  j < 4: the diagonal entry H(j, j), then its damping        j >= 4: g_l[j - 4]
+//     s1:  j < 6: the off-diagonal entries (1,0) (2,0) (2,1) (3,0) (3,1) (3,2)        j = 6, 7: (3,0) once more, unused
+// the ten entries and g_l reach lanes 0..3 by DPP moves (no LDS, no wait), each of lanes 0..3 factors the damped block (the same values four times) and solves
+// ONE column of the inverse, and (H^-1 g) is summed over the columns in their order along the lanes 0 -> 3.  Every sum and every value derived from it is computed by
+// the operations of the one-lane form in the same order: both forms agree bitwise (tests/test_gpu_line_b1_lanes.py).
+#ifndef UVS_X_B1_ONE_LANE
+static constexpr bool LINE_B1_LANES = true;
+#else
+static constexpr bool LINE_B1_LANES = false;
+#endif
+static constexpr int LB1_G = 8;                 // lanes per line
+static constexpr int LB1_TRIP = ET / LB1_G;     // lines per trip of the evaluator lanes
+static_assert(64 % LB1_G == 0, "the lanes of a line sit in one wave");
+// x0 y0 + x1 y1 + x2 y2 as the compiler contracts the written sum (left operand of the first addition fused, the right one a product): one term of a sum of H_ll or g_l
+UVS_DEV double ln_term3(double x0, double y0, double x1, double y1, double x2, double y2) { return fma(x2, y2, fma(x0, y0, x1 * y1)); }
+// LM damping of a diagonal entry hd of H_ll under the Jacobi scale sc
+UVS_DEV double ln_damping(const KOpts& o, double sc, double hd, double radius) { return fmin(fmax(sc * sc * hd, o.dlo), o.dhi) / (radius * sc * sc); }
+// lane moves inside a row of 16 lanes, two 32-bit DPP moves per double: no LDS crossbar, no wait
+template <int CTRL> UVS_DEV double dpp_move(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+template <int C> UVS_DEV double quad_lane(double v) { return dpp_move<C * 0x55>(v); }      // quad_perm:[C,C,C,C]: v of lane C of this lane's quad
+UVS_DEV double upper_quad(double v) { return dpp_move<0x104>(v); }                          // row_shl:4: v of lane i + 4 (lanes 0..3 of a line's group: of its lanes 4..7)
+static_assert(LB1_G == 8, "a line's group is two quads of one row of 16 lanes");
+template <int C> UVS_DEV void ln_hg_stage(const double* e, double glc, double* hg) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) hg[a] = quad_lane<C>(hg[a] + e[a] * glc);
+}
+struct LnLane { int j, q0, q1, a1, b1; };      // lane in the group, packed indices of its entries of H (q0: j < 4, q1: j < 6), row and column of the second
+UVS_DEV LnLane ln_lane(int tid) {
+    LnLane l; l.j = tid & (LB1_G - 1);
+    l.q0 = (l.j * (l.j + 3)) >> 1;
+    l.a1 = l.j < 1 ? 1 : l.j < 3 ? 2 : 3; l.b1 = l.j < 6 ? l.j - ((l.a1 * (l.a1 - 1)) >> 1) : 0;
+    l.q1 = ((l.a1 * (l.a1 + 1)) >> 1) + l.b1;
+    return l;
+}
+// In: s0, s1 as above (H undamped), sc on lanes 0..3.  Out: the damping of entry (j, j) on lane j < 4, column j of the inverse in e[0..3] (X[q][j] = e[q]) on lane j < 4, and
+// H^-1 g in hg[0..3] on lane 3.  Every lane of the wave calls it; a group without a line repeats the chunk's last line and stores nothing.
+UVS_DEV void ln_lanes_solve(const KOpts& o, int j, double s0, double s1, double sc, double radius, double* dd, double* e, double* hg) {
+    *dd = ln_damping(o, sc, s0, radius);
+    const double d0 = j < 4 ? s0 + *dd : s0;
+    const double u0 = upper_quad(d0), u1 = upper_quad(s1);      // lanes 0..3: g_l[j], the entries (3,1) and (3,2)
+    double H[10], gl[4];
+    H[0] = quad_lane<0>(d0); H[2] = quad_lane<1>(d0); H[5] = quad_lane<2>(d0); H[9] = quad_lane<3>(d0);
+    gl[0] = quad_lane<0>(u0); gl[1] = quad_lane<1>(u0); gl[2] = quad_lane<2>(u0); gl[3] = quad_lane<3>(u0);
+    H[1] = quad_lane<0>(s1); H[3] = quad_lane<1>(s1); H[4] = quad_lane<2>(s1); H[6] = quad_lane<3>(s1);
+    H[7] = quad_lane<0>(u1); H[8] = quad_lane<1>(u1);
+    double L[10], inv[4];
+    spd4_factor(H, L, inv);
+    spd4_column(L, inv, j & 3, e);
+    // (H^-1 g)_a = sum over the columns c, in their order, of X[a][c] g[c]: the partial sums travel from the lane of column c to the lane of column c + 1.  In stage c
+    // every lane adds its own column's term to what it holds and lane c's result goes to the whole quad, so only the chain 0 -> 1 -> 2 -> 3 survives; it ends on lane 3.
+    hg[0] = 0.0; hg[1] = 0.0; hg[2] = 0.0; hg[3] = 0.0;
+    ln_hg_stage<0>(e, gl[0], hg); ln_hg_stage<1>(e, gl[1], hg); ln_hg_stage<2>(e, gl[2], hg);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) hg[a] += e[a] * gl[3];
 }
 
 // ---- linearization, part 2: one landmark chunk: stage -> per-landmark Schur prep -> list-driven gather into acc[]
@@ -1838,7 +1910,22 @@ UVS_DEV void copy_lists_gatherers(const Ctx& c, const ChunkDesc& d) {
 }
 // the two pieces of a line chunk's evaluation half (behind chunk_eval)
 UVS_DEV double line_pass_a(const Ctx& c, const ChunkDesc& d, const double* x, const double* line, int rec_base);
-UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base);
+// What the first trip of pass B1's lane form reads from global memory: a line's observation range and the Jacobi scale of the lane's diagonal entry.  None of it depends on
+// the chunk's records, so the caller asks for it AHEAD of the workgroup barrier in front of line_pass_b, where it waits anyway, instead of behind it (a round trip per line chunk).
+struct LnB1Pre { int b0, b1; double sc; };
+UVS_DEV LnB1Pre line_b1_preload(const Ctx& c, const ChunkDesc& d, bool first) {
+    LnB1Pre p; p.b0 = 0; p.b1 = 0; p.sc = 1.0;
+    if (LINE_B1_LANES && c.o.line_b1 && d.nlm > 0) {
+        DevWinK& h = *c.hdr;
+        const int tid = lane_tid(), li = tid / LB1_G;
+        const int k = d.k0 + (li < d.nlm ? li : d.nlm - 1);
+        const int* beg = c.bi + h.i_ln_beg;
+        p.b0 = beg[k] - d.o0; p.b1 = beg[k + 1] - d.o0;
+        if (!first) p.sc = c.ws[h.w_scale_ln + 4 * k + (tid & 3)];
+    }
+    return p;
+}
+UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base, const LnB1Pre& pre);
 UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const double* invd, const double* line, bool first, double radius) {
     DevWinK& h = *c.hdr;
     double* sh = c.sh;
@@ -1923,10 +2010,11 @@ UVS_DEV void chunk_eval(const Ctx& c, const ChunkDesc& d, const double* x, const
             if (!LISTS_BY_GATHERERS) { int* lists = chunk_lists(c, d); for (int t = tid; t < nlist; t += ET) lists[t] = glists[t]; }
             cost = line_pass_a(c, d, x, line, 0);
             UVS_TLOG(c, 3);
+            const LnB1Pre pre = line_b1_preload(c, d, first);
             __syncthreads();
             UVS_PROF(c, P_OBS);
             UVS_TLOG(c, 4);
-            line_pass_b(c, d, first, radius, cost, 0);
+            line_pass_b(c, d, first, radius, cost, 0, pre);
         }
     }
 }
@@ -1983,7 +2071,7 @@ UVS_DEV double line_pass_a(const Ctx& c, const ChunkDesc& d, const double* x, co
 }
 // Passes B1 and B2 (two workgroup barriers: behind B1, behind B2), then the lane's shares into the per-lane accumulators.  Between the barrier that ends pass A
 // and this function nothing is held in registers but `cost`.
-UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base) {
+UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double radius, double cost, int rec_base, const LnB1Pre& pre) {
     DevWinK& h = *c.hdr;
     double* sh = c.sh;
     const int tid = lane_tid();
@@ -1996,7 +2084,59 @@ UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double ra
             double* Eb = sh + L_S + (size_t)nob * UVS_LN_REC;        // [nob][UVS_LN_EY]  E[c][a] = (J_l^T J_p)   (24 used, see uvs_layout.h)
             double* Yb = Eb + (size_t)nob * UVS_LN_EY;               // [nob][UVS_LN_EY]  Y = Hinv E
             double* Xb = Yb + (size_t)nob * UVS_LN_EY;               // [nlm][20] : Hinv[16], Hinv*g[4]
-            // pass B1: one lane per line: H_ll, g_l, damping, 4x4 inverse
+            // pass B1: H_ll, g_l, damping, 4x4 inverse.  Eight lanes per line (ln_lanes_solve), the lines dealt over all evaluator lanes ...
+            if (LINE_B1_LANES && c.o.line_b1) {
+                const LnLane l = ln_lane(tid);
+                const int j = l.j;
+                // where the lane's factors sit in a record: s0 = sum x0 y0, s1 = sum x1 y1, three products each at strides (4, ys)
+                const int x0 = UVS_LN_JL + (j & 3), y0 = j < 4 ? x0 : 0, y01 = j < 4 ? x0 + 4 : 1, y02 = j < 4 ? x0 + 8 : UVS_LN_RV;
+                const int x1 = UVS_LN_JL + l.a1, y1 = UVS_LN_JL + l.b1;
+                for (int l0 = 0; l0 < nlm; l0 += LB1_TRIP) {      // (the same trips in every lane: the shuffles run with whole waves)
+                    // A group past the chunk's last line repeats that line and stores nothing: no load and no store sits behind a lane-dependent branch, so the
+                    // three loads below are ONE round trip and every global store comes after the arithmetic (a wait for a load waits for the stores before it too)
+                    const int li = l0 + tid / LB1_G;
+                    const bool on = li < nlm;
+                    const int k = k0 + (on ? li : nlm - 1);
+                    int b0 = pre.b0, b1 = pre.b1;
+                    double sc = pre.sc;      // Jacobi scale of entry (j, j), j < 4: requested before the accumulation loop, used after it
+                    if (l0 > 0) {            // (the first trip's came in over the barrier: line_b1_preload)
+                        b0 = beg[k] - o0; b1 = beg[k + 1] - o0;
+                        if (!first) sc = c.ws[h.w_scale_ln + 4 * k + (j & 3)];
+                    }
+                    double s0 = 0.0, s1 = 0.0;
+                    {      // the observations in the one-lane form's order; one pointer per run of factors, bumped per record
+                        const double* R = rec + (size_t)b0 * UVS_LN_REC;
+                        const double *px0 = R + x0, *py0 = R + y0, *py01 = R + y01, *py02 = R + y02, *px1 = R + x1, *py1 = R + y1;
+                        for (int n = b1 - b0; n > 0; --n) {
+                            s0 += ln_term3(px0[0], py0[0], px0[4], py01[0], px0[8], py02[0]);
+                            s1 += ln_term3(px1[0], py1[0], px1[4], py1[4], px1[8], py1[8]);
+                            px0 += UVS_LN_REC; py0 += UVS_LN_REC; py01 += UVS_LN_REC; py02 += UVS_LN_REC; px1 += UVS_LN_REC; py1 += UVS_LN_REC;
+                        }
+                    }
+                    if (first) sc = c.o.jacobi ? 1.0 / (1.0 + sqrt(s0)) : 1.0;
+                    double dd, e[4], hg[4];
+                    ln_lanes_solve(c.o, j, s0, s1, sc, radius, &dd, e, hg);
+                    double* lx = c.ws + h.w_ln_x + UVS_LN_X * (size_t)k;
+                    gmax_lm = fmax(gmax_lm, j < 4 ? 0.0 : fabs(s0));
+                    if (on) {
+                        lx[j < 4 ? 12 + l.q0 : j] = s0;      // the undamped entry (j, j), what a re-damping after a rejected step starts from | g_l[a] at lx[4 + a], a = j - 4
+                        lx[12 + l.q1] = s1;                  // (lanes 6 and 7 repeat lane 3's sum of entry (3, 0): the same value to the same place)
+                        if (j < 4) {
+                            double* X = Xb + 20 * li;
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) X[4 * q + j] = e[q];
+                            lx[8 + j] = dd;
+                            if (first) c.ws[h.w_scale_ln + 4 * k + j] = sc;
+                        }
+                        if (j == 3) {
+                            double* X = Xb + 20 * li;
+#pragma unroll
+                            for (int a = 0; a < 4; ++a) { X[16 + a] = hg[a]; lx[a] = hg[a]; }
+                        }
+                    }
+                }
+            } else
+            // ... or one lane per line (UVS_LINE_B1=0, -DUVS_X_B1_ONE_LANE)
             for (int li = tid; li < nlm; li += ET) {
                 const int k = k0 + li, b0 = beg[k] - o0, b1 = beg[k + 1] - o0;
                 double H[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, gl[4] = {0, 0, 0, 0};   // lower packed (0,0)(1,0)(1,1)(2,0)...
@@ -2009,9 +2149,9 @@ UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double ra
                     const double* R = rec + (size_t)o * UVS_LN_REC;
 #pragma unroll
                     for (int a = 0; a < 4; ++a) {
-                        gl[a] += R[UVS_LN_JL + a] * R[0] + R[UVS_LN_JL + 4 + a] * R[1] + R[UVS_LN_JL + 8 + a] * R[UVS_LN_RV];
+                        gl[a] += ln_term3(R[UVS_LN_JL + a], R[0], R[UVS_LN_JL + 4 + a], R[1], R[UVS_LN_JL + 8 + a], R[UVS_LN_RV]);
 #pragma unroll
-                        for (int b = 0; b <= a; ++b) H[(a * (a + 1)) / 2 + b] += R[UVS_LN_JL + a] * R[UVS_LN_JL + b] + R[UVS_LN_JL + 4 + a] * R[UVS_LN_JL + 4 + b] + R[UVS_LN_JL + 8 + a] * R[UVS_LN_JL + 8 + b];
+                        for (int b = 0; b <= a; ++b) H[(a * (a + 1)) / 2 + b] += ln_term3(R[UVS_LN_JL + a], R[UVS_LN_JL + b], R[UVS_LN_JL + 4 + a], R[UVS_LN_JL + 4 + b], R[UVS_LN_JL + 8 + a], R[UVS_LN_JL + 8 + b]);
                     }
                 }
                 double* lx = c.ws + h.w_ln_x + UVS_LN_X * (size_t)k;
@@ -2022,7 +2162,7 @@ UVS_DEV void line_pass_b(const Ctx& c, const ChunkDesc& d, bool first, double ra
                     const double hd = H[(a * (a + 1)) / 2 + a];
                     double sc;
                     if (first) { sc = c.o.jacobi ? 1.0 / (1.0 + sqrt(hd)) : 1.0; c.ws[h.w_scale_ln + 4 * k + a] = sc; } else sc = scl[a];
-                    const double dd = fmin(fmax(sc * sc * hd, c.o.dlo), c.o.dhi) / (radius * sc * sc);
+                    const double dd = ln_damping(c.o, sc, hd, radius);
                     H[(a * (a + 1)) / 2 + a] = hd + dd;
                     lx[4 + a] = gl[a]; lx[8 + a] = dd;
                     gmax_lm = fmax(gmax_lm, fabs(gl[a]));
@@ -2161,6 +2301,39 @@ UVS_DEV void redamp_prep(const Ctx& c, const ChunkDesc& d, double radius) {
         double* Xb = Yb + (size_t)nob * UVS_LN_EY;
         int* lists = (int*)(Xb + 20 * nlm);
         for (int t = tid; t < nlist; t += ET) lists[t] = glists[t];
+        // the new damping and inverse of every line: eight lanes per line as in pass B1 (ln_lanes_solve; every lane loads and stores the entries it owns) ...
+        if (LINE_B1_LANES && c.o.line_b1) {
+            const LnLane l = ln_lane(tid);
+            const int j = l.j;
+            for (int l0 = 0; l0 < nlm; l0 += LB1_TRIP) {
+                const int li = l0 + tid / LB1_G;
+                const bool on = li < nlm;
+                const int k = k0 + (on ? li : nlm - 1);      // (a group past the last line repeats it and stores nothing: the loads are one round trip)
+                double* lx = c.ws + h.w_ln_x + UVS_LN_X * (size_t)k;
+                double* t = T + 34 * li;
+                const double s0 = lx[j < 4 ? 12 + l.q0 : j];      // H(j, j) | g_l[j - 4]
+                const double s1 = lx[12 + l.q1];                  // (lanes 6, 7: an entry they do not own, unused)
+                const double sc = c.ws[h.w_scale_ln + 4 * k + (j & 3)], ddo = lx[8 + (j & 3)];
+                double hgo[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) hgo[a] = lx[a];
+                double dd, e[4], hg[4];
+                ln_lanes_solve(c.o, j, s0, s1, sc, radius, &dd, e, hg);
+                if (on) {
+                    if (j < 6) t[20 + l.q1] = s1;
+                    if (j < 4) {
+                        t[20 + l.q0] = s0; t[30 + j] = ddo; lx[8 + j] = dd;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) t[4 * q + j] = e[q];
+                    }
+                    if (j == 3) {
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) { t[16 + a] = hg[a] - hgo[a]; lx[a] = hg[a]; }
+                    }
+                }
+            }
+        } else
+        // ... or one lane per line
         for (int li = tid; li < nlm; li += ET) {
             const int k = k0 + li;
             double* lx = c.ws + h.w_ln_x + UVS_LN_X * (size_t)k;
@@ -2175,7 +2348,7 @@ UVS_DEV void redamp_prep(const Ctx& c, const ChunkDesc& d, double radius) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const double hd = H[(a * (a + 1)) / 2 + a], sc = c.ws[h.w_scale_ln + 4 * k + a];
-                const double dd = fmin(fmax(sc * sc * hd, c.o.dlo), c.o.dhi) / (radius * sc * sc);
+                const double dd = ln_damping(c.o, sc, hd, radius);
                 H[(a * (a + 1)) / 2 + a] = hd + dd;
                 t[30 + a] = ddo[a]; lx[8 + a] = dd;
             }
@@ -2640,6 +2813,9 @@ UVS_DEV void gacc_load(const Ctx& c, GAcc& A) {
 // then, in every row, the gatherers walk and the evaluators go on: to pass A of chunk t + 1 if it runs ahead (no barrier inside), else to chunk_touch (none).  The
 // first chunk of a linearization never runs ahead (nothing walks before it), a re-damping never does.  UVS_LINE_AHEAD=0 (KOpts::line_ahead) and
 // -DUVS_X_NO_LINE_AHEAD (A/B builds) give the plain order everywhere.
+// B1 (and the line half of redamp_prep) is the stretch all gatherers wait through: eight lanes per line on all evaluator waves (ln_lanes_solve; KOpts::line_b1), no barrier
+// inside, no LDS beyond the records it reads and the X it writes, nothing in the lists' place.  Its first trip's global reads (a line's observation range, the Jacobi
+// scales) are asked for in front of the barrier before it -- the entry barrier when pass A ran ahead, the one behind pass A otherwise -- and cross it in four registers (LnB1Pre).
 #ifndef UVS_X_NO_LINE_AHEAD
 static constexpr bool LINE_AHEAD = ROLES;
 #else
@@ -2669,10 +2845,11 @@ UVS_DEV void linearize_roles(const Ctx& c, const double* x, const double* invd, 
             if (redamp) redamp_prep(c, d, radius);
             else if (rb >= 0) {
                 UVS_TLOG(c, 1);
+                const LnB1Pre pre = line_b1_preload(c, d, first);
                 __syncthreads();      // the chunk's entry barrier: the previous walk is done, E / Y / X and the lists' places are free; the records are complete
                 UVS_PROF(c, P_GATHER);
                 UVS_TLOG(c, 2);
-                line_pass_b(c, d, first, radius, acost, rb);      // B1 | barrier | B2 | barrier
+                line_pass_b(c, d, first, radius, acost, rb, pre);      // B1 | barrier | B2 | barrier
                 __syncthreads();      // the fourth barrier of a line chunk (the gatherers count four whichever way pass A ran)
             } else {
                 chunk_eval(c, d, x, invd, line, first, radius);

@@ -167,6 +167,7 @@ inline uvsdev::KOpts make_kopts(const uvs_options& o, int debug) {
     k.max_invalid = o.max_consecutive_invalid_steps; k.debug = debug;
     { const char* e = std::getenv("UVS_REDAMP"); k.redamp = (e && e[0] == '0') ? 0 : 1; }      // diagnostic switch, read per launch (tests, A/B): 0 = re-linearize after every rejected step
     { const char* e = std::getenv("UVS_LINE_AHEAD"); k.line_ahead = (e && e[0] == '0') ? 0 : 1; }      // diagnostic switch, read per launch (tests, A/B): 0 = no line chunk's pass A runs ahead of its entry barrier
+    { const char* e = std::getenv("UVS_LINE_B1"); k.line_b1 = (e && e[0] == '0') ? 0 : 1; }      // diagnostic switch, read per launch (tests, A/B): 0 = one lane per line in pass B1 of a line chunk and in the line half of a re-damping
     return k;
 }
 
