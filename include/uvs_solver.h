@@ -1444,6 +1444,54 @@ int uvs_tri_shift_depth(uvs_tri *t, int n_points, const double *uv0, const doubl
 /* HIP-event time of the kernels of the last successful call on the handle's stream, upload and download excluded (milliseconds). */
 double uvs_tri_last_device_ms(const uvs_tri *t);
 
+/* ---- IMU pre-integration for batches of intervals (uvs_imu_*, csrc/uvs_imu_preintegrate.hip; additions only, the ABI version stays 7) ----
+ * IntegrationBase::push_back / propagate / midPointIntegration / repropagate (integration_base.h:30-158) for a batch of intervals in one
+ * launch, one wavefront per interval, FP64.  Per sample (dt, acc_1, gyr_1), with R(q) Eigen's toRotationMatrix() polynomial:
+ *   un_gyr = (gyr_0 + gyr_1) / 2 - bg;  rq = delta_q * (un_gyr dt / 2, 1), used UN-normalised in this step;
+ *   un_acc = (R(delta_q) (acc_0 - ba) + R(rq) (acc_1 - ba)) / 2;  rp = delta_p + delta_v dt + un_acc dt^2 / 2;  rv = delta_v + un_acc dt;
+ *   F (15 x 15) and V (15 x 18) as in midPointIntegration;  jacobian = F jacobian;  covariance = F covariance F^T + V noise V^T with
+ *   noise = diag(acc_n, gyr_n, acc_n, gyr_n, acc_w, gyr_w)^2 (x) I3;  then delta_q = rq / |rq|, delta_p = rp, delta_v = rv, sum_dt += dt,
+ *   (acc_0, gyr_0) = (acc_1, gyr_1).  skip = sum_dt > 10.0.  An interval without samples yields the empty pre-integration: identity delta and
+ *   jacobian, zero covariance, sum_dt = 0.  Re-propagation is the same call with other biases.
+ * Dead reckoning (state_p / state_R / state_v set): in the same walk, processIMU's prediction (estimator.cpp:104-117) from the state of frame i:
+ *   R' = R R(deltaQ(un_gyr dt)) with deltaQ = (theta / 2, 1) not normalised, no re-normalisation of R;
+ *   a = ((R (acc_0 - ba) - g) + (R' (acc_1 - ba) - g)) / 2;  P += dt V + dt^2 a / 2;  V += dt a.
+ * No CPU path: uvs_imu_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_IMU_MAX_INTERVALS 65536           /* largest max_intervals uvs_imu_create takes */
+#define UVS_IMU_MAX_SAMPLES (1 << 22)         /* largest max_samples */
+#define UVS_IMU_STAGE_CHUNK 64                /* samples the kernel stages at a time (one per lane); of interest to tests only */
+typedef struct uvs_imu uvs_imu;               /* opaque: device buffers, pinned staging, stream, the noise values */
+
+typedef struct uvs_imu_batch {
+    int32_t n_intervals;
+    const int32_t *sample_begin;   /* [n_intervals + 1], [0] = 0, non-decreasing: interval k owns samples sample_begin[k] .. sample_begin[k+1]-1 */
+    const double *acc_0, *gyr_0;   /* [n_intervals][3] the sample the interval starts from */
+    const double *ba, *bg;         /* [n_intervals][3] linearized_ba / linearized_bg */
+    const int32_t *frame_i;        /* [n_intervals] copied into the block; may be NULL (0) */
+    const double *dt;              /* [n_samples] */
+    const double *acc, *gyr;       /* [n_samples][3] */
+    /* dead reckoning, all NULL or all set */
+    const double *state_p, *state_R, *state_v;   /* [n_intervals][3], [9] (row-major), [3] */
+    double gravity[3];
+} uvs_imu_batch;
+
+/* UVS_ERR_INVALID_ARG: null out or a capacity < 1; UVS_ERR_CAPACITY: a capacity above its bound. */
+int uvs_imu_create(int device, int max_intervals, int max_samples, uvs_imu **out);
+void uvs_imu_destroy(uvs_imu *h);
+const char *uvs_imu_last_error(const uvs_imu *h);
+/* The four noise densities of `noise`.  A new handle holds the EuRoC values 0.08, 0.004, 0.00004, 2.0e-6.  UVS_ERR_INVALID_ARG unless all
+ * are positive and finite (the values then stay as they were). */
+int uvs_imu_set_noise(uvs_imu *h, double acc_n, double gyr_n, double acc_w, double gyr_w);
+/* One upload, the launch, one download.  blocks[n_intervals] (linearized_ba / bg and frame_i copied from the batch); with dead reckoning
+ * pred_p[n_intervals][3], pred_R[n_intervals][9], pred_v[n_intervals][3], else the three are not touched and may be NULL.
+ * n_intervals == 0: UVS_OK, nothing launched.  Every refusal happens before anything is launched, writes nothing and leaves the handle usable.
+ * UVS_ERR_INVALID_ARG: a null pointer (the sample arrays may be NULL when there are no samples), a negative count, sample_begin[0] != 0 or
+ * a decreasing sample_begin, a dt that is negative or not finite, a sample, bias, state or gravity that is not finite, a dead-reckoning trio
+ * set only in part or its outputs missing.  UVS_ERR_CAPACITY: n_intervals or the sample count above the handle's capacity. */
+int uvs_imu_preintegrate(uvs_imu *h, const uvs_imu_batch *b, uvs_imu_block *blocks, double *pred_p, double *pred_R, double *pred_v);
+/* HIP-event time of the kernel of the last successful call, upload and download excluded (milliseconds). */
+double uvs_imu_last_device_ms(const uvs_imu *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -981,3 +981,61 @@ def tri_batch(batch, null=()):
         if name not in null and a.size:
             setattr(b, name, a.ctypes.data_as(c_double_p if a.dtype == np.float64 else c_i32_p))
     return b, keep
+
+
+# ---- IMU pre-integration for batches of intervals (uvs_imu_*, include/uvs_solver.h) ------------------------------
+IMU_MAX_INTERVALS = 65536
+IMU_MAX_SAMPLES = 1 << 22
+IMU_STAGE_CHUNK = 64
+IMU_INTERVAL_FIELDS = ("acc_0", "gyr_0", "ba", "bg")
+IMU_SAMPLE_FIELDS = ("dt", "acc", "gyr")
+IMU_STATE_FIELDS = ("state_p", "state_R", "state_v")
+IMU_BLOCK_DTYPE = np.dtype([("sum_dt", "<f8"), ("delta_p", "<f8", 3), ("delta_q", "<f8", 4), ("delta_v", "<f8", 3), ("linearized_ba", "<f8", 3),
+                            ("linearized_bg", "<f8", 3), ("jacobian", "<f8", (15, 15)), ("covariance", "<f8", (15, 15)), ("frame_i", "<i4"), ("skip", "<i4")])
+assert IMU_BLOCK_DTYPE.itemsize == C.sizeof(ImuBlock)
+
+
+class ImuBatch(C.Structure):
+    _fields_ = [("n_intervals", C.c_int32), ("sample_begin", c_i32_p), ("acc_0", c_double_p), ("gyr_0", c_double_p), ("ba", c_double_p), ("bg", c_double_p),
+                ("frame_i", c_i32_p), ("dt", c_double_p), ("acc", c_double_p), ("gyr", c_double_p),
+                ("state_p", c_double_p), ("state_R", c_double_p), ("state_v", c_double_p), ("gravity", C.c_double * 3)]
+
+
+def imu_batch(batch, null=()):
+    """(ImuBatch, keepalive) from a dict with the fields of uvs_imu_batch as arrays: sample_begin [n + 1], IMU_INTERVAL_FIELDS [n, 3],
+    IMU_SAMPLE_FIELDS ([m], [m, 3], [m, 3]); optional frame_i [n] and, for the dead reckoning, IMU_STATE_FIELDS ([n, 3], [n, 3, 3], [n, 3])
+    with gravity [3].  `null` names fields passed as NULL."""
+    b = ImuBatch(); keep = {}
+    keep["sample_begin"] = np.ascontiguousarray(batch["sample_begin"], np.int32)
+    b.n_intervals = len(keep["sample_begin"]) - 1
+    for name in IMU_INTERVAL_FIELDS + IMU_SAMPLE_FIELDS + IMU_STATE_FIELDS:
+        if batch.get(name) is not None:
+            keep[name] = np.ascontiguousarray(batch[name], np.float64)
+    if batch.get("frame_i") is not None:
+        keep["frame_i"] = np.ascontiguousarray(batch["frame_i"], np.int32)
+    for name, a in list(keep.items()):
+        if name not in null:
+            p = a if a.size else np.zeros(1, a.dtype)          # an empty array is still a pointer
+            keep[name + "_p"] = p
+            setattr(b, name, p.ctypes.data_as(c_double_p if a.dtype == np.float64 else c_i32_p))
+    g = np.asarray(batch.get("gravity", (0.0, 0.0, 0.0)), np.float64)
+    b.gravity[0], b.gravity[1], b.gravity[2] = float(g[0]), float(g[1]), float(g[2])
+    return b, keep
+
+
+def imu_batch_of(intervals, states=None, gravity=None):
+    """The batch dict of a list of intervals, each a dict(acc_0, gyr_0, ba, bg, dt [m], acc [m, 3], gyr [m, 3]) with an optional frame_i;
+    `states`: per interval (P [3], R [3, 3], V [3]) for the dead reckoning, with `gravity` [3]."""
+    n = len(intervals)
+    cnt = [len(np.atleast_1d(iv["dt"])) for iv in intervals]
+    cat = lambda key, w: (np.concatenate([np.asarray(iv[key], np.float64).reshape(-1, w) for iv in intervals]) if n else np.zeros((0, w)))
+    b = dict(sample_begin=np.r_[0, np.cumsum(cnt)].astype(np.int32), dt=cat("dt", 1).reshape(-1), acc=cat("acc", 3), gyr=cat("gyr", 3),
+             frame_i=np.array([iv.get("frame_i", 0) for iv in intervals], np.int32))
+    for key in IMU_INTERVAL_FIELDS:
+        b[key] = np.array([iv[key] for iv in intervals], np.float64).reshape(n, 3)
+    if states is not None:
+        b["state_p"] = np.array([s[0] for s in states], np.float64).reshape(n, 3)
+        b["state_R"] = np.array([s[1] for s in states], np.float64).reshape(n, 3, 3)
+        b["state_v"] = np.array([s[2] for s in states], np.float64).reshape(n, 3)
+        b["gravity"] = np.asarray(gravity, np.float64)
+    return b

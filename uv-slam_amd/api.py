@@ -36,6 +36,7 @@ EXPORTS = [
     "uvs_pr_query", "uvs_pr_detect", "uvs_pr_last_device_ms",
     "uvs_tri_create", "uvs_tri_destroy", "uvs_tri_last_error", "uvs_tri_set_init_depth", "uvs_tri_triangulate", "uvs_tri_check_lines", "uvs_tri_shift_depth",
     "uvs_tri_last_device_ms",
+    "uvs_imu_create", "uvs_imu_destroy", "uvs_imu_last_error", "uvs_imu_set_noise", "uvs_imu_preintegrate", "uvs_imu_last_device_ms",
 ]
 
 
@@ -218,6 +219,13 @@ def lib():
         L.uvs_tri_check_lines.restype = C.c_int
         L.uvs_tri_shift_depth.argtypes = [C.c_void_p, C.c_int] + [abi.c_double_p] * 7 + [abi.c_i32_p]; L.uvs_tri_shift_depth.restype = C.c_int
         L.uvs_tri_last_device_ms.argtypes = [C.c_void_p]; L.uvs_tri_last_device_ms.restype = C.c_double
+        L.uvs_imu_create.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_void_p)]; L.uvs_imu_create.restype = C.c_int
+        L.uvs_imu_destroy.argtypes = [C.c_void_p]; L.uvs_imu_destroy.restype = None
+        L.uvs_imu_last_error.argtypes = [C.c_void_p]; L.uvs_imu_last_error.restype = C.c_char_p
+        L.uvs_imu_set_noise.argtypes = [C.c_void_p] + [C.c_double] * 4; L.uvs_imu_set_noise.restype = C.c_int
+        L.uvs_imu_preintegrate.argtypes = [C.c_void_p, C.POINTER(abi.ImuBatch), C.c_void_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
+        L.uvs_imu_preintegrate.restype = C.c_int
+        L.uvs_imu_last_device_ms.argtypes = [C.c_void_p]; L.uvs_imu_last_device_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -1627,3 +1635,80 @@ class Triangulator(_Handle):
         depth, pf, orth, lf = self.triangulate(b, init_depth)
         pcut = np.cumsum([len(w.inv_depth) for w in windows])[:-1]; lcut = np.cumsum([len(w.line_orth) for w in windows])[:-1]
         return np.split(1.0 / depth, pcut), np.split(orth, lcut), np.split(pf, pcut), np.split(lf, lcut)
+
+
+class ImuPreintegrator(_Handle):
+    """Owns one `uvs_imu` handle: IntegrationBase's pre-integration (and, on request, processIMU's dead reckoning) for whole batches of
+    intervals on one GPU, one wavefront per interval.  Re-propagation is the same call with other biases.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    _UNIT = "uvs_imu"
+    FILL = -7.0        # what preintegrate_raw puts into its outputs before the call: a refused call must leave it there
+
+    def __init__(self, device=0, max_intervals=2560, max_samples=2560 * 64):
+        self._create(device, int(max_intervals), int(max_samples))
+        self.last_ms = self.last_device_ms = 0.0
+
+    def set_noise_raw(self, acc_n, gyr_n, acc_w, gyr_w):
+        return lib().uvs_imu_set_noise(self._h, float(acc_n), float(gyr_n), float(acc_w), float(gyr_w))
+
+    def set_noise(self, acc_n, gyr_n, acc_w, gyr_w):
+        """The noise densities behind `covariance` (a new handle: synth.ACC_N, GYR_N, ACC_W, GYR_W)."""
+        rc = self.set_noise_raw(acc_n, gyr_n, acc_w, gyr_w)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_imu_set_noise", rc)
+
+    def preintegrate_raw(self, batch, null=(), n_intervals=None):
+        """-> (return code, blocks, pred_p, pred_R, pred_v) without raising: for the tests of the argument checks.  `null` names batch fields or
+        outputs ("blocks", "pred_p", "pred_R", "pred_v") passed as NULL, or "batch"; n_intervals overrides the count passed.  The outputs are
+        filled with FILL before the call (every byte of `blocks` with 0xA5)."""
+        b, keep = abi.imu_batch(batch, null)
+        if n_intervals is not None:
+            b.n_intervals = int(n_intervals)
+        n = max(len(keep["sample_begin"]) - 1, 0)
+        blocks = np.frombuffer(bytearray(b"\xa5" * (max(n, 1) * abi.IMU_BLOCK_DTYPE.itemsize)), abi.IMU_BLOCK_DTYPE)
+        pp = np.full((max(n, 1), 3), self.FILL); pR = np.full((max(n, 1), 3, 3), self.FILL); pv = np.full((max(n, 1), 3), self.FILL)
+        out = dict(blocks=C.c_void_p(blocks.ctypes.data), pred_p=abi._dp(pp), pred_R=abi._dp(pR), pred_v=abi._dp(pv))
+        for k in null:
+            if k in out:
+                out[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_imu_preintegrate(self._h, None if "batch" in null else C.byref(b), out["blocks"], out["pred_p"], out["pred_R"], out["pred_v"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: checks, packing, upload, kernel, download
+        self.last_device_ms = float(lib().uvs_imu_last_device_ms(self._h))      # HIP events around the kernel alone
+        return rc, blocks[:n], pp[:n], pR[:n], pv[:n]
+
+    def preintegrate(self, batch):
+        """batch: a dict with the fields of uvs_imu_batch as arrays (abi.imu_batch, abi.imu_batch_of) -> blocks, a structured array of
+        abi.IMU_BLOCK_DTYPE [n_intervals]; with the dead-reckoning state in the batch -> (blocks, pred_p [n, 3], pred_R [n, 3, 3], pred_v [n, 3])."""
+        rc, blocks, pp, pR, pv = self.preintegrate_raw(batch)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_imu_preintegrate", rc)
+        return (blocks, pp, pR, pv) if batch.get("state_p") is not None else blocks
+
+    @staticmethod
+    def block_dict(rec):
+        """One record of the structured blocks as the dict abi.Window.imu carries."""
+        return dict(sum_dt=float(rec["sum_dt"]), delta_p=rec["delta_p"].copy(), delta_q=rec["delta_q"].copy(), delta_v=rec["delta_v"].copy(),
+                    linearized_ba=rec["linearized_ba"].copy(), linearized_bg=rec["linearized_bg"].copy(), jacobian=rec["jacobian"].copy(),
+                    covariance=rec["covariance"].copy(), frame_i=int(rec["frame_i"]), skip=int(rec["skip"]))
+
+    def preintegrate_windows(self, samples_per_window, ba, bg):
+        """samples_per_window: per window the list synth._simulate_frames(..., samples=) fills -- entry 0 holds the one message the first interval
+        starts from, entry f + 1 the (dt, acc, gyr) messages of the interval frame f -> f + 1; ba, bg: per window [3], or [n_frames - 1, 3] per
+        interval.  One call for every interval of every window -> per window the `imu` list of abi.Window (frame_i = 0, 1, ...)."""
+        intervals = []
+        for wi, frames in enumerate(samples_per_window):
+            start = frames[0][-1]
+            wba = np.broadcast_to(np.asarray(ba[wi], np.float64), (len(frames) - 1, 3)); wbg = np.broadcast_to(np.asarray(bg[wi], np.float64), (len(frames) - 1, 3))
+            for f, msgs in enumerate(frames[1:]):
+                intervals.append(dict(acc_0=start[1], gyr_0=start[2], ba=wba[f], bg=wbg[f], frame_i=f, dt=[m[0] for m in msgs],
+                                      acc=np.array([m[1] for m in msgs]).reshape(-1, 3), gyr=np.array([m[2] for m in msgs]).reshape(-1, 3)))
+                if msgs:
+                    start = msgs[-1]
+        blocks = self.preintegrate(abi.imu_batch_of(intervals))
+        out, at = [], 0
+        for frames in samples_per_window:
+            out.append([self.block_dict(blocks[at + f]) for f in range(len(frames) - 1)]); at += len(frames) - 1
+        return out

@@ -38,6 +38,7 @@ Estimator::~Estimator() {
     if (eval_solver) { if (uvs::evaluation_solver() == eval_solver) uvs::set_evaluation_solver(nullptr); uvs_destroy(eval_solver); }
     finishMarginalization();
     setDeviceTriangulation(false);
+    setDeviceIntegration(false);
     uvs_destroy(solver); delete last_marginalization_info; for (auto* p : pre_integrations) delete p;
 }
 
@@ -49,6 +50,54 @@ void Estimator::setDeviceTriangulation(bool on) {
     if (rc == UVS_OK && (rc = uvs_tri_set_init_depth(tri, INIT_DEPTH)) != UVS_OK) { uvs_tri_destroy(tri); tri = nullptr; }
     if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_tri_create: ") + uvs_status_string(rc));     // no CPU fallback once asked for
     f_manager.tri = tri;
+}
+
+void Estimator::setDeviceIntegration(bool on) {
+    if (on == (imu != nullptr)) return;
+    if (!on) { uvs_imu_destroy(imu); imu = nullptr; return; }
+    if (!uvs_imu_create) throw std::runtime_error("setDeviceIntegration: this back end has no uvs_imu_*");
+    int rc = uvs_imu_create(0, WINDOW_SIZE + 1, 1 << 16, &imu);      // an interval is cut off at 10 s (skip): 1 << 16 samples hold a window of them at 200 Hz
+    if (rc == UVS_OK && (rc = uvs_imu_set_noise(imu, ACC_N, GYR_N, ACC_W, GYR_W)) != UVS_OK) { uvs_imu_destroy(imu); imu = nullptr; }
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_imu_create: ") + uvs_status_string(rc));     // no CPU fallback once asked for
+}
+
+// One uvs_imu_preintegrate call for the listed slots: each IntegrationBase is integrated afresh over the samples recorded for its slot, from its
+// linearized_acc / linearized_gyr at its linearized_ba / linearized_bg, and its fields are written from the returned block.
+void Estimator::integrateOnDevice(const int* slots, int n_slots) {
+    std::vector<int32_t> begin(1, 0);
+    std::vector<double> head[4], dt, acc, gyr;
+    for (int k = 0; k < n_slots; ++k) {
+        const int s = slots[k];
+        const IntegrationBase& pre = *pre_integrations[s];
+        const Eigen::Vector3d* v[4] = {&pre.linearized_acc, &pre.linearized_gyr, &pre.linearized_ba, &pre.linearized_bg};
+        for (int q = 0; q < 4; ++q) for (int a = 0; a < 3; ++a) head[q].push_back((*v[q])(a));
+        for (std::size_t m = 0; m < dt_buf[s].size(); ++m) {
+            dt.push_back(dt_buf[s][m]);
+            for (int a = 0; a < 3; ++a) { acc.push_back(linear_acceleration_buf[s][m](a)); gyr.push_back(angular_velocity_buf[s][m](a)); }
+        }
+        begin.push_back((int32_t)dt.size());
+    }
+    uvs_imu_batch b{};
+    b.n_intervals = n_slots; b.sample_begin = begin.data();
+    b.acc_0 = head[0].data(); b.gyr_0 = head[1].data(); b.ba = head[2].data(); b.bg = head[3].data();
+    const double none[3] = {0, 0, 0};
+    b.dt = dt.empty() ? none : dt.data(); b.acc = acc.empty() ? none : acc.data(); b.gyr = gyr.empty() ? none : gyr.data();
+    std::vector<uvs_imu_block> blocks(n_slots);
+    const int rc = uvs_imu_preintegrate(imu, &b, blocks.data(), nullptr, nullptr, nullptr);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_imu_preintegrate: ") + uvs_status_string(rc) + " / " + uvs_imu_last_error(imu));
+    for (int k = 0; k < n_slots; ++k) {
+        const int s = slots[k];
+        IntegrationBase& pre = *pre_integrations[s];
+        const uvs_imu_block& blk = blocks[k];
+        pre.sum_dt = blk.sum_dt;
+        pre.delta_p = Eigen::Vector3d(blk.delta_p[0], blk.delta_p[1], blk.delta_p[2]);
+        pre.delta_q = Eigen::Quaterniond(blk.delta_q[3], blk.delta_q[0], blk.delta_q[1], blk.delta_q[2]);
+        pre.delta_v = Eigen::Vector3d(blk.delta_v[0], blk.delta_v[1], blk.delta_v[2]);
+        std::memcpy(pre.jacobian, blk.jacobian, sizeof(pre.jacobian)); std::memcpy(pre.covariance, blk.covariance, sizeof(pre.covariance));
+        // the object's own sample record and its last sample follow the slot's, as push_back would have left them
+        pre.dt_buf = dt_buf[s]; pre.acc_buf = linear_acceleration_buf[s]; pre.gyr_buf = angular_velocity_buf[s];
+        pre.acc_0 = pre.acc_buf.empty() ? pre.linearized_acc : pre.acc_buf.back(); pre.gyr_0 = pre.gyr_buf.empty() ? pre.linearized_gyr : pre.gyr_buf.back();
+    }
 }
 
 // ---- small helpers of this file: a 7-double parameter block (px py pz qx qy qz qw, estimator.cpp:530-537) <-> (translation, rotation)
@@ -306,7 +355,7 @@ void Estimator::processIMU(double dt, const Eigen::Vector3d& acc, const Eigen::V
     IntegrationBase*& pre = pre_integrations[newest];
     if (pre == nullptr) pre = new IntegrationBase{acc_0, gyr_0, Bas[newest], Bgs[newest]};
     if (newest > 0) {
-        pre->push_back(dt, acc, gyr);
+        if (!imu) pre->push_back(dt, acc, gyr);      // device route: the interval is integrated once per image (processImage)
         recordSample(newest, dt, acc, gyr);
         deadReckon(newest, dt, acc, gyr);
     }
@@ -330,6 +379,7 @@ void Estimator::deadReckon(int f, double dt, const Eigen::Vector3d& acc, const E
 // One image: track bookkeeping + keyframe decision, then (window full) solve, failure check, slide (estimator.cpp:120-222).
 // all_image_frame / tmp_pre_integration feed initialStructure() only and are not kept; ESTIMATE_EXTRINSIC == 2 is initialization too.
 void Estimator::processImage(const FeatureManager::ImagePoints& image, const FeatureManager::ImageLines& image_line, const std_msgs::Header& header) {
+    if (imu && frame_count > 0 && pre_integrations[frame_count]) integrateOnDevice(&frame_count, 1);
     const bool second_newest_is_keyframe = f_manager.addFeatureCheckParallax(frame_count, image, image_line, td);
     marginalization_flag = second_newest_is_keyframe ? MARGIN_OLD : MARGIN_SECOND_NEW;
     Headers[frame_count] = header;
@@ -368,7 +418,13 @@ bool Estimator::initialStructure() {
         Ps[i] = Eigen::Vector3d(pose[0], pose[1], pose[2]);
         Rs[i] = Eigen::Quaterniond(pose[6], pose[3], pose[4], pose[5]).normalized().toRotationMatrix();
         Vs[i] = Eigen::Vector3d(sb[0], sb[1], sb[2]); Bas[i] = Eigen::Vector3d(sb[3], sb[4], sb[5]); Bgs[i] = Eigen::Vector3d(sb[6], sb[7], sb[8]);
-        if (pre_integrations[i] && i > 0) pre_integrations[i]->repropagate(Bas[i], Bgs[i]);
+        if (pre_integrations[i] && i > 0 && !imu) pre_integrations[i]->repropagate(Bas[i], Bgs[i]);
+    }
+    if (imu) {                            // the same re-propagation, one device call for all intervals
+        std::vector<int> slots;
+        for (int i = 1; i <= WINDOW_SIZE; ++i)
+            if (pre_integrations[i]) { pre_integrations[i]->linearized_ba = Bas[i]; pre_integrations[i]->linearized_bg = Bgs[i]; slots.push_back(i); }
+        if (!slots.empty()) integrateOnDevice(slots.data(), (int)slots.size());
     }
     for (auto& it : f_manager.feature) it.estimated_depth = -1;
     initial_window.clear();
@@ -413,11 +469,12 @@ void Estimator::slideWindow() {
     }
     const int kept = last - 1;
     for (std::size_t k = 0; k < dt_buf[last].size(); ++k) {
-        pre_integrations[kept]->push_back(dt_buf[last][k], linear_acceleration_buf[last][k], angular_velocity_buf[last][k]);
+        if (!imu) pre_integrations[kept]->push_back(dt_buf[last][k], linear_acceleration_buf[last][k], angular_velocity_buf[last][k]);
         dt_buf[kept].push_back(dt_buf[last][k]);
         linear_acceleration_buf[kept].push_back(linear_acceleration_buf[last][k]);
         angular_velocity_buf[kept].push_back(angular_velocity_buf[last][k]);
     }
+    if (imu) integrateOnDevice(&kept, 1);      // the kept interval over its appended samples
     Ps[kept] = Ps[last]; Vs[kept] = Vs[last]; Rs[kept] = Rs[last]; Bas[kept] = Bas[last]; Bgs[kept] = Bgs[last];
     Headers[kept] = Headers[last];
     restart_newest_preintegration();

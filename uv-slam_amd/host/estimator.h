@@ -12,6 +12,14 @@
 #include "factor/factors.h"
 #include "window_assembly.h"
 
+// uvs_imu_* are weak references like uvs_tri_* (feature_manager.h): this file is also compiled against the CPU oracle, which has neither, and
+// Estimator::setDeviceIntegration refuses to make a handle there.
+#pragma weak uvs_imu_create
+#pragma weak uvs_imu_destroy
+#pragma weak uvs_imu_last_error
+#pragma weak uvs_imu_set_noise
+#pragma weak uvs_imu_preintegrate
+
 namespace std_msgs { struct Header { struct Stamp { double t = 0; double toSec() const { return t; } } stamp; }; }      // the one field of std_msgs::Header the estimator reads
 
 class Estimator {
@@ -102,6 +110,14 @@ class Estimator {
     // setLineOrtho / removeBackShiftDepth.  Throws when the handle cannot be made (no GPU, or a back end without uvs_tri_*).
     void setDeviceTriangulation(bool on);
     uvs_tri* tri = nullptr;
+    // Pre-integration on the device (uvs_imu_*): OFF by default -- the IntegrationBase objects then integrate sample by sample as they always did.  On: the
+    // estimator owns a uvs_imu handle, processIMU only records and dead-reckons, and the fields of the IntegrationBase objects are written from ONE device call
+    // over the recorded dt_buf / linear_acceleration_buf / angular_velocity_buf: the newest interval once per image (processImage), the kept interval
+    // after the merge of slideWindow() under MARGIN_SECOND_NEW, all intervals at the re-propagation of initialStructure().  Throws when the handle cannot
+    // be made (no GPU, or a back end without uvs_imu_*), and when a call is refused.
+    void setDeviceIntegration(bool on);
+    void integrateOnDevice(const int* slots, int n_slots);      // pre_integrations[slot] <- its recorded samples at its own linearized_ba / linearized_bg
+    uvs_imu* imu = nullptr;
     // wall-clock spent inside optimization() (sums over the calls): whole call, uvs::Solve() alone, marginalization alone
     double optimization_ms = 0, solve_ms = 0, marginalize_ms = 0; int optimization_calls = 0;
 };

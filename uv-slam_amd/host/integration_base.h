@@ -1,6 +1,7 @@
 // integration_base.h -- host mirror of IntegrationBase (vins_estimator/src/factor/integration_base.h:9-208).
-// Midpoint pre-integration with Jacobian / covariance propagation (sequential, ~20 samples
-// per frame => host code).  jacobian / covariance are 15x15 ROW-major, the layout uvs_imu_block expects.
+// Midpoint pre-integration with Jacobian / covariance propagation, sample by sample on the host; the same rule
+// for batches of intervals on the device is uvs_imu_preintegrate, which Estimator::setDeviceIntegration routes these objects through.
+// jacobian / covariance are 15x15 ROW-major, the layout uvs_imu_block expects.
 #pragma once
 #include <cstring>
 #include <vector>
