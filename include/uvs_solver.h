@@ -1492,6 +1492,108 @@ int uvs_imu_preintegrate(uvs_imu *h, const uvs_imu_batch *b, uvs_imu_block *bloc
 /* HIP-event time of the kernel of the last successful call, upload and download excluded (milliseconds). */
 double uvs_imu_last_device_ms(const uvs_imu *h);
 
+/* ---- relative pose of window pairs: the bootstrap's choice of its reference frame (uvs_rp_*, csrc/uvs_relative_pose.hip; additions only, the
+ * ABI version stays 7) ----
+ * Estimator::relativePose (estimator.cpp:448-477) with MotionEstimator::solveRelativeRT (initial/solve_5pts.cpp:193-227) and that file's
+ * recoverPose / decomposeEssentialMat (:5-182), for a batch of frame pairs.  An item is the correspondences of one pair (frame_l, WINDOW_SIZE)
+ * of one window (what FeatureManager::getCorresponding returns, host bookkeeping): left[i], right[i] the normalized points of track i in the
+ * two frames.  The ten pairs of a window are ten items of one launch, many windows one batch; a window's answer is its first item with ok.
+ * An item gives the same bits alone or in a batch and from run to run.  Every FP64 operation of steps 1 to 3 is one of + - * / sqrt, rounded
+ * once, in the order written (no fused multiply-add): they are held bit for bit to tests/rp_ref.py and tests/fr_ref.py.  Steps 4 to 6 are
+ * held to the 60-digit evaluation of tests/rp_ref.py: the counts, masks and the choice exactly, R and t within a bound.
+ *   1 gate      n > min_corres, else status UVS_RP_FEW_CORRES.  average_parallax = (the sum over i = 0 .. n - 1, in that order, of
+ *               sqrt(dx dx + dy dy), dx = left_x - right_x, dy = left_y - right_y on the points as given) / n;
+ *               average_parallax focal_length > min_parallax_px, else UVS_RP_LOW_PARALLAX.  n >= min_ransac_points, else UVS_RP_FEW_POINTS.
+ *               A gated item has ok = 0, runs no RANSAC (its workgroup leaves at once) and no recovery; its other fields are 0 (hypothesis
+ *               = root = chosen = -1, ransac.status = UVS_FT_REJECT_SKIPPED, an all-zero mask); n = 0 gives average_parallax = 0
+ *   2 rounding  solveRelativeRT turns the points into cv::Point2f: from here on every coordinate is rounded to float32 (to nearest even) and
+ *               widened again
+ *   3 RANSAC    uvs_ft_reject's rule, unchanged, on the rounded points (prev = left, next = right) with f_threshold, confidence and the
+ *               item's seed; `ransac` is its result block.  UVS_FT_REJECT_NO_MODEL gives status UVS_RP_NO_MODEL, ok = 0 -- a stated
+ *               deviation, the reference would hand an empty matrix to recoverPose
+ *   4 decompose F = U diag(s) V^T with s0 >= s1 >= s2.  The signs, which the reference leaves to its SVD routine, are fixed here: each right
+ *               singular vector v_k, k = 0, 1, 2, has its entry of largest magnitude (the first such) positive; u_k = F v_k / s_k for k = 0, 1;
+ *               u_2 = u_0 x u_1 with the sign that makes ITS entry of largest magnitude positive.  Then U is negated if det(U) < 0, V^T if
+ *               det(V^T) < 0.  W = [[0,1,0],[-1,0,0],[0,0,1]]; R1 = U W V^T, R2 = U W^T V^T, t = U[:,2]
+ *               An F with s1 = 0 (rank < 2) or a singular value that is not finite has no such decomposition: UVS_RP_NO_MODEL, ok = 0,
+ *               the fields behind `ransac` as for a gated item
+ *   5 cheirality  for the candidates k = 0 .. 3 = (R1, t), (R2, t), (R1, -t), (R2, -t) and every point: the 4 x 4 matrix of OpenCV's
+ *               triangulatePoints from P0 = [I | 0] and P = [R | t], rows x P0[2] - P0[0], y P0[2] - P0[1] with (x, y) = left, then
+ *               x P[2] - P[0], y P[2] - P[1] with (x, y) = right; Q = its right singular vector of the smallest singular value;
+ *               m = Q2 Q3 > 0; X = Q[0..2] / Q3, m &= X2 < max_depth; Y = R X + t, m &= Y2 > 0, m &= Y2 < max_depth; m &= the RANSAC mask.
+ *               good[k] = the ones of m
+ *   6 choice    the reference's chain (solve_5pts.cpp:152-181): k = 0 if good0 >= each of the others, else 1 if good1 >= each of the others,
+ *               else 2 if good2 >= each of the others, else 3 -- ties go to the lower k.  R = the candidate's rotation, t its translation,
+ *               mask = its m; inlier_cnt = good[chosen]; Rotation = R^T, Translation = -(R^T t); ok = inlier_cnt > min_inliers, else status
+ *               UVS_RP_FEW_INLIERS
+ * Kernels: k_rp_gate (a wavefront per item: step 1, step 2), k_ft_reject_run (step 3: the kernel of uvs_ft_reject, shared through
+ * csrc/uvs_ft_reject_kernel.h; F and its mask stay on the device), k_rp_recover (a wavefront per item: the 3 x 3 SVD by one-sided Jacobi,
+ * wave-uniform; lanes stride over the points, the four triangulations of a point in registers by Givens rotations and a one-sided Jacobi
+ * SVD; the counts by ballots).  No CPU path: uvs_rp_create fails with UVS_ERR_NO_DEVICE without a GPU. */
+#define UVS_RP_MAX_ITEMS 4096                 /* largest max_items uvs_rp_create takes; max_points up to UVS_FT_MAX_POINTS */
+enum { UVS_RP_OK = 0, UVS_RP_FEW_CORRES = 1, UVS_RP_LOW_PARALLAX = 2, UVS_RP_FEW_POINTS = 3, UVS_RP_NO_MODEL = 4, UVS_RP_FEW_INLIERS = 5 };
+typedef struct uvs_rp uvs_rp;                 /* opaque: device buffers, pinned staging, stream */
+
+typedef struct uvs_rp_item {
+    int32_t window;                    /* 0 .. n_windows - 1, non-decreasing over the items */
+    int32_t frame_l;                   /* 0 .. UVS_WINDOW_SIZE - 1, strictly increasing within a window */
+    int32_t n;                         /* correspondences, 0 .. max_points */
+    int32_t reserved;
+    uint64_t seed;                     /* of the item's RANSAC samples */
+    const double *left;                /* [n][2] normalized points in frame_l, finite */
+    const double *right;               /* [n][2] normalized points in the newest frame, finite */
+} uvs_rp_item;
+
+typedef struct uvs_rp_params {         /* uvs_rp_default_params: the reference's values */
+    double focal_length;               /* 460     FOCAL_LENGTH */
+    double min_parallax_px;            /* 30      average_parallax * FOCAL_LENGTH > 30 */
+    double f_threshold;                /* 0.3 / 460 */
+    double confidence;                 /* 0.99 */
+    double max_depth;                  /* 50      recoverPose's dist */
+    int32_t min_corres;                /* 20      corres.size() > 20 */
+    int32_t min_ransac_points;         /* 15      corres.size() >= 15; at least 8 */
+    int32_t min_inliers;               /* 12      inlier_cnt > 12 */
+    int32_t reserved;
+} uvs_rp_params;
+
+typedef struct uvs_rp_item_result {
+    int32_t status;                    /* UVS_RP_* */
+    int32_t n;
+    double average_parallax;
+    uvs_ft_reject_result ransac;       /* of step 3 */
+    int32_t good[4];
+    int32_t chosen;                    /* 0 .. 3, -1 if the item did not get that far */
+    int32_t inlier_cnt;
+    int32_t ok;
+    int32_t reserved;
+    double R[9], t[3];                 /* as recoverPose returns them, row-major */
+    double Rotation[9], Translation[3];/* as solveRelativeRT returns them: R^T, -(R^T t) */
+} uvs_rp_item_result;
+
+typedef struct uvs_rp_window_result {
+    int32_t l;                         /* frame_l of the window's first item with ok, or -1 */
+    int32_t reserved;
+    double Rotation[9], Translation[3];/* of that item; 0 if none */
+} uvs_rp_window_result;
+
+/* UVS_ERR_INVALID_ARG: null out or a capacity < 1; UVS_ERR_CAPACITY: max_items > UVS_RP_MAX_ITEMS or max_points > UVS_FT_MAX_POINTS. */
+int uvs_rp_create(int device, int max_items, int max_points, uvs_rp **out);
+void uvs_rp_destroy(uvs_rp *rp);
+const char *uvs_rp_last_error(const uvs_rp *rp);
+void uvs_rp_default_params(uvs_rp_params *params);
+/* One upload, the three kernels, one download.  mask[] is PACKED over the items in order: item i owns n_i bytes, the final recoverPose mask
+ * (1 = the point passed every test of the chosen candidate).  item_results[n_items]; window_results[n_windows] (a window without items has
+ * l = -1).  Every refusal is UVS_ERR_INVALID_ARG and happens before anything is launched: a null pointer (handle, items, params, mask, either
+ * result array, or a point array behind a positive n), n_items outside 1 .. max_items, n_windows < 1, a window outside 0 .. n_windows - 1 or
+ * decreasing, a frame_l outside 0 .. UVS_WINDOW_SIZE - 1 or not increasing within its window, n outside 0 .. max_points, a coordinate that
+ * is not finite, a parameter that is not finite, focal_length, f_threshold or max_depth <= 0, confidence outside (0, 1), min_ransac_points
+ * < 8, min_corres or min_inliers < 0.  A refused call changes nothing -- no output is written -- and the handle stays usable. */
+int uvs_rp_relative_pose(uvs_rp *rp, int n_items, const uvs_rp_item *items, const uvs_rp_params *params, uint8_t *mask,
+                         uvs_rp_item_result *item_results, int n_windows, uvs_rp_window_result *window_results);
+/* HIP-event time of a part of the last successful call on the handle's stream, upload and download excluded (milliseconds):
+ * part 0 k_rp_gate, 1 k_ft_reject_run, 2 k_rp_recover; any other part 0. */
+double uvs_rp_last_device_ms(const uvs_rp *rp, int part);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1039,3 +1039,67 @@ def imu_batch_of(intervals, states=None, gravity=None):
         b["state_v"] = np.array([s[2] for s in states], np.float64).reshape(n, 3)
         b["gravity"] = np.asarray(gravity, np.float64)
     return b
+
+
+# ---- relative pose of window pairs (uvs_rp_*, include/uvs_solver.h) -----------------------------------------------
+RP_MAX_ITEMS = 4096
+RP_OK, RP_FEW_CORRES, RP_LOW_PARALLAX, RP_FEW_POINTS, RP_NO_MODEL, RP_FEW_INLIERS = range(6)
+RP_PARAM_DEFAULTS = dict(focal_length=460.0, min_parallax_px=30.0, f_threshold=0.3 / 460, confidence=0.99, max_depth=50.0, min_corres=20,
+                         min_ransac_points=15, min_inliers=12)
+RP_ITEM_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("average_parallax", "<f8"),
+                                 ("ransac_status", "<i4"), ("n_inliers", "<i4"), ("hypothesis", "<i4"), ("root", "<i4"), ("iterations", "<i4"),
+                                 ("ransac_reserved", "<i4"), ("F", "<f8", 9),
+                                 ("good", "<i4", 4), ("chosen", "<i4"), ("inlier_cnt", "<i4"), ("ok", "<i4"), ("reserved", "<i4"),
+                                 ("R", "<f8", (3, 3)), ("t", "<f8", 3), ("Rotation", "<f8", (3, 3)), ("Translation", "<f8", 3)])
+RP_WINDOW_RESULT_DTYPE = np.dtype([("l", "<i4"), ("reserved", "<i4"), ("Rotation", "<f8", (3, 3)), ("Translation", "<f8", 3)])
+
+
+class RpItem(C.Structure):
+    _fields_ = [("window", C.c_int32), ("frame_l", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
+                ("left", c_double_p), ("right", c_double_p)]
+
+
+class RpParams(C.Structure):
+    _fields_ = [("focal_length", C.c_double), ("min_parallax_px", C.c_double), ("f_threshold", C.c_double), ("confidence", C.c_double),
+                ("max_depth", C.c_double), ("min_corres", C.c_int32), ("min_ransac_points", C.c_int32), ("min_inliers", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class RpItemResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n", C.c_int32), ("average_parallax", C.c_double), ("ransac", FtRejectResult), ("good", C.c_int32 * 4),
+                ("chosen", C.c_int32), ("inlier_cnt", C.c_int32), ("ok", C.c_int32), ("reserved", C.c_int32), ("R", C.c_double * 9),
+                ("t", C.c_double * 3), ("Rotation", C.c_double * 9), ("Translation", C.c_double * 3)]
+
+
+class RpWindowResult(C.Structure):
+    _fields_ = [("l", C.c_int32), ("reserved", C.c_int32), ("Rotation", C.c_double * 9), ("Translation", C.c_double * 3)]
+
+
+assert RP_ITEM_RESULT_DTYPE.itemsize == C.sizeof(RpItemResult) and RP_WINDOW_RESULT_DTYPE.itemsize == C.sizeof(RpWindowResult)
+
+
+def rp_params(**over):
+    """RpParams with the reference's values (RP_PARAM_DEFAULTS), `over` on top."""
+    p = RpParams()
+    for k, v in {**RP_PARAM_DEFAULTS, **over}.items():
+        setattr(p, k, v)
+    return p
+
+
+def rp_items_of(items, null=()):
+    """(RpItem array, keepalive) from dicts with window, frame_l, seed and left [n, 2], right [n, 2] float64 normalized points; an optional
+    `n` overrides the count passed.  `null` names "left" / "right": passed as NULL in every item."""
+    arr = (RpItem * max(len(items), 1))()
+    keep = []
+    for k, it in enumerate(items):
+        l = np.ascontiguousarray(it["left"], np.float64).reshape(-1, 2); r = np.ascontiguousarray(it["right"], np.float64).reshape(-1, 2)
+        if len(l) != len(r):
+            raise ValueError("rp_items_of: left and right differ in length")
+        keep += [l, r]
+        arr[k].window = int(it.get("window", 0)); arr[k].frame_l = int(it.get("frame_l", 0)); arr[k].n = int(it.get("n", len(l)))
+        arr[k].seed = int(it.get("seed", 0)) & ((1 << 64) - 1)
+        if len(l) and "left" not in null:
+            arr[k].left = _dp(l)
+        if len(r) and "right" not in null:
+            arr[k].right = _dp(r)
+    return arr, keep

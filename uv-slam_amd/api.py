@@ -37,6 +37,7 @@ EXPORTS = [
     "uvs_tri_create", "uvs_tri_destroy", "uvs_tri_last_error", "uvs_tri_set_init_depth", "uvs_tri_triangulate", "uvs_tri_check_lines", "uvs_tri_shift_depth",
     "uvs_tri_last_device_ms",
     "uvs_imu_create", "uvs_imu_destroy", "uvs_imu_last_error", "uvs_imu_set_noise", "uvs_imu_preintegrate", "uvs_imu_last_device_ms",
+    "uvs_rp_create", "uvs_rp_destroy", "uvs_rp_last_error", "uvs_rp_default_params", "uvs_rp_relative_pose", "uvs_rp_last_device_ms",
 ]
 
 
@@ -226,6 +227,13 @@ def lib():
         L.uvs_imu_preintegrate.argtypes = [C.c_void_p, C.POINTER(abi.ImuBatch), C.c_void_p, abi.c_double_p, abi.c_double_p, abi.c_double_p]
         L.uvs_imu_preintegrate.restype = C.c_int
         L.uvs_imu_last_device_ms.argtypes = [C.c_void_p]; L.uvs_imu_last_device_ms.restype = C.c_double
+        L.uvs_rp_create.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_void_p)]; L.uvs_rp_create.restype = C.c_int
+        L.uvs_rp_destroy.argtypes = [C.c_void_p]; L.uvs_rp_destroy.restype = None
+        L.uvs_rp_last_error.argtypes = [C.c_void_p]; L.uvs_rp_last_error.restype = C.c_char_p
+        L.uvs_rp_default_params.argtypes = [C.POINTER(abi.RpParams)]; L.uvs_rp_default_params.restype = None
+        L.uvs_rp_relative_pose.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.RpItem), C.POINTER(abi.RpParams), abi.c_u8_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.uvs_rp_relative_pose.restype = C.c_int
+        L.uvs_rp_last_device_ms.argtypes = [C.c_void_p, C.c_int]; L.uvs_rp_last_device_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -1712,3 +1720,80 @@ class ImuPreintegrator(_Handle):
         for frames in samples_per_window:
             out.append([self.block_dict(blocks[at + f]) for f in range(len(frames) - 1)]); at += len(frames) - 1
         return out
+
+
+class RelativePose(_Handle):
+    """Owns one `uvs_rp` handle: Estimator::relativePose -- the gates, the fundamental-matrix RANSAC of uvs_ft_reject and recoverPose -- for
+    batches of frame pairs (frame_l, WINDOW_SIZE) on one GPU.  The ten pairs of a window are ten items of one launch; a window's answer is its
+    first item with ok.
+
+    Fails loudly (RuntimeError) without a GPU -- there is no CPU path."""
+
+    _UNIT = "uvs_rp"
+    FILL = 0xA5        # what solve_raw puts into every byte of its outputs before the call: a refused call must leave it there
+
+    def __init__(self, device=0, max_items=2560, max_points=1024, **params):
+        self._create(device, int(max_items), int(max_points))
+        self.params = abi.rp_params(**params)
+        self.last_ms = 0.0
+        self.last_device_ms = (0.0, 0.0, 0.0)
+
+    def solve_raw(self, items, n_windows=None, null=(), n_items=None, params=None):
+        """-> (return code, item results [n] of abi.RP_ITEM_RESULT_DTYPE, list of final masks, window results [n_windows] of
+        abi.RP_WINDOW_RESULT_DTYPE) without raising: for the tests of the argument checks.  `null` names "items", "params", "mask",
+        "item_results", "window_results", or "left" / "right" (the point arrays of every item); n_items / n_windows override the counts."""
+        arr, keep = abi.rp_items_of(items, null)
+        nw = (max([int(it.get("window", 0)) for it in items], default=0) + 1) if n_windows is None else int(n_windows)
+        counts = [len(keep[2 * k]) for k in range(len(items))]
+        mask = np.full(max(sum(counts), 1), self.FILL, np.uint8)
+        res = np.frombuffer(bytearray(bytes([self.FILL]) * (max(len(items), 1) * abi.RP_ITEM_RESULT_DTYPE.itemsize)), abi.RP_ITEM_RESULT_DTYPE)
+        win = np.frombuffer(bytearray(bytes([self.FILL]) * (max(nw, 1) * abi.RP_WINDOW_RESULT_DTYPE.itemsize)), abi.RP_WINDOW_RESULT_DTYPE)
+        p = self.params if params is None else params
+        args = dict(items=arr, params=C.byref(p), mask=mask.ctypes.data_as(abi.c_u8_p), item_results=C.c_void_p(res.ctypes.data),
+                    window_results=C.c_void_p(win.ctypes.data))
+        for k in null:
+            if k in args:
+                args[k] = None
+        t0 = time.perf_counter()
+        rc = lib().uvs_rp_relative_pose(self._h, len(items) if n_items is None else int(n_items), args["items"], args["params"], args["mask"],
+                                        args["item_results"], nw, args["window_results"])
+        self.last_ms = (time.perf_counter() - t0) * 1e3       # the whole C-ABI call: checks, packing, upload, kernels, download
+        self.last_device_ms = tuple(float(lib().uvs_rp_last_device_ms(self._h, k)) for k in range(3))      # gate, RANSAC, recover
+        cut = np.cumsum(counts)[:-1] if counts else []
+        return rc, res[:len(items)], np.split(mask[:sum(counts)], cut), win[:max(nw, 0)]
+
+    def solve(self, items, n_windows=None):
+        """items: dicts with window, frame_l, seed, left [n, 2], right [n, 2] (abi.rp_items_of) -> (item results, a structured array of
+        abi.RP_ITEM_RESULT_DTYPE; the final recoverPose mask of every item; window results of abi.RP_WINDOW_RESULT_DTYPE)."""
+        rc, res, masks, win = self.solve_raw(items, n_windows)
+        if rc != abi.UVS_OK:
+            raise self._error("uvs_rp_relative_pose", rc)
+        return res, masks, win
+
+    @staticmethod
+    def corresponding(tracks, frame_l, frame_r=abi.WINDOW_SIZE):
+        """FeatureManager::getCorresponding: of the tracks (start_frame, points [n_frames, 2 or 3]), in feature order, those with
+        start_frame <= frame_l and start_frame + n_frames - 1 >= frame_r -> (left [n, 2], right [n, 2])."""
+        l, r = [], []
+        for start, pts in tracks:
+            pts = np.asarray(pts, np.float64)
+            if start <= frame_l and start + len(pts) - 1 >= frame_r:
+                l.append(pts[frame_l - start, :2]); r.append(pts[frame_r - start, :2])
+        return np.array(l, np.float64).reshape(-1, 2), np.array(r, np.float64).reshape(-1, 2)
+
+    @classmethod
+    def window_items(cls, windows, seeds=None):
+        """The WINDOW_SIZE items of every window: windows[w] is the window's track list; the seed of item (w, l) is seeds[w][l], or
+        w * WINDOW_SIZE + l."""
+        items = []
+        for w, tracks in enumerate(windows):
+            for l in range(abi.WINDOW_SIZE):
+                left, right = cls.corresponding(tracks, l)
+                items.append(dict(window=w, frame_l=l, seed=(w * abi.WINDOW_SIZE + l) if seeds is None else seeds[w][l], left=left, right=right))
+        return items
+
+    def relative_pose_windows(self, windows, seeds=None):
+        """windows: per window the tracks as (start_frame, per-frame points) in feature order.  One call for the ten pairs of every window
+        -> (l [n_windows] (-1: no pair passed), Rotation [n_windows, 3, 3], Translation [n_windows, 3], the per-item results, the masks)."""
+        res, masks, win = self.solve(self.window_items(windows, seeds), n_windows=len(windows))
+        return win["l"].copy(), win["Rotation"].copy(), win["Translation"].copy(), res, masks

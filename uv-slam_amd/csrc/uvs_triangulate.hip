@@ -11,8 +11,9 @@
 //                  reference's svd_A.  The rows are never stored: each goes through four Givens rotations into the 4 x 4 upper triangle T of
 //                  svd_A = Q T (10 doubles).  The right singular vectors of T are those of svd_A; they come from a one-sided Jacobi SVD of T
 //                  (Hestenes: columns rotated in the fixed order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) until a sweep rotates nothing, at most
-//                  kMaxSweeps sweeps).  Both steps are orthogonal transformations of svd_A itself -- svd_A^T svd_A is never formed, so the
-//                  condition number is not squared.  depth = V[2] / V[3] of the column of the smallest norm.
+//                  kMaxSweeps sweeps; both routines live in uvs_svd_dev.h, which uvs_relative_pose.hip shares).  Both steps are orthogonal
+//                  transformations of svd_A itself -- svd_A^T svd_A is never formed, so the condition number is not squared (DESIGN.md
+//                  3.19).  depth = V[2] / V[3] of the column of the smallest norm.
 //   k_tri_lines    lane per line: the two back-projected planes, the Pluecker line in the world, its orthonormal form.
 // uvs_tri_check_lines runs k_tri_cameras and k_tri_check (lane per line), uvs_tri_shift_depth runs k_tri_shift (lane per point).
 //
@@ -26,13 +27,12 @@
 
 #include "../../include/uvs_solver.h"
 #include "uvs_handle.h"
+#include "uvs_svd_dev.h"
 
 namespace uvstri {
 
 constexpr int kNF = UVS_NUM_FRAMES;
 constexpr int kThreads = 64;               // one wave per workgroup: 38 400 points are 600 workgroups over 256 compute units
-constexpr int kMaxSweeps = 30;             // a 4 x 4 triangle converges in 4 .. 7 sweeps; the cap only bounds a lane that holds NaNs
-constexpr double kEps = 2.220446049250313e-16;
 constexpr double kPi = 3.14159265358979323846;
 
 struct Cam { double R[3][3], t[3]; };      // camera -> world
@@ -90,23 +90,6 @@ __global__ void __launch_bounds__(kThreads) k_tri_cameras(const double* __restri
     }
 }
 
-// one row of svd_A into the upper triangle T by Givens rotations (x is destroyed)
-__device__ __forceinline__ void givens_row(double T[4][4], double x[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (x[j] != 0.0) {
-            const double a = T[j][j], b = x[j], h = sqrt(a * a + b * b), c = a / h, s = b / h;
-            T[j][j] = h;
-#pragma unroll
-            for (int m = j + 1; m < 4; ++m) {
-                const double tm = T[j][m], xm = x[m];
-                T[j][m] = c * tm + s * xm;
-                x[m] = c * xm - s * tm;
-            }
-        }
-    }
-}
-
 // ---- points: the DLT of feature_manager.cpp:437-478
 __global__ void __launch_bounds__(kThreads) k_tri_points(const double* __restrict__ cams, const int32_t* __restrict__ pt_window,
                                                        const int32_t* __restrict__ pt_start, const int32_t* __restrict__ pt_obs_begin,
@@ -139,49 +122,14 @@ __global__ void __launch_bounds__(kThreads) k_tri_points(const double* __restric
         double x0[4], x1[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) { x0[c] = f0 * P[2][c] - f2 * P[0][c]; x1[c] = f1 * P[2][c] - f2 * P[1][c]; }
-        givens_row(T, x0);
-        givens_row(T, x1);
+        uvssvd::givens_row(T, x0);
+        uvssvd::givens_row(T, x1);
     }
-    // one-sided Jacobi on the columns of T: T V = U Sigma
-    double V[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) V[r][c] = r == c ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { alpha += T[k][p] * T[k][p]; beta += T[k][q] * T[k][q]; gamma += T[k][p] * T[k][q]; }
-                if (fabs(gamma) > kEps * sqrt(alpha * beta)) {                  // false for a zero column and for NaN
-                    rotated = true;
-                    const double zeta = (beta - alpha) / (2.0 * gamma);
-                    const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double gp = T[k][p], gq = T[k][q];
-                        T[k][p] = c * gp - sn * gq; T[k][q] = sn * gp + c * gq;
-                        const double vp = V[k][p], vq = V[k][q];
-                        V[k][p] = c * vp - sn * vq; V[k][q] = sn * vp + c * vq;
-                    }
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-    double best = 0.0, v2 = 0.0, v3 = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        double nn = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) nn += T[k][c] * T[k][c];
-        if (c == 0 || nn < best || nn != nn) { best = nn; v2 = V[2][c]; v3 = V[3][c]; }
-    }
+    // one-sided Jacobi on the columns of T: T V = U Sigma (uvs_svd_dev.h)
+    double V[4][4], q[4];
+    UVS_JACOBI_COLUMNS(4, T, V);
+    uvssvd::smallest_column(T, V, q);
+    const double v2 = q[2], v3 = q[3];
     double d = v2 / v3;
     int fl = 0;
     if (!(fabs(d) <= 1.7976931348623157e308)) { fl = 2; d = init_depth; }      // not finite: the reference lets it through (stated deviation)

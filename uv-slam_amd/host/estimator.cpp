@@ -39,6 +39,7 @@ Estimator::~Estimator() {
     finishMarginalization();
     setDeviceTriangulation(false);
     setDeviceIntegration(false);
+    if (rp) uvs_rp_destroy(rp);
     uvs_destroy(solver); delete last_marginalization_info; for (auto* p : pre_integrations) delete p;
 }
 
@@ -59,6 +60,41 @@ void Estimator::setDeviceIntegration(bool on) {
     int rc = uvs_imu_create(0, WINDOW_SIZE + 1, 1 << 16, &imu);      // an interval is cut off at 10 s (skip): 1 << 16 samples hold a window of them at 200 Hz
     if (rc == UVS_OK && (rc = uvs_imu_set_noise(imu, ACC_N, GYR_N, ACC_W, GYR_W)) != UVS_OK) { uvs_imu_destroy(imu); imu = nullptr; }
     if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_imu_create: ") + uvs_status_string(rc));     // no CPU fallback once asked for
+}
+
+bool Estimator::relativePose(Eigen::Matrix3d& relative_R, Eigen::Vector3d& relative_T, int& l) {
+    if (!rp) {
+        if (!uvs_rp_create) throw std::runtime_error("relativePose: this back end has no uvs_rp_*");
+        const int rc = uvs_rp_create(0, WINDOW_SIZE, NUM_OF_F, &rp);
+        if (rc != UVS_OK) { rp = nullptr; throw std::runtime_error(std::string("uvs_rp_create: ") + uvs_status_string(rc)); }     // no CPU path
+    }
+    std::vector<double> left[WINDOW_SIZE], right[WINDOW_SIZE];
+    uvs_rp_item items[WINDOW_SIZE];
+    size_t n_pts = 0;
+    for (int i = 0; i < WINDOW_SIZE; ++i) {
+        const auto corres = f_manager.getCorresponding(i, WINDOW_SIZE);
+        for (const auto& c : corres) {
+            left[i].push_back(c.first(0)); left[i].push_back(c.first(1));
+            right[i].push_back(c.second(0)); right[i].push_back(c.second(1));
+        }
+        items[i] = uvs_rp_item{0, i, (int32_t)corres.size(), 0, rp_seed + (uint64_t)i, left[i].data(), right[i].data()};
+        n_pts += corres.size();
+    }
+    uvs_rp_params params;
+    uvs_rp_default_params(&params);
+    params.focal_length = FOCAL_LENGTH;
+    std::vector<uint8_t> mask(n_pts + 1);
+    uvs_rp_item_result results[WINDOW_SIZE];
+    uvs_rp_window_result win;
+    const int rc = uvs_rp_relative_pose(rp, WINDOW_SIZE, items, &params, mask.data(), results, 1, &win);
+    if (rc != UVS_OK) throw std::runtime_error(std::string("uvs_rp_relative_pose: ") + uvs_status_string(rc) + " / " + uvs_rp_last_error(rp));
+    if (win.l < 0) return false;
+    l = win.l;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) relative_R(r, c) = win.Rotation[3 * r + c];
+        relative_T(r) = win.Translation[r];
+    }
+    return true;
 }
 
 // One uvs_imu_preintegrate call for the listed slots: each IntegrationBase is integrated afresh over the samples recorded for its slot, from its

@@ -19,6 +19,12 @@
 #pragma weak uvs_imu_last_error
 #pragma weak uvs_imu_set_noise
 #pragma weak uvs_imu_preintegrate
+// ... and uvs_rp_*: Estimator::relativePose throws there.
+#pragma weak uvs_rp_create
+#pragma weak uvs_rp_destroy
+#pragma weak uvs_rp_last_error
+#pragma weak uvs_rp_default_params
+#pragma weak uvs_rp_relative_pose
 
 namespace std_msgs { struct Header { struct Stamp { double t = 0; double toSec() const { return t; } } stamp; }; }      // the one field of std_msgs::Header the estimator reads
 
@@ -118,6 +124,15 @@ class Estimator {
     void setDeviceIntegration(bool on);
     void integrateOnDevice(const int* slots, int n_slots);      // pre_integrations[slot] <- its recorded samples at its own linearized_ba / linearized_bg
     uvs_imu* imu = nullptr;
+    // The bootstrap's choice of its reference frame (estimator.cpp:448-477): the first frame l of the window whose pair (l, WINDOW_SIZE) has more than
+    // 20 correspondences, 30 px of average parallax and a relative pose with more than 12 inliers; relative_R, relative_T as solveRelativeRT returns
+    // them.  The device route only (uvs_rp_*): the ten pairs of f_manager.getCorresponding are the ten items of ONE uvs_rp_relative_pose call on a
+    // handle made by the first call; item l draws its RANSAC samples from rp_seed + l.  Throws when the handle cannot be made (no GPU, or a back end
+    // without uvs_rp_*) and when the call is refused.  initialStructure() does not call it yet: GlobalSFM, the per-frame PnP and visualInitialAlign
+    // have no mirror.
+    bool relativePose(Eigen::Matrix3d& relative_R, Eigen::Vector3d& relative_T, int& l);
+    uvs_rp* rp = nullptr;
+    uint64_t rp_seed = 0;
     // wall-clock spent inside optimization() (sums over the calls): whole call, uvs::Solve() alone, marginalization alone
     double optimization_ms = 0, solve_ms = 0, marginalize_ms = 0; int optimization_calls = 0;
 };

@@ -187,6 +187,15 @@ class FeatureManager {
         views(tracks.back()).push_back(view);
         return false;
     }
+    // The normalised points (x, y, 1) of every track that spans both frames, in feature order: first = its view in frame_count_l, second = its
+    // view in frame_count_r (feature_manager.cpp:181-200).
+    std::vector<std::pair<Eigen::Vector3d, Eigen::Vector3d>> getCorresponding(int frame_count_l, int frame_count_r) const {
+        std::vector<std::pair<Eigen::Vector3d, Eigen::Vector3d>> corres;
+        for (const FeaturePerId& it : feature)
+            if (it.start_frame <= frame_count_l && it.endFrame() >= frame_count_r)
+                corres.emplace_back(it.feature_per_frame[frame_count_l - it.start_frame].point, it.feature_per_frame[frame_count_r - it.start_frame].point);
+        return corres;
+    }
     // Takes the measurements of the image that just arrived and decides whether the SECOND-NEWEST frame is a keyframe (then the oldest
     // frame will be marginalized, otherwise the second-newest is dropped): yes while the window is filling, when fewer than 20 tracks
     // continued, or when the tracks spanning frames frame_count-2 / frame_count-1 moved by MIN_PARALLAX on average (:73-158).
